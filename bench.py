@@ -1,6 +1,6 @@
 """Benchmark of the ASE PPO-update hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision auto|f16gpx3|f16gp32|f32|bf16|...] [--no-graph]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision auto|f16gpx3|f16gp32|f32|bf16|...] [--no-graph] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -703,6 +703,43 @@ HEADLINE_CANDIDATES = ['f16gpx3', 'f16gp32', 'f32']     # fastest first; the hea
 STRICT_CANDIDATES = ['bf16x3', 'f32']                    # strict mode: true |delta| / |ref| <= 1e-4 on every loss scalar, no floor
 
 
+DUMP_BUDGET = 64 << 20       # --dump-outputs: bytes of .npy data at most
+DUMP_MAX_ELEMS = 4 << 20     # one array above this many elements is dumped as a fixed, seeded sample of its flat entries
+
+
+def timed_outputs(agent, info):
+    """What the last timed step handed its caller, copied to the host right after it: the per-optimisation-step results of
+    agent.update() (float64, one row per step) and the state the update wrote - the flat parameter buffer and the model's floating
+    buffers (running normalisers), float32.  Arrays above DUMP_MAX_ELEMS are sampled at seeded positions (the same for the same
+    size), so that the same command line dumps the same entries on every build."""
+    import numpy as np
+    out = {}
+    for k, v in sorted(info.items()):
+        if v and all(torch.is_tensor(x) or isinstance(x, (int, float)) for x in v):
+            out['update.' + k] = np.stack([x.detach().double().cpu().numpy() if torch.is_tensor(x) else np.float64(x) for x in v])
+    net = agent.model.a2c_network
+    out['params'] = net.flat_params.detach().float().cpu().numpy()
+    for k, b in agent.model.named_buffers():
+        if b.is_floating_point():
+            out['buffer.' + k] = b.detach().float().cpu().numpy()
+    for k, a in list(out.items()):
+        if a.size > DUMP_MAX_ELEMS:
+            pick = np.sort(np.random.default_rng(a.size).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            out[k + '.sample'] = a.reshape(-1)[pick]
+            out[k + '.sample_index'] = pick.astype(np.float64)
+    out = {k: a for k, a in out.items() if a.size <= DUMP_MAX_ELEMS}
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BUDGET, f'--dump-outputs: {total} bytes over the {DUMP_BUDGET} budget'
+    return out
+
+
+def write_outputs(outputs, d):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for k, a in outputs.items():
+        np.save(os.path.join(d, k + '.npy'), a)
+
+
 def _mode_ok(par):
     return bool(par) and _state_ok(par['fresh'], 'fresh') and _state_ok(par['stress'], 'stress')
 
@@ -774,6 +811,8 @@ def measure_mode(args, precision, device, world, rank, use_graph):
     if args.gc == 'freeze':
         import gc
         gc.enable()
+    # (before the instrumented update below moves the weights on)
+    outputs = timed_outputs(agent, info) if args.dump_outputs and rank == 0 else None
     ms_tail = sum(a.elapsed_time(b) for a, b in tail_marks[-args.steps:]) / args.steps
     if args.verbose and rank == 0:
         try:
@@ -859,7 +898,7 @@ def measure_mode(args, precision, device, world, rank, use_graph):
                              'tflops': round(v['flops'] / (v['ms'] * 1e-3) / 1e12, 1)} for k, v in summ.items()},
             'hbm_kernels': tb.hbm_summary()}
     return {'precision': precision, 'agent': agent, 'cfg': cfg, 'value': value, 'ms_per_step': ms_per_step, 'ms_tail': ms_tail,
-            'last': last, 'roofline': roof, 'B': B, 'Bl': Bl, 'weak': weak,
+            'last': last, 'roofline': roof, 'B': B, 'Bl': Bl, 'weak': weak, 'outputs': outputs,
             'grad_scale': agent.engine.gs}
 
 
@@ -913,7 +952,11 @@ def main():
     ap.add_argument('--gc', default='freeze', choices=['on', 'freeze'],
                     help="'freeze' (default; the agents' config['manual_gc']): gc.freeze() + gc.disable() around the timed updates (no "
                          "generation-2 pass of Python's collector inside an update); 'on': leave the collector alone")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (update results, weights, normalisers) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -987,6 +1030,8 @@ def main():
         torch.cuda.empty_cache()
     precision = head['precision']
     agent, cfg = head['agent'], head['cfg']
+    if head['outputs'] is not None:
+        write_outputs(head.pop('outputs'), args.dump_outputs)
     B, Bl, weak = head['B'], head['Bl'], head['weak']
 
     # ---- more modes on request (parity in both states + throughput; detail file)

@@ -172,35 +172,41 @@ def test_configure_sets_the_queue_count_once_and_respects_the_user(monkeypatch):
     """ase_amd.configure(): importing the package changes nothing; configure() exports GPU_MAX_HW_QUEUES before HIP
     initialises, leaves a user's value alone, and says what happened in the note the bench line carries."""
     import importlib
+    import torch
     import ase_amd
-    monkeypatch.delenv('GPU_MAX_HW_QUEUES', raising=False)
+    monkeypatch.setenv('GPU_MAX_HW_QUEUES', '1')         # (records the session's own value, restored at teardown)
+    monkeypatch.delenv('GPU_MAX_HW_QUEUES')
+    # (earlier tests of the same session may have initialised HIP: what configure() does after that is checked below)
+    monkeypatch.setattr(torch.cuda, 'is_initialized', lambda: False)
     importlib.reload(ase_amd)
     assert 'GPU_MAX_HW_QUEUES' not in os.environ and not ase_amd.hw_queues_applied and 'not called' in ase_amd.hw_queue_note
     assert ase_amd.configure() is True
-    assert os.environ['GPU_MAX_HW_QUEUES'] == '4' and ase_amd.hw_queues_applied and 'set by ase_amd.configure()' in ase_amd.hw_queue_note
-    monkeypatch.setenv('GPU_MAX_HW_QUEUES', '6')
-    assert ase_amd.configure(hw_queues='3') is True
-    assert os.environ['GPU_MAX_HW_QUEUES'] == '6' and 'set by the user' in ase_amd.hw_queue_note
-    import torch
+    assert os.environ['GPU_MAX_HW_QUEUES'] == ase_amd.HW_QUEUES_DEFAULT == '2' and ase_amd.hw_queues_applied and 'set by ase_amd.configure()' in ase_amd.hw_queue_note
+    monkeypatch.setenv('GPU_MAX_HW_QUEUES', '1')
+    assert ase_amd.configure(hw_queues='2') is True
+    assert os.environ['GPU_MAX_HW_QUEUES'] == '1' and 'set by the user' in ase_amd.hw_queue_note
+    monkeypatch.delenv('GPU_MAX_HW_QUEUES')
+    monkeypatch.setattr(torch.cuda, 'is_initialized', lambda: True)
+    assert ase_amd.configure() is False
+    assert 'GPU_MAX_HW_QUEUES' not in os.environ and not ase_amd.hw_queues_applied and 'WARNING' in ase_amd.hw_queue_note
     n = torch.get_num_threads()
     ase_amd.configure(cpu_threads=1)
     assert torch.get_num_threads() == 1
     torch.set_num_threads(n)
 
 
-def test_cfg_tables_follow_the_reference_yaml():
-    """ase_amd/cfg: the hyper-parameter tables are the reference's yaml files (read here when /root/reference is mounted; the
-    GPU box compares nothing), numeric strings of PyYAML ('2e-5') normalised."""
+def test_cfg_tables_follow_the_reference_yaml(golden_dir):
+    """ase_amd/cfg: the hyper-parameter tables are the reference's yaml files (their layer widths / activations and scalar
+    config entries, as the yaml loader returns them, stored in tests/golden/reference_cfg.json by oracle/make_golden_cfg.py),
+    numeric strings of PyYAML ('2e-5') normalised."""
     from ase_amd import cfg as C
     net, conf = C.get('ase')
     assert isinstance(conf['learning_rate'], float) and net['mlp']['units'] == [1024, 1024, 512]
     assert C.normalize({'learning_rate': '2e-5', 'disc_weight_decay': '0.0001'}) == {'learning_rate': 2e-5, 'disc_weight_decay': 1e-4}
-    ref_dir = '/root/reference/ase/data/cfg/train/rlg'
-    if not os.path.isdir(ref_dir):
-        return
-    import yaml
-    for kind, fn in (('ase', 'ase_humanoid.yaml'), ('amp', 'amp_humanoid.yaml'), ('hrl', 'hrl_humanoid.yaml')):
-        ref = yaml.safe_load(open(os.path.join(ref_dir, fn)))['params']
+    golden = json.load(open(os.path.join(golden_dir, 'reference_cfg.json')))
+    assert set(golden) == {'ase', 'amp', 'hrl'}
+    for kind in ('ase', 'amp', 'hrl'):
+        ref = golden[kind]
         net, conf = C.get(kind)
         for part in ('mlp', 'disc', 'enc'):
             if part in ref['network']:
@@ -210,3 +216,29 @@ def test_cfg_tables_follow_the_reference_yaml():
         for k, v in rc.items():
             if k in conf and isinstance(v, (int, float, bool, str)) and k not in ('name', 'llc_config'):
                 assert conf[k] == v, (kind, k, conf[k], v)
+
+
+def test_bench_dump_outputs_are_float_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs: the update's per-step results as float64 rows, the weights and normalisers as float32, an array
+    above the element cap replaced by a sample whose positions depend on its size only, the whole dump within 64 MB."""
+    import types
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    model = torch.nn.Module()
+    model.register_buffer('running_mean', torch.arange(5, dtype=torch.float64))
+    model.register_buffer('count', torch.tensor(3))
+    model.a2c_network = types.SimpleNamespace(flat_params=torch.randn(bench.DUMP_MAX_ELEMS + 1000))
+    agent = types.SimpleNamespace(model=model)
+    info = {'actor_loss': [torch.tensor(1.5), torch.tensor(2.5)], 'last_lr': [2e-5, 2e-5], 'note': ['x', 'y']}
+    out = bench.timed_outputs(agent, info)
+    assert set(out) == {'update.actor_loss', 'update.last_lr', 'buffer.running_mean', 'params.sample', 'params.sample_index'}
+    assert out['update.actor_loss'].dtype == np.float64 and out['update.actor_loss'].tolist() == [1.5, 2.5]
+    assert out['buffer.running_mean'].dtype == np.float32 and out['params.sample'].dtype == np.float32
+    idx = out['params.sample_index'].astype(np.int64)
+    assert len(idx) == bench.DUMP_MAX_ELEMS and np.all(np.diff(idx) > 0)
+    assert np.array_equal(out['params.sample'], model.a2c_network.flat_params.numpy()[idx])
+    assert np.array_equal(bench.timed_outputs(agent, info)['params.sample_index'], out['params.sample_index'])
+    assert sum(a.nbytes for a in out.values()) <= bench.DUMP_BUDGET
+    bench.write_outputs(out, str(tmp_path / 'dump'))
+    assert sorted(os.listdir(tmp_path / 'dump')) == sorted(k + '.npy' for k in out)
