@@ -50,6 +50,7 @@ class HipBackend:
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.lib = L.get()
         self._head_scratch = torch.zeros(L.PPO_SCRATCH, dtype=torch.float64, device=self.device)   # (zeroed: it ends in a ticket word)
+        self._head_scratch_ls = None          # the learned log-std's wider slabs (ASE_PPO_SCRATCH_LS), on first use
 
     # ------------------------------------------------------------------ helpers
     def _stream(self):
@@ -308,16 +309,28 @@ class HipBackend:
 
     def ppo_head(self, mu, value, mb, new_z, logstd, d_mu, d_value, db_mu, db_value, acc, M, m_global, act_dim,
                  z_dim, masked, div_on, mu_tanh, clip_value, e_clip, critic_coef, bounds_coef, div_coef, div_tar,
-                 mu_out=None, grad_scale=1.0, dyn=None):
+                 mu_out=None, grad_scale=1.0, dyn=None, ls_mode=L.LS_FROZEN, d_logstd=None, db_logstd=None, entropy_coef=0.0):
+        """ls_mode (L.LS_*): LS_FROZEN - logstd f32[act_dim], no log-std gradient (the defaults reproduce the frozen call);
+        LS_VECTOR - logstd f32[act_dim] learned; LS_ROWS - logstd f32[rows, >= act_dim] (a strided view, e.g. the sigma
+        columns of the stacked head output).  Learned modes: d_logstd (nullable, d_mu's dtype) receives the per-row
+        d loss / d logstd times grad_scale, db_logstd (nullable, f32[act_dim]) += its column sums."""
+        scratch = self._head_scratch if ls_mode == L.LS_FROZEN else self.reserve_learned_logstd()
         L.check(self.lib.ase_hip_ppo_head(
             _ptr(mu), _ld(mu), _ptr(value), _ld(value), _ptr(mb['actions']), _ptr(mb['mu']), _ptr(mb['sigma']),
             _ptr(mb['old_logp_actions']), _ptr(mb['advantages']), _ptr(mb.get('old_values')), _ptr(mb['returns']),
             _ptr(mb.get('rand_action_mask')), _ptr(mb.get('ase_latents')), _ptr(new_z), _ptr(logstd),
             _ptr(d_mu), _ld(d_mu), _ptr(d_value), _ld(d_value), _ptr(db_mu), _ptr(db_value), _ptr(mu_out), _ptr(acc),
-            _ptr(self._head_scratch),
+            _ptr(scratch),
             M, m_global, act_dim, z_dim, int(masked), int(div_on), int(mu_tanh), int(clip_value),
             float(e_clip), float(critic_coef), float(bounds_coef), float(div_coef), float(div_tar), float(grad_scale),
-            _ptr(dyn), _code(d_mu.dtype), self._stream()), "ppo_head")
+            _ptr(dyn), int(ls_mode), _ld(logstd) if ls_mode == L.LS_ROWS else 0, _ptr(d_logstd), _ld(d_logstd),
+            _ptr(db_logstd), float(entropy_coef), _code(d_mu.dtype), self._stream()), "ppo_head")
+
+    def reserve_learned_logstd(self):
+        """The wider workspace of ppo_head's learned log-std modes (allocated once, before any launch program is recorded)."""
+        if self._head_scratch_ls is None:
+            self._head_scratch_ls = torch.zeros(L.PPO_SCRATCH_LS, dtype=torch.float64, device=self.device)
+        return self._head_scratch_ls
 
     def disc_head(self, logit, d_logit, db_logit, acc, amb, amb_global, disc_coef, grad_scale=1.0, dyn=None):
         L.check(self.lib.ase_hip_disc_head(_ptr(logit), _ld(logit), _ptr(d_logit), _ld(d_logit), _ptr(db_logit),
@@ -443,8 +456,10 @@ class HipBackend:
         L.check(self.lib.ase_hip_normalize_rows(_ptr(x), _ld(x), _ptr(y), _ld(y), n, dim, self._stream()), "normalize_rows")
 
     def sample_actions(self, mu, logstd, rand_probs, rng_state, mu_out, sigma_out, actions, neglogp, rand_mask, n, act_dim,
-                       mu_tanh=False):
-        L.check(self.lib.ase_hip_sample_actions(_ptr(mu), _ld(mu), _ptr(logstd), _ptr(rand_probs), _ptr(rng_state), _ptr(mu_out),
+                       mu_tanh=False, logstd_rows=False):
+        """logstd_rows: logstd is a per-row [n, >= act_dim] view (the sigma head's output) instead of one f32[act_dim] vector."""
+        L.check(self.lib.ase_hip_sample_actions(_ptr(mu), _ld(mu), _ptr(logstd), _ld(logstd) if logstd_rows else 0,
+                                                _ptr(rand_probs), _ptr(rng_state), _ptr(mu_out),
                                                 _ptr(sigma_out), _ptr(actions), _ptr(neglogp), _ptr(rand_mask), n, act_dim,
                                                 int(mu_tanh), self._stream()), "sample_actions")
 

@@ -32,23 +32,39 @@ struct PpoArgs {
     float e_clip, critic_coef, bounds_coef, div_coef, div_tar;
     float gs, inv_gs;             // the stored head gradients carry the gradient scale (f16 storage), the bias gradients do not
     float* gs_dev;                // nullable: scale record {factor on top of gs, overflow count} (the dynamic loss scale, common.h)
+    // learned log-std (LS != 0; appended so that the frozen instantiation reads its arguments where it always did)
+    int64_t ld_ls;                // per-row mode: row stride of logstd
+    void* d_ls; int64_t ld_dls;   // nullable: per-row d logstd, storage T, scaled by gs like d_mu
+    float* db_ls;                 // nullable: column sums of d logstd (the vector's gradient / the sigma head's bias gradient)
+    float entropy_coef;
 };
 
-// per-workgroup partials: 7 loss sums, then 64 + 1 head-bias column sums (mu columns, value)
+// per-workgroup partials: 7 loss sums, then 64 + 1 head-bias column sums (mu columns, value); a learned log-std adds
+// 64 column sums of d logstd
 constexpr int kPpoSlots = 72;
+constexpr int kPpoSlotsLs = kPpoSlots + 64;
+
+// log-std of the policy (network space.continuous): LS_FROZEN - the frozen vector sigma (learn_sigma False); LS_VECTOR - the
+// learned state-independent vector (fixed_sigma True); LS_ROWS - per-state, the sigma head's output row (fixed_sigma False)
+enum { LS_FROZEN = 0, LS_VECTOR = 1, LS_ROWS = 2 };
 
 // LPR lanes per row (act_dim <= LPR: 32 for the humanoid's 28 / 31 actions, 64 for the HRL high-level policy whose action
 // is the 64-d latent), 256 / LPR rows per 256-thread block.
 // (8 waves per SIMD = at most 64 registers, at the price of ~10 spilled dwords per lane: a latency-bound kernel on the step's critical
 //  path that starts while other branches' matrix kernels hold every CU - their two waves per SIMD leave 64 registers (round 6), and at
 //  72 this kernel waited for a CU to drain: 18 us alone, 111 us behind a resident grid)
-template <typename T, int LPR>
+// LS: the log-std mode (LS_*).  A learned log-std adds dL/dlogstd = w (-g ratio (1 - d^2) - entropy_coef) per row and action
+// (neglogp through the ratio, and the entropy bonus; the KL sees sigma detached): stored per row in T (LS_ROWS) and summed per
+// column through the same slabs as the bias gradients.
+template <typename T, int LPR, int LS>
 __global__ __launch_bounds__(256, 8) void ppo_head_kernel(PpoArgs p) {
     constexpr int ROWS = 256 / LPR;
+    constexpr int NSLOT = LS == LS_FROZEN ? kPpoSlots : kPpoSlotsLs;
     __shared__ double sm[7 * 16];
     __shared__ float sdb[ROWS][LPR + 1];
+    __shared__ float sdl[LS == LS_FROZEN ? 1 : ROWS][LPR];
     const int lane = threadIdx.x & (LPR - 1), rib = threadIdx.x / LPR;
-    float gm_out = 0.f, gm2_out = 0.f, dv_out = 0.f;
+    float gm_out = 0.f, gm2_out = 0.f, dv_out = 0.f, gl_out = 0.f;
     const int D = p.act_dim;
     if (p.gs_dev) {
         p.gs *= *p.gs_dev;
@@ -69,7 +85,7 @@ __global__ __launch_bounds__(256, 8) void ppo_head_kernel(PpoArgs p) {
             const float raw = p.mu[(int64_t)i * p.ld_mu + lane];
             m = p.mu_tanh ? tanhf(raw) : raw;
             a = p.actions[(int64_t)i * D + lane];
-            ls = p.logstd[lane];
+            ls = LS == LS_ROWS ? p.logstd[(int64_t)i * p.ld_ls + lane] : p.logstd[lane];
             sg = expf(ls);
             d = (a - m) / sg;
             omu = p.old_mu[(int64_t)i * D + lane];
@@ -101,6 +117,18 @@ __global__ __launch_bounds__(256, 8) void ppo_head_kernel(PpoArgs p) {
         const float kl_row = group_sum<LPR>(klj);
 
         float gm = w * g * ratio * d / sg + p.bounds_coef * w * 2.f * (bh + bl);
+        if constexpr (LS != LS_FROZEN) {
+            if (act_ok) {
+                const T ol = from_f32<T>(p.gs * (w * (-g * ratio * (1.f - d * d) - p.entropy_coef)));
+                if (p.d_ls) {
+                    reinterpret_cast<T*>(p.d_ls)[(int64_t)i * p.ld_dls + lane] = ol;
+                    // the diversity rows' log-std enters no loss term
+                    if (p.div_on) reinterpret_cast<T*>(p.d_ls)[(int64_t)(p.M + i) * p.ld_dls + lane] = from_f32<T>(0.f);
+                }
+                bad |= ovf_hit1(ol);
+                gl_out += p.inv_gs * to_f32(ol);
+            }
+        }
 
         // diversity (learning/ase_agent.py:445-467)
         float div_row = 0.f, gm2 = 0.f, m2 = 0.f;
@@ -178,15 +206,25 @@ __global__ __launch_bounds__(256, 8) void ppo_head_kernel(PpoArgs p) {
     // slab - 1024 workgroups adding to the same 40 addresses with atomics cost ~20 us of this kernel; ppo_head_fold_kernel
     // folds the slabs.
     double* const slabs = p.scratch + 8;
-    double* mine = slabs + (int64_t)blockIdx.x * kPpoSlots;
+    double* mine = slabs + (int64_t)blockIdx.x * NSLOT;
     sdb[rib][lane] = gm_out + gm2_out;
     if (lane == 0) sdb[rib][LPR] = dv_out;
+    if constexpr (LS != LS_FROZEN) sdl[rib][lane] = gl_out;
     __syncthreads();
     if (threadIdx.x < LPR + 1) {
         float t = 0.f;
 #pragma unroll
         for (int q = 0; q < ROWS; ++q) t += sdb[q][threadIdx.x];
         mine[7 + (threadIdx.x < LPR ? threadIdx.x : 64)] = (double)t;
+    }
+    if constexpr (LS != LS_FROZEN) {
+        if (threadIdx.x >= 128 && threadIdx.x < 128 + LPR) {
+            const int c = threadIdx.x - 128;
+            float t = 0.f;
+#pragma unroll
+            for (int q = 0; q < ROWS; ++q) t += sdl[q][c];
+            mine[kPpoSlots + c] = (double)t;
+        }
     }
     block_sum<7>(part, sm);
     if (threadIdx.x == 0) {
@@ -198,26 +236,28 @@ __global__ __launch_bounds__(256, 8) void ppo_head_kernel(PpoArgs p) {
 // second stage (a kernel boundary is the cheapest agent-scope release / acquire there is: a per-workgroup release fence
 // - one L2 write-back each - made the 1024-workgroup kernel 6x slower): a few workgroups fold the slabs into the accumulators
 // and the head-bias gradients.  Thread (c, g) sums slot c over the slabs b = lo + g, lo + g + 4, ...; the four groups meet in LDS.
+// NS: the slab pitch (kPpoSlots, or kPpoSlotsLs with the column sums of d logstd in slots 72.. -> db_ls)
+template <int NS>
 __global__ __launch_bounds__(256) void ppo_head_fold_kernel(const double* __restrict__ slabs, int nblocks, double* __restrict__ acc,
                                                             float* __restrict__ db_mu, float* __restrict__ db_value, int act_dim,
-                                                            int div_on) {
+                                                            int div_on, float* __restrict__ db_ls) {
     // gridDim.x workgroups share the slabs; 8 independent loads in flight per thread (a single chain of dependent loads over
     // 1024 slabs took 129 us)
-    __shared__ double fold[4][kPpoSlots];
+    __shared__ double fold[4][NS];
     const int c = threadIdx.x & 63, g4 = threadIdx.x >> 6;
     const int per = (nblocks + gridDim.x - 1) / gridDim.x, lo = blockIdx.x * per, hi = min(nblocks, lo + per);
-    for (int cc = c; cc < kPpoSlots; cc += 64) {
+    for (int cc = c; cc < NS; cc += 64) {
         double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int b = lo + g4;
         for (; b + 28 < hi; b += 32) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] += slabs[(int64_t)(b + 4 * u) * kPpoSlots + cc];
+            for (int u = 0; u < 8; ++u) t[u] += slabs[(int64_t)(b + 4 * u) * NS + cc];
         }
-        for (; b < hi; b += 4) t[0] += slabs[(int64_t)b * kPpoSlots + cc];
+        for (; b < hi; b += 4) t[0] += slabs[(int64_t)b * NS + cc];
         fold[g4][cc] = ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]));
     }
     __syncthreads();
-    if (threadIdx.x < kPpoSlots) {
+    if (threadIdx.x < NS) {
         const int cc = threadIdx.x;
         const double t = fold[0][cc] + fold[1][cc] + fold[2][cc] + fold[3][cc];
         if (cc < 7) {
@@ -228,6 +268,7 @@ __global__ __launch_bounds__(256) void ppo_head_fold_kernel(const double* __rest
             if (j < act_dim) atomic_add_f32(db_mu + j, (float)t);
             else if (j == 64 && db_value) atomic_add_f32(db_value, (float)t);
         }
+        if (NS > 72 && cc >= 72 && cc - 72 < act_dim && db_ls) atomic_add_f32(db_ls + (cc - 72), (float)t);
     }
 }
 
@@ -587,7 +628,8 @@ extern "C" int ase_hip_ppo_head(const float* mu, int64_t ld_mu, const float* val
                                 const float* logstd, void* d_mu, int64_t ld_dmu, void* d_value, int64_t ld_dv,
                                 float* db_mu, float* db_value, float* mu_out, double* acc, double* scratch, int M, int m_global, int act_dim, int z_dim, int masked,
                                 int div_on, int mu_tanh, int clip_value, float e_clip, float critic_coef,
-                                float bounds_coef, float div_coef, float div_tar, float grad_scale, float* grad_scale_dev, int dtype,
+                                float bounds_coef, float div_coef, float div_tar, float grad_scale, float* grad_scale_dev,
+                                int ls_mode, int64_t ld_ls, void* d_ls, int64_t ld_dls, float* db_ls, float entropy_coef, int dtype,
                                 void* stream) {
     ASE_CHECK_ARG(mu && value && mb_actions && mb_old_mu && mb_old_sigma && mb_old_logp && mb_adv && mb_return &&
                       logstd && d_mu && d_value && acc && scratch && M > 0 && m_global >= M,
@@ -597,6 +639,9 @@ extern "C" int ase_hip_ppo_head(const float* mu, int64_t ld_mu, const float* val
     ASE_CHECK_ARG(!div_on || (mb_z && new_z && z_dim > 0), "ppo_head: diversity loss without latents");
     ASE_CHECK_ARG(!clip_value || mb_old_value, "ppo_head: clip_value without old values");
     ASE_CHECK_ARG(grad_scale > 0.f, "ppo_head: grad_scale must be positive");
+    ASE_CHECK_ARG(ls_mode >= LS_FROZEN && ls_mode <= LS_ROWS, "ppo_head: log-std mode %d", ls_mode);
+    ASE_CHECK_ARG(ls_mode != LS_ROWS || ld_ls >= act_dim, "ppo_head: per-row log-std stride %lld < act_dim", (long long)ld_ls);
+    ASE_CHECK_ARG(!d_ls || (ls_mode != LS_FROZEN && ld_dls >= act_dim), "ppo_head: bad d logstd operand");
     PpoArgs p;
     p.mu = mu; p.ld_mu = ld_mu; p.value = value; p.ld_v = ld_v;
     p.actions = mb_actions; p.old_mu = mb_old_mu; p.old_sigma = mb_old_sigma; p.old_logp = mb_old_logp;
@@ -605,17 +650,30 @@ extern "C" int ase_hip_ppo_head(const float* mu, int64_t ld_mu, const float* val
     p.acc = acc; p.scratch = scratch; p.M = M; p.m_global = m_global; p.act_dim = act_dim; p.z_dim = z_dim; p.masked = masked;
     p.div_on = div_on; p.mu_tanh = mu_tanh; p.clip_value = clip_value; p.e_clip = e_clip; p.critic_coef = critic_coef;
     p.bounds_coef = bounds_coef; p.div_coef = div_coef; p.div_tar = div_tar; p.gs = grad_scale; p.inv_gs = 1.f / grad_scale; p.gs_dev = grad_scale_dev;
+    p.ld_ls = ld_ls; p.d_ls = d_ls; p.ld_dls = ld_dls; p.db_ls = db_ls; p.entropy_coef = entropy_coef;
     const int rows = act_dim <= 32 ? 8 : 4;         // rows per workgroup (32 / 64 lanes per row)
-    const dim3 grid(min((M + rows - 1) / rows, 1024));       // scratch: (1024 x 72 + 1) doubles, the ticket word zero between launches
+    const dim3 grid(min((M + rows - 1) / rows, 1024));       // scratch: 1024 x 72 (learned log-std: 1024 x 136) + 8 doubles
     const int rc = ase_dispatch_storage(dtype, [&](auto tag) {
         typedef typename decltype(tag)::type T;
-        if (act_dim <= 32) ASE_LAUNCH((ppo_head_kernel<T, 32>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else ASE_LAUNCH((ppo_head_kernel<T, 64>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        if (ls_mode == LS_FROZEN) {
+            if (act_dim <= 32) ASE_LAUNCH((ppo_head_kernel<T, 32, LS_FROZEN>), grid, dim3(256), 0, (hipStream_t)stream, p);
+            else ASE_LAUNCH((ppo_head_kernel<T, 64, LS_FROZEN>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        } else if (ls_mode == LS_VECTOR) {
+            if (act_dim <= 32) ASE_LAUNCH((ppo_head_kernel<T, 32, LS_VECTOR>), grid, dim3(256), 0, (hipStream_t)stream, p);
+            else ASE_LAUNCH((ppo_head_kernel<T, 64, LS_VECTOR>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        } else {
+            if (act_dim <= 32) ASE_LAUNCH((ppo_head_kernel<T, 32, LS_ROWS>), grid, dim3(256), 0, (hipStream_t)stream, p);
+            else ASE_LAUNCH((ppo_head_kernel<T, 64, LS_ROWS>), grid, dim3(256), 0, (hipStream_t)stream, p);
+        }
         return ASE_OK;
     });
     ASE_CHECK_ARG(rc == ASE_OK, "ppo_head: bad dtype %d", dtype);
-    ASE_LAUNCH(ppo_head_fold_kernel, dim3(grid.x >= 64 ? 8 : 1), dim3(256), 0, (hipStream_t)stream, (const double*)(scratch + 8), (int)grid.x, acc, db_mu,
-               db_value, act_dim, div_on);
+    if (ls_mode == LS_FROZEN)
+        ASE_LAUNCH(ppo_head_fold_kernel<kPpoSlots>, dim3(grid.x >= 64 ? 8 : 1), dim3(256), 0, (hipStream_t)stream, (const double*)(scratch + 8),
+                   (int)grid.x, acc, db_mu, db_value, act_dim, div_on, (float*)nullptr);
+    else
+        ASE_LAUNCH(ppo_head_fold_kernel<kPpoSlotsLs>, dim3(grid.x >= 64 ? 8 : 1), dim3(256), 0, (hipStream_t)stream, (const double*)(scratch + 8),
+                   (int)grid.x, acc, db_mu, db_value, act_dim, div_on, db_ls);
     ASE_CHECK_LAUNCH("ppo_head");
     return ASE_OK;
 }

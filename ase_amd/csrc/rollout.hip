@@ -139,7 +139,7 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t offset, 
 //   mu (optionally tanh, learning/hrl_network_builder.py:26-29) -> a = mu + sigma * N(0, 1) -> neglogp(a) -> eps-greedy:
 //   rows whose Bernoulli(p_row) draw is 0 take the deterministic action mu (the stored neglogp stays the sampled one).
 __global__ __launch_bounds__(256) void sample_actions_kernel(const float* __restrict__ mu, int64_t ld_mu,
-                                                             const float* __restrict__ logstd,
+                                                             const float* __restrict__ logstd, int64_t ld_logstd,
                                                              const float* __restrict__ rand_probs,
                                                              const uint64_t* __restrict__ rng, float* __restrict__ mu_out,
                                                              float* __restrict__ sigma_out, float* __restrict__ actions,
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void sample_actions_kernel(const float* __rest
     if (lane < A) {
         m = mu[(int64_t)r * ld_mu + lane];
         if (mu_tanh) m = tanhf(m);
-        ls = logstd[lane];
+        ls = logstd[(int64_t)r * ld_logstd + lane];      // ld_logstd 0: one vector for every row
         s = expf(ls);
         a = m + s * philox_normal(seed, off, (uint64_t)r * A + lane);
         const float d = (a - m) / s;
@@ -291,12 +291,12 @@ extern "C" int ase_hip_normalize_rows(const float* x, int64_t ld_x, float* y, in
     return ASE_OK;
 }
 
-extern "C" int ase_hip_sample_actions(const float* mu, int64_t ld_mu, const float* logstd, const float* rand_probs,
-                                      uint64_t* rng_state, float* mu_out, float* sigma_out, float* actions,
+extern "C" int ase_hip_sample_actions(const float* mu, int64_t ld_mu, const float* logstd, int64_t ld_logstd,
+                                      const float* rand_probs, uint64_t* rng_state, float* mu_out, float* sigma_out, float* actions,
                                       float* neglogp, float* rand_mask, int n, int act_dim, int mu_tanh, void* stream) {
     ASE_CHECK_ARG(mu && logstd && rng_state && mu_out && sigma_out && actions && neglogp && n > 0 && act_dim >= 1 &&
-                      act_dim <= 64 && ld_mu >= act_dim, "sample_actions: bad operand");
-    ASE_LAUNCH(sample_actions_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, mu, ld_mu, logstd,
+                      act_dim <= 64 && ld_mu >= act_dim && (ld_logstd == 0 || ld_logstd >= act_dim), "sample_actions: bad operand");
+    ASE_LAUNCH(sample_actions_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, mu, ld_mu, logstd, ld_logstd,
                        rand_probs, rng_state, mu_out, sigma_out, actions, neglogp, rand_mask, n, act_dim, mu_tanh);
     ASE_LAUNCH(rng_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, rng_state);
     ASE_CHECK_LAUNCH("sample_actions");

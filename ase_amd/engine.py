@@ -145,6 +145,11 @@ class UpdateEngine:
         self.enc_sep = bool(getattr(net, 'enc_separate', False))
         self.enc_gp = kind == 'ase' and cfg.get('enc_grad_penalty', 0) != 0 and cfg.get('enc_coef', 0) != 0
         self.mu_tanh = kind == 'ppo' and getattr(net, 'mu_tanh', False)
+        # the policy's log-std (network space.continuous): 'frozen' (learn_sigma False: the reference's configurations),
+        # 'vector' (a learned state-independent vector, one bias-only row of the Adam table) or 'head' (the sigma head, stacked
+        # beside mu in one head group: mu columns [0, act), log-std columns [64, 64 + act))
+        self.sigma_mode = getattr(net, 'sigma_mode', 'frozen')
+        self.ls_mode = {'frozen': L.LS_FROZEN, 'vector': L.LS_VECTOR, 'head': L.LS_ROWS}[self.sigma_mode]
         # gp_f32: the gradient penalty's value path (demo-row forward, chain) in exact f32 inside a 16-bit engine (_gp_f32)
         self.gp32 = bool(cfg.get('gp_f32', False)) and self.has_disc and dtype in (torch.float16, torch.bfloat16) and \
             cfg.get('disc_coef', 0) * cfg.get('disc_grad_penalty', 0) != 0
@@ -289,7 +294,10 @@ class UpdateEngine:
             self.actor.append(Dense([(names_a[i], u, 0)], k, act, sp))
             self.critic.append(Dense([(names_c[i], u, 0)], k, act, sp))
             k = u
-        self.mu_head = Dense([('mu', self.act, 0)], k, 'None')
+        if self.sigma_mode == 'head':
+            self.mu_head = Dense([('mu', self.act, 0), ('sigma', self.act, P(self.act))], k, 'None')
+        else:
+            self.mu_head = Dense([('mu', self.act, 0)], k, 'None')
         self.value_head = Dense([('value', 1, 0)], k, 'None')
         self.disc, self.enc_chain = [], []
         self.disc_head = self.enc_head = None
@@ -349,8 +357,15 @@ class UpdateEngine:
                 ob, _ = net.param_slices[name + '.bias']
                 d.b.append(self.params[ob:ob + nr])
                 d.gb.append(self.grads[ob:ob + nr])
-        o, shp = net.param_slices['sigma']
-        self.logstd = self.params[o:o + shp[0]]
+        self.logstd = self.glogstd = None           # 'head': the log-std is the sigma columns of the head output
+        if self.ls_mode != L.LS_FROZEN and hasattr(self.be, 'reserve_learned_logstd'):
+            self.be.reserve_learned_logstd()
+        if self.sigma_mode != 'head':
+            o, shp = net.param_slices['sigma']
+            self.logstd = self.params[o:o + shp[0]]
+            if self.sigma_mode == 'vector':
+                assert o + shp[0] <= self.n_train, "the learned log-std vector must be trainable"
+                self.glogstd = self.grads[o:o + shp[0]]
         # weight-only loss terms (learning/amp_agent.py:449-466, learning/ase_agent.py:420-425): ranges of the flat buffer
         self.l2_terms = []
         c = self.cfg
@@ -586,18 +601,30 @@ class UpdateEngine:
                              struct.unpack('<i', struct.pack('<f', float(coef)))[0], sa, sb, wide, 0, 0])
                 items.append((W, ws, wts, d.split_src, d.split_dst, b, bs, gW.view(-1).view_as(W), mW.view_as(W), vW.view_as(W),
                               gb, mb, vb, float(coef), sa, sb))
+        n_pol = sum(len(d.parts) for d in self.style + self.actor + [self.mu_head] + self.critic + [self.value_head])
+        if self.sigma_mode == 'vector':
+            # the learned log-std vector: a bias-only row (no weight matrix: k_real = 0, no shadow tiles) whose "bias" is the
+            # vector, its own shadow; it sits at the end of the policy rows (flat order ... mu.weight, mu.bias, sigma, _disc...)
+            b = self.logstd
+            ob = (b.data_ptr() - base) // 4
+            gb, mb, vb = self.glogstd, self.adam_m[ob:ob + b.numel()], self.adam_v[ob:ob + b.numel()]
+            W = self.params[ob:ob]
+            rows.insert(n_pol, [W.data_ptr(), b.numel(), 0, 0, 0, 0, 0, 0, 0, b.data_ptr(), b.data_ptr(), 0, gb.data_ptr(),
+                                mb.data_ptr(), vb.data_ptr(), gb.data_ptr(), mb.data_ptr(), vb.data_ptr(), 0, -1, -1, 0, 0, 0])
+            items.insert(n_pol, (W.view(0, 0), None, None, 0, 0, b, b, self.grads[ob:ob].view(0, 0), self.adam_m[ob:ob].view(0, 0),
+                                 self.adam_v[ob:ob].view(0, 0), gb, mb, vb, 0.0, -1, -1))
+            n_pol += 1
         n_cov = sum(it[0].numel() + it[5].numel() for it in items)
         assert n_cov == self.n_train, (n_cov, self.n_train)     # every trainable scalar belongs to exactly one layer part
         self._apply_desc = torch.tensor(rows, dtype=torch.int64, device=self.dev)
         self._apply_items = items
         # parameter buckets of the two branch groups: rows of the table + the range of the flat buffers they cover
         # (checkpoint order: actor, critic, value, mu | discriminator, logits, encoder - each group is contiguous)
-        n_pol = sum(len(d.parts) for d in self.style + self.actor + [self.mu_head] + self.critic + [self.value_head])
 
         def span(its):
-            lo = min(min((it[0].data_ptr() - base) // 4, (it[5].data_ptr() - base) // 4) for it in its)
-            hi = max(max((it[0].data_ptr() - base) // 4 + it[0].numel(), (it[5].data_ptr() - base) // 4 + it[5].numel())
-                     for it in its)
+            ts = [t for it in its for t in (it[0], it[5]) if t.numel()]      # (the log-std vector's row has no weight)
+            lo = min((t.data_ptr() - base) // 4 for t in ts)
+            hi = max((t.data_ptr() - base) // 4 + t.numel() for t in ts)
             assert hi - lo == sum(it[0].numel() + it[5].numel() for it in its), "a parameter bucket must be contiguous"
             return lo, hi
         self._apply_groups = {'policy': (0, n_pol) + span(items[:n_pol])}
@@ -1235,10 +1262,18 @@ class UpdateEngine:
                 be.wait(self._fill_done)       # gradients zeroed (discriminator's stream) before the loss head adds to them
 
         # -- PPO loss head (value + gradient w.r.t. mu / value + head bias gradients)
-        be.ppo_head(self.MU, self.V, self.mb, self.new_z if self.div_on else None, self.logstd, self.dMU, self.dV,
+        ls_kw = {}
+        if self.sigma_mode == 'head':
+            off = self.mu_head.parts[1][2]
+            ls_kw = dict(ls_mode=L.LS_ROWS, d_logstd=self.dMU[:, off:], db_logstd=self.mu_head.gb[1],
+                         entropy_coef=c.get('entropy_coef', 0.0))
+        elif self.sigma_mode == 'vector':
+            ls_kw = dict(ls_mode=L.LS_VECTOR, db_logstd=self.glogstd, entropy_coef=c.get('entropy_coef', 0.0))
+        be.ppo_head(self.MU, self.V, self.mb, self.new_z if self.div_on else None, self._logstd_of(self.MU), self.dMU, self.dV,
                     self.mu_head.gb[0], self.value_head.gb[0], self.acc, M, self.Mg if self.shard else self.M, self.act, self.z,
                     self.masked, self.div_on, self.mu_tanh, c['clip_value'], c['e_clip'], c['critic_coef'],
-                    self.bounds_coef, c.get('amp_diversity_bonus', 0.0), c.get('amp_diversity_tar', 0.0), grad_scale=self.gs, dyn=self._dS)
+                    self.bounds_coef, c.get('amp_diversity_bonus', 0.0), c.get('amp_diversity_tar', 0.0), grad_scale=self.gs, dyn=self._dS,
+                    **ls_kw)
         fork2 = self._mark()
 
         # -- actor backward on the main stream, critic backward beside it.  The wide layers' weight gradients of BOTH
@@ -1971,17 +2006,31 @@ class UpdateEngine:
             self.be.rms_unnormalize(self.val_state, v, v)
         return v
 
+    def _logstd_of(self, MU):
+        """The log-std operand of the loss / sampling heads: the vector, or (sigma head) the log-std columns of the head output."""
+        if self.sigma_mode == 'head':
+            off = self.mu_head.parts[1][2]
+            return MU[:, off:off + self.act]
+        return self.logstd
+
     def policy_forward(self, obs, z=None, normalize=True, unnorm_value=True, want=('mu', 'value')):
         """Eval-mode actor / critic on raw observations [n, obs] (learning/ase_agent.py:117-148,385-393):
         eval-mode obs normalisation -> nets -> (mu [n, act], value [n, 1] un-normalised).  The returned tensors are
         persistent scratch, overwritten by the next call with the same n."""
         n = obs.shape[0]
-        MU, V = self._policy_nets(obs, z, normalize, 'mu' in want, 'value' in want)
+        MU, V = self._policy_nets(obs, z, normalize, 'mu' in want or 'logstd' in want, 'value' in want)
         out = {}
         if 'mu' in want:
             mu = self._scr('mu_out', n, self.act, torch.float32)
             self.be.gather_rows(MU, self.act, None, (0, 0), n, mu)
             out['mu'] = torch.tanh_(mu) if self.mu_tanh else mu
+        if 'logstd' in want:          # per row [n, act] (the sigma head's output, no activation), or the vector [act]
+            if self.sigma_mode == 'head':
+                ls = self._scr('logstd_out', n, self.act, torch.float32)
+                self.be.gather_rows(self._logstd_of(MU), self.act, None, (0, 0), n, ls)
+                out['logstd'] = ls
+            else:
+                out['logstd'] = self.logstd
         if 'value' in want:
             out['value'] = self._value_out(V, n, unnorm_value)
         return out
@@ -1994,9 +2043,10 @@ class UpdateEngine:
         MU, V = self._policy_nets(obs, z, True, True, True)
         o = {k: self._scr('act_' + k, n, c, f32) for k, c in (('mus', self.act), ('sigmas', self.act), ('actions', self.act),
                                                              ('neglogpacs', 1), ('rand_action_mask', 1))}
-        self.be.sample_actions(MU, self.logstd, rand_probs, rng_state, o['mus'], o['sigmas'], o['actions'],
+        kw = dict(logstd_rows=True) if self.sigma_mode == 'head' else {}
+        self.be.sample_actions(MU, self._logstd_of(MU), rand_probs, rng_state, o['mus'], o['sigmas'], o['actions'],
                                o['neglogpacs'], o['rand_action_mask'] if rand_probs is not None else None, n, self.act,
-                               self.mu_tanh)
+                               self.mu_tanh, **kw)
         res = {'neglogpacs': o['neglogpacs'].view(-1), 'values': self._value_out(V, n, True, 'act_values'),
                'actions': o['actions'], 'mus': o['mus'], 'sigmas': o['sigmas'], 'rnn_states': None}
         if rand_probs is not None:

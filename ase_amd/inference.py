@@ -25,6 +25,11 @@ class InferenceEngine:
     def actor(self, obs, z=None):
         return self.eng.policy_forward(obs, z, normalize=False, want=('mu',))['mu']
 
+    def actor_logstd(self, obs, z=None):
+        """(mu, per-row log-std) of a policy with a sigma head: one actor forward."""
+        out = self.eng.policy_forward(obs, z, normalize=False, want=('mu', 'logstd'))
+        return out['mu'], out['logstd']
+
     def critic(self, obs, z=None):
         return self.eng.policy_forward(obs, z, normalize=False, unnorm_value=False, want=('value',))['value']
 

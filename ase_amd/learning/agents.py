@@ -429,6 +429,9 @@ class CommonAgent:
 
     # ------------------------------------------------------------------ rollout side (inference path)
     def _policy(self, obs, z=None):
+        if self.engine.sigma_mode == 'head':
+            out = self.engine.policy_forward(obs, z, want=('mu', 'logstd', 'value'))
+            return out['mu'], torch.exp(out['logstd']), out['value']
         out = self.engine.policy_forward(obs, z)
         mu = out['mu']
         sigma = torch.exp(mu * 0.0 + self.engine.logstd)

@@ -65,8 +65,13 @@ class A2CNetwork(nn.Module):
         self.num_seqs = num_seqs
         self.is_continuous = True
         sp = params['space']['continuous']
-        assert sp['fixed_sigma'] and not sp['learn_sigma'], "only the reference's frozen log-std is supported"
-        assert sp.get('mu_activation', 'None') == 'None' and sp.get('sigma_activation', 'None') == 'None'
+        # rl_games A2CBuilder's three log-std forms (learning/ase_network_builder.py:56-61): learn_sigma False - a frozen vector
+        # (every shipped configuration); learn_sigma + fixed_sigma - a learned state-independent vector; learn_sigma alone - a
+        # per-state head sigma = Linear(actor_out, actions) beside mu
+        self.sigma_mode = 'frozen' if not sp['learn_sigma'] else ('vector' if sp['fixed_sigma'] else 'head')
+        assert sp.get('mu_activation', 'None') == 'None', "mu_activation: only 'None' is supported"
+        assert sp.get('sigma_activation', 'None') == 'None', \
+            f"sigma_activation {sp.get('sigma_activation')!r}: only 'None' (log-std = the sigma output itself) is supported"
         assert params.get('separate', False), "reference configs use separate actor / critic trunks"
         self.units = list(params['mlp']['units'])
         self.activation = params['mlp']['activation']
@@ -90,7 +95,10 @@ class A2CNetwork(nn.Module):
         out = self.units[-1]
         self.value = nn.Linear(out, 1)
         self.mu = nn.Linear(out, self.actions_num)
-        self.sigma = nn.Parameter(torch.full((self.actions_num,), float(sp['sigma_init']['val'])), requires_grad=False)
+        if self.sigma_mode == 'head':
+            self.sigma = nn.Linear(out, self.actions_num)
+        else:
+            self.sigma = nn.Parameter(torch.zeros(self.actions_num), requires_grad=self.sigma_mode == 'vector')
         if kind in ('amp', 'ase'):
             self.disc_units = list(params['disc']['units'])
             self.disc_activation = params['disc']['activation']
@@ -118,6 +126,8 @@ class A2CNetwork(nn.Module):
             nn.init.uniform_(self._enc.weight, -ENC_LOGIT_INIT_SCALE, ENC_LOGIT_INIT_SCALE)
         if kind in ('amp', 'ase'):
             nn.init.uniform_(self._disc_logits.weight, -DISC_LOGIT_INIT_SCALE, DISC_LOGIT_INIT_SCALE)
+        # sigma_init after every Linear's initialiser (learning/ase_network_builder.py:82-85): the vector, or the head's weight
+        _sigma_init(self.sigma if self.sigma_mode != 'head' else self.sigma.weight, sp['sigma_init'])
         self._flatten(torch.device(device))
         self.infer = None          # ase_amd.inference.InferenceEngine, attached lazily
 
@@ -180,6 +190,8 @@ class A2CNetwork(nn.Module):
 
     def eval_actor(self, obs, ase_latents=None, use_hidden_latents=False):
         assert not use_hidden_latents
+        if self.sigma_mode == 'head':
+            return self._engine().actor_logstd(obs, ase_latents)
         mu = self._engine().actor(obs, ase_latents)
         return mu, mu * 0.0 + self.sigma
 
@@ -207,6 +219,23 @@ class A2CNetwork(nn.Module):
         ws = [torch.flatten(m.weight) for m in self._enc_mlp.modules() if isinstance(m, nn.Linear)]
         ws.append(torch.flatten(self._enc.weight))
         return ws
+
+
+def _sigma_init(t, spec):
+    """rl_games init_factory for the initialisers a sigma_init names (const / uniform / normal / default)."""
+    name = spec.get('name', 'default')
+    with torch.no_grad():
+        if name == 'const_initializer':
+            nn.init.constant_(t, float(spec['val']))
+        elif name == 'random_uniform_initializer':
+            nn.init.uniform_(t, a=float(spec.get('a', 0.0)), b=float(spec.get('b', 1.0)))
+        elif name == 'random_normal_initializer':
+            nn.init.normal_(t, mean=float(spec.get('mean', 0.0)), std=float(spec.get('std', 1.0)))
+        elif name == 'default':
+            pass                          # rl_games 'default': the tensor keeps what it has (zeros / nn.Linear's own init)
+        else:
+            raise ValueError(f"sigma_init {name!r}: const_initializer, random_uniform_initializer, random_normal_initializer "
+                             "or default")
 
 
 class _Builder:

@@ -9,8 +9,10 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libase_hip.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 PPO_SCRATCH = 1024 * 72 + 8       # ASE_PPO_SCRATCH: doubles of ase_hip_ppo_head's workspace
+PPO_SCRATCH_LS = 1024 * 136 + 8   # ASE_PPO_SCRATCH_LS: the same with a learned log-std
+LS_FROZEN, LS_VECTOR, LS_ROWS = 0, 1, 2     # ASE_LS_*: ase_hip_ppo_head's log-std modes
 TN_SLAB = 65536 + 256        # ASE_TN_SLAB: floats per work item in the grouped weight-gradient launch's workspace
 F32, BF16, F32X3, F16, F32H3 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SILU, ACT_ELU, ACT_GELU, ACT_SIGMOID, ACT_SELU, ACT_SOFTPLUS = range(9)
@@ -43,7 +45,8 @@ SIGNATURES = {
     "ase_hip_rms_unnormalize": [_p, _p, _p, _i64, _p],
     "ase_hip_gather_rows": [_p, _i64, _i, _p, _i, _i, _i, _p, _i64, _i, _p],
     "ase_hip_reduce_sum": [_p, _i64, _i, _p, _i, _p],
-    "ase_hip_ppo_head": [_p, _i64, _p, _i64] + [_p] * 11 + [_p, _i64, _p, _i64, _p, _p, _p, _p, _p] + [_i] * 8 + [_f] * 6 + [_p, _i, _p],
+    "ase_hip_ppo_head": [_p, _i64, _p, _i64] + [_p] * 11 + [_p, _i64, _p, _i64, _p, _p, _p, _p, _p] + [_i] * 8 + [_f] * 6 + [_p]
+                        + [_i, _i64, _p, _i64, _p, _f] + [_i, _p],
     "ase_hip_disc_head": [_p, _i64, _p, _i64, _p, _p, _i, _i, _f, _f, _p, _i, _p],
     "ase_hip_enc_head": [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _i, _i, _i, _f, _f, _p, _i, _p],
     "ase_hip_gp_seed": [_p, _i64, _p, _p, _i64, _i, _i, _f, _i, _i, _p],
@@ -70,7 +73,7 @@ SIGNATURES = {
     "ase_hip_rms_moments_multi": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p],
     "ase_hip_rms_normalize_multi": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "ase_hip_normalize_rows": [_p, _i64, _p, _i64, _i, _i, _p],
-    "ase_hip_sample_actions": [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
+    "ase_hip_sample_actions": [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     "ase_hip_debug_nt_profile": [_p],
     "ase_hip_debug_nt_profile_clock": [_i],
     "ase_hip_motion_state": [_p] * 6 + [_i] + [_p] * 6 + [_i, _p, _p, _i, _p, _i] + [_p] * 8,

@@ -24,6 +24,9 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
       -> (stats [6], d_mu, d_value)                   CommonAgent._actor_loss / _critic_loss / bound_loss + entropy, clip fraction, kl
                                                       (learning/common_agent.py:456-464,505-534) with the gradient of
                                                       actor_loss + bounds_coef bound_loss w.r.t. mu and of critic_coef critic_loss w.r.t. value
+  ppo_loss_head_ls(..., logstd [M, A] | [A], ..., entropy_coef) -> (stats [6], d_mu, d_logstd, d_value)
+                                                      the same with a learned log-std (rl_games learn_sigma): d_logstd per row
+                                                      (- entropy_coef entropy included)
   disc_loss_gp(logits, grad_demo, disc_coef) -> (stats [4], d_logits)
                                                       AMPAgent._disc_loss' data terms (learning/amp_agent.py:442-459,481-496): BCE halves,
                                                       accuracies, the gradient penalty mean |d logit / d obs|^2, d loss / d logits
@@ -388,6 +391,47 @@ def ppo_loss_head(mu: torch.Tensor, value: torch.Tensor, actions: torch.Tensor, 
 def _(mu, value, actions, old_mu, old_sigma, old_neglogp, advantages, old_values, returns, mask, logstd, e_clip, critic_coef,
       bounds_coef, clip_value):
     return mu.new_empty(6), torch.empty_like(mu), mu.new_empty(mu.shape[0], 1)
+
+
+@torch.library.custom_op('ase_hip::ppo_loss_head_ls', mutates_args=(), device_types='cuda')
+def ppo_loss_head_ls(mu: torch.Tensor, value: torch.Tensor, actions: torch.Tensor, old_mu: torch.Tensor, old_sigma: torch.Tensor,
+                     old_neglogp: torch.Tensor, advantages: torch.Tensor, old_values: torch.Tensor, returns: torch.Tensor,
+                     mask: torch.Tensor, logstd: torch.Tensor, e_clip: float, critic_coef: float, bounds_coef: float,
+                     clip_value: bool, entropy_coef: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """ppo_loss_head with a LEARNED log-std (rl_games learn_sigma): logstd is the state-independent vector [A] (fixed_sigma) or
+    the per-row output of the sigma head [M, A].  The loss gains - entropy_coef x entropy; d_logstd [M, A] = d (actor_loss +
+    bounds_coef bound_loss - entropy_coef entropy) / d logstd per row (the KL takes sigma detached, as the reference's does).
+    The vector's gradient is d_logstd.sum(0).  Returns (stats [6], d_mu, d_logstd, d_value)."""
+    M, A = mu.shape
+    _check(mu.dim() == 2 and 1 <= A <= 64, 'ppo_loss_head_ls: mu [M, actions <= 64]')
+    rows = logstd.dim() == 2
+    _check(tuple(logstd.shape) in ((M, A), (A,)), 'ppo_loss_head_ls: logstd [M, actions] or [actions]')
+    be, dev = _backend(), mu.device
+    mu, value = _f32c(mu, 'mu'), _f32c(value.reshape(M, 1), 'value')
+    masked = mask.numel() > 0
+    mb = {'actions': _f32c(actions, 'actions', A), 'mu': _f32c(old_mu, 'old_mu', A), 'sigma': _f32c(old_sigma, 'old_sigma', A),
+          'old_logp_actions': _f32c(old_neglogp.reshape(M, 1), 'old_neglogp'), 'advantages': _f32c(advantages.reshape(M, 1), 'advantages'),
+          'old_values': _f32c(old_values.reshape(M, 1), 'old_values'), 'returns': _f32c(returns.reshape(M, 1), 'returns')}
+    acc = torch.zeros(L.ACC_COUNT, dtype=torch.float64, device=dev)
+    if masked:
+        mb['rand_action_mask'] = _f32c(mask.reshape(M, 1).float(), 'mask')
+        be.reduce_sum(mb['rand_action_mask'], M, False, acc, L.ACC_MASK_SUM)
+    f32 = dict(dtype=torch.float32, device=dev)
+    d_mu, d_value, d_ls = torch.zeros(M, A, **f32), torch.zeros(M, 1, **f32), torch.zeros(M, A, **f32)
+    ls = _f32c(logstd, 'logstd', A) if rows else _f32c(logstd, 'logstd')
+    be.ppo_head(mu, value, mb, None, ls, d_mu, d_value, None, None, acc, M, M, A, 0, masked, False,
+                False, bool(clip_value), e_clip, critic_coef, bounds_coef, 0.0, 0.0,
+                ls_mode=L.LS_ROWS if rows else L.LS_VECTOR, d_logstd=d_ls, entropy_coef=entropy_coef)
+    den = acc[L.ACC_MASK_SUM] if masked else float(M)
+    stats = torch.stack([acc[L.ACC_A_LOSS] / den, acc[L.ACC_C_LOSS] / M, acc[L.ACC_B_LOSS] / den, acc[L.ACC_ENTROPY] / den,
+                         acc[L.ACC_CLIPPED] / den, acc[L.ACC_KL] / M]).float()
+    return stats, d_mu, d_ls, d_value
+
+
+@ppo_loss_head_ls.register_fake
+def _(mu, value, actions, old_mu, old_sigma, old_neglogp, advantages, old_values, returns, mask, logstd, e_clip, critic_coef,
+      bounds_coef, clip_value, entropy_coef):
+    return mu.new_empty(6), torch.empty_like(mu), torch.empty_like(mu), mu.new_empty(mu.shape[0], 1)
 
 
 @torch.library.custom_op('ase_hip::disc_loss_gp', mutates_args=(), device_types='cuda')

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ASE_HIP_ABI_VERSION 7
+#define ASE_HIP_ABI_VERSION 8
 
 enum { ASE_F32 = 0, ASE_BF16 = 1, ASE_F32X3 = 2 /* f32 storage, products as 3 bf16 MFMAs on a hi/lo split (GEMMs only) */,
        ASE_F32H3 = 4 /* 4-byte storage, products as 3 f16 MFMAs on hi/lo splits of operands scaled by 2^ea / 2^eb (the exponents ride in
@@ -252,8 +252,22 @@ int ase_hip_reduce_sum(const float* x, int64_t n, int square, double* acc, int s
  *            keeps it), read when the launch runs; overflow count, see ase_hip_gemm_nt's alpha_dev}.
  *   scratch: device f64[ASE_PPO_SCRATCH] workspace, private to one launch at a time: per-workgroup partial sums (loss
  *            scalars, head-bias column sums), folded into acc / db_* by a second one-workgroup kernel of the same call (no
- *            contended atomics; a kernel boundary instead of per-workgroup fences). */
+ *            contended atomics; a kernel boundary instead of per-workgroup fences).
+ *   ls_mode (ABI 8): the policy's log-std (network space.continuous, rl_games A2CBuilder):
+ *            ASE_LS_FROZEN  logstd f32[act_dim], frozen (learn_sigma False): no log-std gradient; ld_ls, d_ls, db_ls unused.
+ *            ASE_LS_VECTOR  logstd f32[act_dim], learned (learn_sigma, fixed_sigma True).
+ *            ASE_LS_ROWS    logstd f32[rows, ld_ls], one row per state (learn_sigma, fixed_sigma False: the sigma head's output,
+ *                           e.g. columns 64.. of the stacked [mu | sigma] head output, ld_ls = ld_mu).
+ *            A learned mode adds d loss / d logstd = w (-g ratio (1 - d^2) - entropy_coef) per row and action (g = d a_loss /
+ *            d ratio, d = (a - mu) / sigma, w the masked-mean weight; the KL takes sigma detached): d_ls (nullable) dtype
+ *            [rows_mu, ld_dls] receives it times grad_scale (diversity rows [M, 2M): zero), db_ls f32[act_dim] (nullable) +=
+ *            its column sums (the vector's gradient, or the sigma head's bias gradient).  scratch then holds
+ *            ASE_PPO_SCRATCH_LS doubles.  entropy_coef: the loss's -entropy_coef * entropy term (learned modes only). */
 #define ASE_PPO_SCRATCH (1024 * 72 + 8)
+#define ASE_PPO_SCRATCH_LS (1024 * 136 + 8)
+#define ASE_LS_FROZEN 0
+#define ASE_LS_VECTOR 1
+#define ASE_LS_ROWS 2
 int ase_hip_ppo_head(const float* mu, int64_t ld_mu, const float* value, int64_t ld_v,
                      const float* mb_actions, const float* mb_old_mu, const float* mb_old_sigma,
                      const float* mb_old_logp, const float* mb_adv, const float* mb_old_value,
@@ -263,7 +277,9 @@ int ase_hip_ppo_head(const float* mu, int64_t ld_mu, const float* value, int64_t
                      float* db_mu, float* db_value, float* mu_out, double* acc, double* scratch,
                      int M, int m_global, int act_dim, int z_dim, int masked, int div_on, int mu_tanh,
                      int clip_value, float e_clip, float critic_coef, float bounds_coef,
-                     float div_coef, float div_tar, float grad_scale, float* grad_scale_dev, int dtype, void* stream);
+                     float div_coef, float div_tar, float grad_scale, float* grad_scale_dev,
+                     int ls_mode, int64_t ld_ls, void* d_ls, int64_t ld_dls, float* db_ls, float entropy_coef,
+                     int dtype, void* stream);
 
 /* Discriminator logit losses (learning/amp_agent.py:442-447,481-496): rows [0,2*amb) agent+replay
  * (target 0), rows [2*amb,3*amb) demo (target 1).  d_logit dtype [3*amb, ld_d] column 0. */
@@ -417,8 +433,10 @@ int ase_hip_normalize_rows(const float* x, int64_t ld_x, float* y, int64_t ld_y,
  * (learning/amp_models.py:29-36; learning/amp_agent.py:139-169; learning/ase_agent.py:117-148): per row
  * mu' = mu (tanh'ed when mu_tanh, learning/hrl_network_builder.py:26-29), sigma = exp(logstd), a = mu' + sigma N(0,1)
  * (Philox, rng_state as below), neglogp(a), rand_mask = Bernoulli(rand_probs[row]) and actions = rand_mask ? a : mu'.
- * rand_probs / rand_mask nullable (plain PPO: every row stochastic).  mu has leading dimension ld_mu, outputs are dense. */
-int ase_hip_sample_actions(const float* mu, int64_t ld_mu, const float* logstd, const float* rand_probs,
+ * rand_probs / rand_mask nullable (plain PPO: every row stochastic).  mu has leading dimension ld_mu, outputs are dense.
+ * logstd: row r reads logstd[r * ld_logstd ..] (ABI 8): ld_logstd 0 - one vector for every row, >= act_dim - a per-state
+ * log-std (the sigma head's output rows). */
+int ase_hip_sample_actions(const float* mu, int64_t ld_mu, const float* logstd, int64_t ld_logstd, const float* rand_probs,
                            uint64_t* rng_state, float* mu_out, float* sigma_out, float* actions, float* neglogp,
                            float* rand_mask, int n, int act_dim, int mu_tanh, void* stream);
 

@@ -29,7 +29,14 @@ ase_amd.configure(cpu_threads=1)     # hardware queues before HIP initialises; o
 import torch  # noqa: E402
 
 
-def build(kind, num_envs, precision, graph=True, overrides=None, net_overrides=None):
+SIGMA_FORMS = {  # network space.continuous of the log-std forms (rl_games learn_sigma / fixed_sigma)
+    'frozen': None,
+    'vector': dict(learn_sigma=True, fixed_sigma=True, sigma_init={'name': 'const_initializer', 'val': -2.9}),
+    'head': dict(learn_sigma=True, fixed_sigma=False, sigma_init={'name': 'random_uniform_initializer', 'a': -0.02, 'b': 0.02}),
+}
+
+
+def build(kind, num_envs, precision, graph=True, overrides=None, net_overrides=None, sigma=None):
     from ase_amd import cfg as defaults
     from ase_amd.learning import agents, models
     from ase_amd.learning.network_builder import AMPBuilder, ASEBuilder, HRLBuilder
@@ -38,6 +45,8 @@ def build(kind, num_envs, precision, graph=True, overrides=None, net_overrides=N
     cfg.update({k: v for k, v in (overrides or {}).items() if k == 'horizon_length'})
     for part, units in (net_overrides or {}).items():
         net_p[part]['units'] = list(units)
+    if SIGMA_FORMS.get(sigma):
+        net_p['space']['continuous'].update(SIGMA_FORMS[sigma])
     obs, act, amp = {'ase': (253, 31, 1400), 'amp': (253, 31, 1400), 'hrl': (258, 64, 0)}[kind]
     z = cfg.get('latent_dim', 0) if kind == 'ase' else 0
     spec = EnvSpec(num_envs=num_envs, horizon=cfg['horizon_length'], obs_size=obs, act_size=act, amp_obs_size=amp,
@@ -95,7 +104,16 @@ def main():
     ap.add_argument('--shard-of', default='', help='comma list of rank counts R: time one rank\'s share of the sharded update')
     ap.add_argument('--precision', default='bf16')
     ap.add_argument('--engine-opts', default='', help='JSON dict of UpdateEngine.engine_opts overrides (the --shard-of runs)')
+    ap.add_argument('--sigma', choices=sorted(SIGMA_FORMS), default=None,
+                    help='time config 2 (ase, 4096 envs, --precision) with this log-std form: frozen / learned vector / sigma head')
     args = ap.parse_args()
+    if args.sigma:
+        ag, cfg, spec = build('ase', 4096, args.precision, sigma=args.sigma)
+        dt = time_updates(ag, args.updates)
+        print(json.dumps({'measurement': f'sigma-{args.sigma}', 'what': 'config 2 update with the log-std form ' + args.sigma,
+                          'precision': args.precision, 'ms_per_update': round(dt * 1e3, 3),
+                          'trainable': int(ag.model.a2c_network.trainable_numel)}), flush=True)
+        return
     if args.shard_of:
         for R in [int(x) for x in args.shard_of.split(',')]:
             ov = {'minibatch_size': 16384 // R, 'amp_minibatch_size': 4096 // R}
