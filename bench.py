@@ -1,6 +1,6 @@
 """Benchmark of the ASE PPO-update hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision auto|f16gpx3|f16gp32|f32|bf16|...] [--no-graph] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision auto|f16gpx3|f16gp32|f32|bf16|...] [--no-graph] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +17,12 @@ learning/common_agent.py:94-107): every rank owns 4096 environments and draws it
 buckets are averaged by RCCL all-reduces over xGMI (the discriminator bucket while the policy branch is still in its
 backward) - weak scaling, `value` = all ranks' samples / max-over-ranks time.  `--dp-mode shard` row-shards every minibatch
 of the SAME 4096 environments over the ranks instead (the R-rank update equals the 1-rank update; strong scaling).
+
+A plain run does what the headline needs and nothing more: set up, W warm-up updates, the K timed ones, --dump-outputs, the
+line.  `--precision auto` then takes its first candidate (f16gpx3) without a parity leg.  `--full` adds everything else the
+benchmark measures or checks: the CPU oracle leg (cpu_baseline; parity of the headline mode in two rollout states, which
+decides the fall-through of `--precision auto`), the roofline pass (one more, instrumented update), `--modes`, the throughput
+mode, the 16384-environment batch, strict mode and the detail file.  The timed steps are the same in both.
 
 Prints ONE JSON line on rank 0.
 """
@@ -750,10 +756,80 @@ def _strict_ok(par):
                              for s_ in ('fresh', 'stress'))
 
 
+def roofline_pass(args, agent, cfg, precision, device, rank, use_graph, Bl, one_update):
+    """--full: the roofline of the dominant kernel class (matrix-core GEMMs), from HIP events around every launch of one
+    additional, eager (un-graphed) update after the timed ones, on the same stream the kernels are launched on."""
+    eng = agent.engine
+    tb = TimedBackend(eng.be)          # every rank runs the instrumented update (it contains collectives); rank 0 reports
+    eng.be = tb
+    agent.use_graph = False
+    ms_flag, eng.multi_stream = eng.multi_stream, False       # serial launches: clean per-kernel durations
+    one_update()
+    summ = tb.summary()
+    if args.breakdown:
+        print('\n'.join(tb.breakdown(peak_tflops=MFMA_PEAK_TFLOPS[precision])), file=sys.stderr)
+    eng.be = tb._be
+    eng.multi_stream = ms_flag
+    agent.use_graph = use_graph
+    n_opt = cfg['mini_epochs'] * (Bl // cfg['minibatch_size'])
+    alg = algorithmic_flops_per_step(eng) * n_opt + 2.0 * Bl * sum(d.N * d.K for d in eng.disc) \
+        + 2.0 * Bl * (1 + eng.z) * eng.disc_head.K
+    gemm_ms = sum(v['ms'] for v in summ.values())
+    launches = sum(v['launches'] for v in summ.values())
+    peak = MFMA_PEAK_TFLOPS[precision]
+    # the dominant kernel = the GEMM kernel class with the most time (16-bit modes: the phased 256 x 256 NT kernel)
+    dom = max(summ, key=lambda k: summ[k]['ms'])
+    dname = {'nt8': f'gemm_nt8_kernel<{DTYPE_OF[precision]}> (phased 256x256 NT: forward + data-gradient of the wide layers)',
+             'nt8_192': f'gemm_nt8_kernel<{DTYPE_OF[precision]}, 192> (phased 192x256 NT)', 'nt': 'gemm_nt_kernel (NT tiles 64/128/256)', 'tn': 'gemm_tn kernels (weight gradients)',
+             'nt_x3': 'gemm_nt_kernel<f32h_t> (the penalty value path: three f16 MFMAs per product)'}[dom]
+    dv = summ[dom]
+    achieved = dv['flops'] / (dv['ms'] * 1e-3) / 1e12
+    # HBM traffic of that kernel per launch: PMC measurement committed under profiles/ (rocprofv3 --pmc FETCH_SIZE /
+    # WRITE_SIZE in separate passes, FETCH doubled per the gfx950 note); bench cannot profile itself
+    # ... and only a measurement of THIS build is quoted: the file carries the sha256 of the library its passes ran
+    # (scripts/make_pmc_json.py --lib), compared with the library loaded here; a profile of another build gives traffic = null
+    traffic, traffic_src = None, None
+    pmc = sorted(f for f in os.listdir(os.path.join(ROOT, 'profiles')) if f.endswith('_pmc.json')) \
+        if os.path.isdir(os.path.join(ROOT, 'profiles')) else []
+    if pmc and precision in ('bf16', 'f16', 'f16gp32', 'f16gpx3'):
+        from scripts.make_pmc_json import lib_sha256
+        from ase_amd import lib as _L
+        sha = lib_sha256(_L.LIB_PATH)
+        for name in reversed(pmc):
+            j = json.load(open(os.path.join(ROOT, 'profiles', name)))
+            if j.get('kernel_class') == dom and j.get('lib_sha256') == sha:
+                traffic, traffic_src = j['hbm_bytes_per_launch'], 'profiles/' + name
+                break
+        if traffic is None:
+            traffic_src = 'none: no profiles/*_pmc.json was measured on the loaded build (sha256 %s...)' % sha[:12]
+    clk = sustained_clock(eng.be, device, eng.dtype) if (dom == 'nt8' and rank == 0) else None
+    roof = {'bound': 'mfma', 'kernel': dname,
+            'achieved': round(achieved, 2), 'peak': peak, 'unit': 'TFLOP/s', 'frac': round(achieved / peak, 4),
+            # the peak is quoted at the 2.4 GHz boost clock; what the chip holds under THIS kernel is measured in the kernel
+            # (shader-clock vs real-time stamps around its main loop): frac_at_sustained_clock prices the same achieved rate
+            # against peak x sustained / 2400, main_loop_mfma_busy = the matrix pipe's share of the main loop's CYCLES
+            'sustained_clock_mhz': clk[0] if clk else None,
+            'frac_at_sustained_clock': round(achieved / (peak * clk[0] / 2400.0), 4) if clk else None,
+            'main_loop': {'shape': '16384 x 1024 x 1024 (ReLU forward)', 'us': clk[1], 'shader_cycles': clk[2],
+                          'mfma_cycles': 16 * 2048, 'mfma_busy': round(16 * 2048 / clk[2], 4)} if clk else None,
+            'traffic': traffic, 'traffic_unit': 'HBM bytes per launch of that kernel (PMC)', 'traffic_source': traffic_src,
+            'launches': dv['launches'], 'avg_launch_us': round(dv['ms'] * 1e3 / dv['launches'], 2),
+            'algorithmic_flop_per_launch': round(dv['flops'] / dv['launches']),
+            'algorithmic_bytes_per_launch': round(tb.bytes.get(dom, 0.0) / dv['launches']) if dom in tb.bytes else None,
+            'share_of_gemm_time': round(dv['ms'] / gemm_ms, 3),
+            'all_gemm': {'achieved': round(alg / (gemm_ms * 1e-3) / 1e12, 2), 'frac': round(alg / (gemm_ms * 1e-3) / 1e12 / peak, 4),
+                         'launches_per_update': launches, 'gemm_ms_per_update': round(gemm_ms, 3),
+                         'algorithmic_tflop_per_update': round(alg / 1e12, 3)},
+            'per_kind': {k: {'launches': v['launches'], 'ms': round(v['ms'], 3),
+                             'tflops': round(v['flops'] / (v['ms'] * 1e-3) / 1e12, 1)} for k, v in summ.items()},
+            'hbm_kernels': tb.hbm_summary()}
+    return roof
+
+
 def measure_mode(args, precision, device, world, rank, use_graph):
     """The contract's timed protocol for one precision mode: build the agent, synthetic rollout into HBM, W untimed warm-up
-    updates, EXACTLY K timed updates between barrier + synchronize brackets (max over ranks), then the instrumented eager
-    single-stream update for the roofline of the dominant kernel."""
+    updates, EXACTLY K timed updates between barrier + synchronize brackets (max over ranks), then (--full) the instrumented
+    eager single-stream update for the roofline of the dominant kernel."""
     t_setup = time.time()
     agent, cfg, spec = make_agent(device, precision, use_graph, world, rank, force_dist=args.force_dist,
                                    multi_stream=not args.no_multi_stream, dp_mode=args.dp_mode)
@@ -831,72 +907,7 @@ def measure_mode(args, precision, device, world, rank, use_graph):
     value = B * args.steps / dt
     last = {k: float(v[-1]) for k, v in info.items() if torch.is_tensor(v[-1]) and v[-1].numel() == 1}
 
-    # ---- roofline of the dominant kernel class (matrix-core GEMMs): HIP events around every launch of one
-    # additional, eager (un-graphed) update on the same stream the kernels are launched on.
-    eng = agent.engine
-    tb = TimedBackend(eng.be)          # every rank runs the instrumented update (it contains collectives); rank 0 reports
-    eng.be = tb
-    agent.use_graph = False
-    ms_flag, eng.multi_stream = eng.multi_stream, False       # serial launches: clean per-kernel durations
-    one_update()
-    summ = tb.summary()
-    if args.breakdown:
-        print('\n'.join(tb.breakdown(peak_tflops=MFMA_PEAK_TFLOPS[precision])), file=sys.stderr)
-    eng.be = tb._be
-    eng.multi_stream = ms_flag
-    agent.use_graph = use_graph
-    n_opt = cfg['mini_epochs'] * (Bl // cfg['minibatch_size'])
-    alg = algorithmic_flops_per_step(eng) * n_opt + 2.0 * Bl * sum(d.N * d.K for d in eng.disc) \
-        + 2.0 * Bl * (1 + eng.z) * eng.disc_head.K
-    gemm_ms = sum(v['ms'] for v in summ.values())
-    launches = sum(v['launches'] for v in summ.values())
-    peak = MFMA_PEAK_TFLOPS[precision]
-    # the dominant kernel = the GEMM kernel class with the most time (16-bit modes: the phased 256 x 256 NT kernel)
-    dom = max(summ, key=lambda k: summ[k]['ms'])
-    dname = {'nt8': f'gemm_nt8_kernel<{DTYPE_OF[precision]}> (phased 256x256 NT: forward + data-gradient of the wide layers)',
-             'nt8_192': f'gemm_nt8_kernel<{DTYPE_OF[precision]}, 192> (phased 192x256 NT)', 'nt': 'gemm_nt_kernel (NT tiles 64/128/256)', 'tn': 'gemm_tn kernels (weight gradients)',
-             'nt_x3': 'gemm_nt_kernel<f32h_t> (the penalty value path: three f16 MFMAs per product)'}[dom]
-    dv = summ[dom]
-    achieved = dv['flops'] / (dv['ms'] * 1e-3) / 1e12
-    # HBM traffic of that kernel per launch: PMC measurement committed under profiles/ (rocprofv3 --pmc FETCH_SIZE /
-    # WRITE_SIZE in separate passes, FETCH doubled per the gfx950 note); bench cannot profile itself
-    # ... and only a measurement of THIS build is quoted: the file carries the sha256 of the library its passes ran
-    # (scripts/make_pmc_json.py --lib), compared with the library loaded here; a profile of another build gives traffic = null
-    traffic, traffic_src = None, None
-    pmc = sorted(f for f in os.listdir(os.path.join(ROOT, 'profiles')) if f.endswith('_pmc.json')) \
-        if os.path.isdir(os.path.join(ROOT, 'profiles')) else []
-    if pmc and precision in ('bf16', 'f16', 'f16gp32', 'f16gpx3'):
-        from scripts.make_pmc_json import lib_sha256
-        from ase_amd import lib as _L
-        sha = lib_sha256(_L.LIB_PATH)
-        for name in reversed(pmc):
-            j = json.load(open(os.path.join(ROOT, 'profiles', name)))
-            if j.get('kernel_class') == dom and j.get('lib_sha256') == sha:
-                traffic, traffic_src = j['hbm_bytes_per_launch'], 'profiles/' + name
-                break
-        if traffic is None:
-            traffic_src = 'none: no profiles/*_pmc.json was measured on the loaded build (sha256 %s...)' % sha[:12]
-    clk = sustained_clock(eng.be, device, eng.dtype) if (dom == 'nt8' and rank == 0) else None
-    roof = {'bound': 'mfma', 'kernel': dname,
-            'achieved': round(achieved, 2), 'peak': peak, 'unit': 'TFLOP/s', 'frac': round(achieved / peak, 4),
-            # the peak is quoted at the 2.4 GHz boost clock; what the chip holds under THIS kernel is measured in the kernel
-            # (shader-clock vs real-time stamps around its main loop): frac_at_sustained_clock prices the same achieved rate
-            # against peak x sustained / 2400, main_loop_mfma_busy = the matrix pipe's share of the main loop's CYCLES
-            'sustained_clock_mhz': clk[0] if clk else None,
-            'frac_at_sustained_clock': round(achieved / (peak * clk[0] / 2400.0), 4) if clk else None,
-            'main_loop': {'shape': '16384 x 1024 x 1024 (ReLU forward)', 'us': clk[1], 'shader_cycles': clk[2],
-                          'mfma_cycles': 16 * 2048, 'mfma_busy': round(16 * 2048 / clk[2], 4)} if clk else None,
-            'traffic': traffic, 'traffic_unit': 'HBM bytes per launch of that kernel (PMC)', 'traffic_source': traffic_src,
-            'launches': dv['launches'], 'avg_launch_us': round(dv['ms'] * 1e3 / dv['launches'], 2),
-            'algorithmic_flop_per_launch': round(dv['flops'] / dv['launches']),
-            'algorithmic_bytes_per_launch': round(tb.bytes.get(dom, 0.0) / dv['launches']) if dom in tb.bytes else None,
-            'share_of_gemm_time': round(dv['ms'] / gemm_ms, 3),
-            'all_gemm': {'achieved': round(alg / (gemm_ms * 1e-3) / 1e12, 2), 'frac': round(alg / (gemm_ms * 1e-3) / 1e12 / peak, 4),
-                         'launches_per_update': launches, 'gemm_ms_per_update': round(gemm_ms, 3),
-                         'algorithmic_tflop_per_update': round(alg / 1e12, 3)},
-            'per_kind': {k: {'launches': v['launches'], 'ms': round(v['ms'], 3),
-                             'tflops': round(v['flops'] / (v['ms'] * 1e-3) / 1e12, 1)} for k, v in summ.items()},
-            'hbm_kernels': tb.hbm_summary()}
+    roof = roofline_pass(args, agent, cfg, precision, device, rank, use_graph, Bl, one_update) if args.full else None
     return {'precision': precision, 'agent': agent, 'cfg': cfg, 'value': value, 'ms_per_step': ms_per_step, 'ms_tail': ms_tail,
             'last': last, 'roofline': roof, 'B': B, 'Bl': Bl, 'weak': weak, 'outputs': outputs,
             'grad_scale': agent.engine.gs}
@@ -912,8 +923,9 @@ def main():
     ap.add_argument('--precision', default='auto',
                     help="headline precision mode.  'auto' (default): the FASTEST of f16gpx3 > f16gp32 > f32 whose loss scalars hold the "
                          '1e-4 parity bar on a fresh rollout AND in the stale-rollout stress state IN THIS RUN - a candidate that misses '
-                         'is reported under `fallthrough` and the next one is measured with the same timed protocol (N > 1 or '
-                         '--no-cpu-baseline: no oracle leg, the first candidate is taken).  A named mode is measured as given.',
+                         'is reported under `fallthrough` and the next one is measured with the same timed protocol (a plain run '
+                         'without --full, N > 1 or --no-cpu-baseline: no oracle leg, the first candidate is taken).  A named mode is '
+                         'measured as given.',
                     choices=['auto', 'bf16', 'f16', 'f16gp32', 'f16gpx3', 'f32', 'bf16x3'])
     ap.add_argument('--no-graph', action='store_true', help='eager launches from Python (no recorded launch program)')
     ap.add_argument('--hipgraph', action='store_true', help='replay captured hipGraphs instead of the library launch programs')
@@ -954,9 +966,16 @@ def main():
                          "generation-2 pass of Python's collector inside an update); 'on': leave the collector alone")
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step computed (update results, weights, normalisers) as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: the CPU oracle leg (cpu_baseline, parity in both rollout states, the '
+                         'fall-through of --precision auto), the roofline pass (one more instrumented update), --modes, the '
+                         'throughput mode, the 16384-environment batch, strict mode and the detail file.  Without it a run sets '
+                         'up, warms up, times the K steps, writes --dump-outputs and prints the line')
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full and (args.modes or args.breakdown):
+        ap.error('--modes and --breakdown need --full')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -993,7 +1012,7 @@ def main():
         args.throughput_mode = ''
     if args.engine_opts:
         ENGINE_OPTS.update(json.loads(args.engine_opts))
-    oracle_leg = world == 1 and not args.no_cpu_baseline          # (rank 0 is the only rank then)
+    oracle_leg = args.full and world == 1 and not args.no_cpu_baseline          # (rank 0 is the only rank then)
     candidates = HEADLINE_CANDIDATES if args.precision == 'auto' else [args.precision]
 
     # ---- the headline: candidates in order of speed; the first whose parity holds in BOTH rollout states is the line's value
@@ -1051,7 +1070,7 @@ def main():
 
     # ---- the throughput mode (bf16: the storage type north_star names; it does NOT hold 1e-4) timed beside the headline
     thr = None
-    if rank == 0 and world == 1 and args.throughput_mode and args.throughput_mode != precision:
+    if rank == 0 and world == 1 and args.full and args.throughput_mode and args.throughput_mode != precision:
         m = args.throughput_mode
         if m in modes:
             thr = {'precision': m, 'value': modes[m]['value'], 'ms_per_step': modes[m]['ms_per_step']}
@@ -1072,7 +1091,7 @@ def main():
     # of the first dense layer only, learning/ase_network_builder.py:262-311), and 8 GPUs are the driver's to measure
     cfg5 = None
     n_opt_head = cfg['mini_epochs'] * (Bl // cfg['minibatch_size'])
-    if rank == 0 and world == 1 and args.config5:
+    if rank == 0 and world == 1 and args.full and args.config5:
         del agent
         head['agent'] = None
         torch.cuda.empty_cache()
@@ -1150,7 +1169,7 @@ def main():
                 'dist': dist_info,
                 'config5_16384_envs': cfg5, 'modes': modes, 'parity': par,
                 'last_train_result': {k: round(v, 6) for k, v in head['last'].items()}}
-        detail = write_detail(full, args.detail)
+        detail = write_detail(full, args.detail) if args.full else None
         line = compact_line(full, detail)
         sys.stdout.flush()
         try:        # RCCL's version banner sits in the C stdio buffer until exit: push it out BEFORE the JSON line

@@ -34,7 +34,7 @@ for M, N, K in [(16384, 1024, 1024), (32768, 1024, 1024), (32768, 1024, 320), (1
     ms = timeit(lambda: be.gemm_nt(A, B, C, M, N, K, bias=bias, act=L.ACT_RELU, mask_out=bits))
     out.append(f'{M}x{N}x{K} {ms * 1e3:.1f}us {2 * M * N * K / ms / 1e9:.0f}TF')
 print(sys.argv[1], 'NT f16:', ' | '.join(out), flush=True)
-sys.argv = ['bench.py', '--gpus', '1', '--steps', '20', '--warmup', '3', '--precision', sys.argv[2], '--no-cpu-baseline', '--no-config5',
+sys.argv = ['bench.py', '--full', '--gpus', '1', '--steps', '20', '--warmup', '3', '--precision', sys.argv[2], '--no-cpu-baseline', '--no-config5',
             '--throughput-mode', 'none', '--detail', ''] + os.environ.get('AB_EXTRA', '').split()
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):          # (stderr stays a real file: bench.py enables faulthandler on it)

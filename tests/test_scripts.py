@@ -87,6 +87,30 @@ def test_bench_stdout_line_fits_the_drivers_tail():
     assert set(bench.DTYPE_OF) == set(bench.MODE_NOTE) == set(bench.MFMA_PEAK_TFLOPS)
 
 
+def test_plain_bench_line_keeps_the_contract_keys():
+    """A plain run (no --full) has no oracle leg, no roofline pass and no side runs: its line still carries every contract key,
+    the headline as given, and null where a --full leg would report."""
+    bench = _load_bench()
+    full = json.loads(open(os.path.join(ROOT, 'profiles', 'r03_bench_n1_bf16.json')).read().strip().splitlines()[-1])
+    extras = ('roofline', 'cpu_baseline', 'parity', 'qualifying_mode', 'throughput_mode', 'strict_mode', 'config5_16384_envs')
+    for k in extras:
+        full[k] = None
+    full['fallthrough'] = []
+    line = bench.compact_line(full, None)
+    for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
+              'dtype', 'data'):
+        assert line[k] == full[k], k
+    assert all(line[k] is None for k in extras) and line['fallthrough'] == [] and line['detail'] is None
+    assert len(json.dumps(line)) < 5000
+
+
+def test_plain_run_refuses_options_of_the_full_run():
+    """--modes and --breakdown only mean something with --full: a plain run stops at the argument check instead of ignoring them."""
+    for extra in (['--modes', 'bf16'], ['--breakdown']):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + extra, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and 'need --full' in r.stderr, (extra, r.stderr[-500:])
+
+
 def test_round4_bench_line_is_compact_and_complete():
     """The driver-form line of round 4 as committed (profiles/r04_bench_n1.json): under the driver's 8 KB tail, headline = the
     qualifying mode, roofline / cpu_baseline / parity present as scalars, fresh-state parity inside BASELINE's 1e-4."""
