@@ -252,6 +252,75 @@ class HipBackend:
                                               ia(clips['key_body_ids']), K, *[_ptr(o) for o in out], self._stream()), "motion_state")
         return out
 
+    # ------------------------------------------------------------------ environment side (N5)
+    @staticmethod
+    def _f32c(*ts):
+        for t in ts:
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous()), "state tensors are contiguous f32"
+
+    @staticmethod
+    def _rows(obs, env_ids):
+        assert obs.dtype == torch.float32 and obs.dim() == 2 and obs.stride(1) == 1, "obs: f32 [rows, columns], unit column stride"
+        if env_ids is None:
+            return None, 0
+        assert env_ids.dtype == torch.int32 and env_ids.is_contiguous() and env_ids.dim() == 1
+        return env_ids, env_ids.numel()
+
+    def humanoid_obs_max(self, body_pos, body_rot, body_vel, body_ang_vel, local_root_obs, root_height_obs, obs, col_offset=0,
+                         env_ids=None):
+        """compute_humanoid_observations_max (env/tasks/humanoid.py:592-636) into columns col_offset.. of obs [n_envs, >=]; with
+        env_ids (int32) only those environments are computed and only their rows written."""
+        n, B = body_pos.shape[0], body_pos.shape[1]
+        self._f32c(body_pos, body_rot, body_vel, body_ang_vel)
+        ids, n_ids = self._rows(obs, env_ids)
+        assert obs.shape[0] >= n and body_rot.shape == (n, B, 4) and body_vel.shape == body_ang_vel.shape == body_pos.shape == (n, B, 3)
+        L.check(self.lib.ase_hip_humanoid_obs_max(_ptr(body_pos), _ptr(body_rot), _ptr(body_vel), _ptr(body_ang_vel), n, B,
+                                                  int(local_root_obs), int(root_height_obs), _ptr(ids), n_ids, _ptr(obs),
+                                                  obs.stride(0), int(col_offset), self._stream()), "humanoid_obs_max")
+
+    def humanoid_reset(self, progress_buf, contact_forces, body_pos, termination_heights, contact_body_ids, max_episode_length,
+                       enable_early_termination, reset, terminated, tar_contact_forces=None, strike_body_ids=None):
+        """compute_humanoid_reset (env/tasks/humanoid.py:645-672); with tar_contact_forces + strike_body_ids the strike form
+        (env/tasks/humanoid_strike.py:255-297).  The body id lists are python lists; reset / terminated: int64 [n_envs]."""
+        n, B = body_pos.shape[0], body_pos.shape[1]
+        self._f32c(contact_forces, body_pos, termination_heights, tar_contact_forces)
+        for t in (progress_buf, reset, terminated):
+            assert t.dtype == torch.int64 and t.is_contiguous() and t.numel() == n
+        assert contact_forces.shape == body_pos.shape == (n, B, 3) and termination_heights.numel() == B
+        assert tar_contact_forces is None or tar_contact_forces.shape == (n, 3)
+        ia = lambda xs: None if xs is None else (C.c_int32 * len(xs))(*[int(x) for x in xs])
+        L.check(self.lib.ase_hip_humanoid_reset(_ptr(progress_buf), _ptr(contact_forces), _ptr(body_pos), _ptr(termination_heights),
+                                                ia(contact_body_ids), len(contact_body_ids), _ptr(tar_contact_forces),
+                                                ia(strike_body_ids), 0 if strike_body_ids is None else len(strike_body_ids), n, B,
+                                                float(max_episode_length), int(enable_early_termination), _ptr(reset),
+                                                _ptr(terminated), self._stream()), "humanoid_reset")
+
+    def task_obs(self, kind, obs, col_offset=0, env_ids=None, root_states=None, tar_a=None, tar_b=None, tar_speed=None,
+                 tar_states=None):
+        """Task observation of kind L.TASK_* (5 / 2 / 3 / 15 columns, see ase_hip.h) into columns col_offset.. of obs."""
+        self._f32c(root_states, tar_a, tar_b, tar_speed, tar_states)
+        ids, n_ids = self._rows(obs, env_ids)
+        n = obs.shape[0] if root_states is None else root_states.shape[0]
+        for t, cols in ((root_states, 13), (tar_a, 3 if kind == L.TASK_REACH else 2), (tar_b, 2), (tar_speed, 1), (tar_states, 13)):
+            assert t is None or t.numel() == n * cols, "task_obs: operand shape"
+        L.check(self.lib.ase_hip_task_obs(int(kind), _ptr(root_states), _ptr(tar_a), _ptr(tar_b), _ptr(tar_speed), _ptr(tar_states), n,
+                                          _ptr(ids), n_ids, _ptr(obs), obs.stride(0), int(col_offset), self._stream()), "task_obs")
+
+    def task_reward(self, kind, reward, root_states=None, prev_root_pos=None, tar_a=None, tar_b=None, tar_speed=None,
+                    tar_states=None, body_pos=None, body_id=0, dt=0.0):
+        """Task reward of kind L.TASK_* into reward [n_envs]; tar_speed: tensor [n] (heading) or python float (location)."""
+        speed_t = tar_speed if torch.is_tensor(tar_speed) else None
+        self._f32c(root_states, prev_root_pos, tar_a, tar_b, speed_t, tar_states, body_pos, reward)
+        n = reward.numel()
+        for t, cols in ((root_states, 13), (prev_root_pos, 3), (tar_a, 3 if kind == L.TASK_REACH else 2), (tar_b, 2), (speed_t, 1),
+                        (tar_states, 13)):
+            assert t is None or t.numel() == n * cols, "task_reward: operand shape"
+        assert body_pos is None or (body_pos.dim() == 3 and body_pos.shape[0] == n and body_pos.shape[2] == 3)
+        L.check(self.lib.ase_hip_task_reward(int(kind), _ptr(root_states), _ptr(prev_root_pos), _ptr(tar_a), _ptr(tar_b), _ptr(speed_t),
+                                             0.0 if speed_t is not None or tar_speed is None else float(tar_speed), _ptr(tar_states),
+                                             _ptr(body_pos), 0 if body_pos is None else body_pos.shape[1], int(body_id), float(dt), n,
+                                             _ptr(reward), self._stream()), "task_reward")
+
     # ------------------------------------------------------------------ normaliser / gather
     def rms_moments(self, src, D, idx, remap, M, state, sums):
         L.check(self.lib.ase_hip_rms_moments(_ptr(src), _ld(src), D, _ptr(idx), remap[0], remap[1], M, _ptr(state),

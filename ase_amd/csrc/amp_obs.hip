@@ -4,6 +4,7 @@
 // staged through LDS so that both the history shift and the new slot are row-contiguous accesses.
 // Follows env/tasks/humanoid_amp.py:248-266,280-316 and env/tasks/humanoid.py:523-552 (reference, /root/reference/ase).
 #include "common.h"
+#include "quat.h"
 
 namespace {
 
@@ -18,33 +19,6 @@ struct AmpObsArgs {
     int dof_off[kMaxJoints + 1];
 };
 
-struct V3 { float x, y, z; };
-struct Q4 { float x, y, z, w; };
-
-// v rotated by the unit quaternion q (xyzw):  v (2 w^2 - 1) + 2 w (u x v) + 2 u (u . v)
-__device__ __forceinline__ V3 rot(const Q4& q, const V3& v) {
-    const float a = 2.f * q.w * q.w - 1.f, d = 2.f * (q.x * v.x + q.y * v.y + q.z * v.z), w2 = 2.f * q.w;
-    return V3{v.x * a + (q.y * v.z - q.z * v.y) * w2 + q.x * d,
-              v.y * a + (q.z * v.x - q.x * v.z) * w2 + q.y * d,
-              v.z * a + (q.x * v.y - q.y * v.x) * w2 + q.z * d};
-}
-__device__ __forceinline__ Q4 mul(const Q4& a, const Q4& b) {
-    return Q4{a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x,
-              a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
-}
-__device__ __forceinline__ Q4 from_angle_axis(float angle, V3 ax) {
-    const float n = fmaxf(sqrtf(ax.x * ax.x + ax.y * ax.y + ax.z * ax.z), 1e-9f);
-    const float s = sinf(0.5f * angle) / n, c = cosf(0.5f * angle);
-    Q4 q{ax.x * s, ax.y * s, ax.z * s, c};
-    const float m = fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-9f);
-    return Q4{q.x / m, q.y / m, q.z / m, q.w / m};
-}
-// tangent (rotated x axis) and normal (rotated z axis)
-__device__ __forceinline__ void tan_norm(const Q4& q, float* o) {
-    const V3 t = rot(q, V3{1.f, 0.f, 0.f}), n = rot(q, V3{0.f, 0.f, 1.f});
-    o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = n.x; o[4] = n.y; o[5] = n.z;
-}
-
 __global__ __launch_bounds__(kEnvPerBlock) void amp_obs_kernel(AmpObsArgs a) {
     extern __shared__ float tile[];                       // [kEnvPerBlock][F + 1]
     const int F = a.F, pitch = F + 1;
@@ -55,8 +29,7 @@ __global__ __launch_bounds__(kEnvPerBlock) void amp_obs_kernel(AmpObsArgs a) {
         const float* rp = a.root_pos + 3 * (int64_t)n;
         const float* rq = a.root_rot + 4 * (int64_t)n;
         const Q4 q{rq[0], rq[1], rq[2], rq[3]};
-        const V3 d = rot(q, V3{1.f, 0.f, 0.f});
-        const Q4 hq = from_angle_axis(-atan2f(d.y, d.x), V3{0.f, 0.f, 1.f});      // inverse heading rotation
+        const Q4 hq = heading_quat_inv(q);
         o[0] = a.root_height ? rp[2] : 0.f;
         tan_norm(a.local_root ? mul(hq, q) : q, o + 1);
         const float* v = a.root_vel + 3 * (int64_t)n;
@@ -118,8 +91,6 @@ struct MotionArgs {
     int n, B, D, J, K;
     int dof_off[kMaxJoints + 1], dof_body[kMaxJoints], key_body[kMaxJoints];
 };
-
-__device__ __forceinline__ Q4 load_q(const float* p) { return Q4{p[0], p[1], p[2], p[3]}; }
 
 __device__ __forceinline__ Q4 slerp(const Q4& a, Q4 b, float t) {
     float c = a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;

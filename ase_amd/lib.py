@@ -17,6 +17,8 @@ TN_SLAB = 65536 + 256        # ASE_TN_SLAB: floats per work item in the grouped 
 F32, BF16, F32X3, F16, F32H3 = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SILU, ACT_ELU, ACT_GELU, ACT_SIGMOID, ACT_SELU, ACT_SOFTPLUS = range(9)
 AUX_NONE, AUX_RELU_MASK, AUX_TANH_GRAD, AUX_RELU_BITS, AUX_PREACT = 0, 1, 2, 3, 4
+TASK_HEADING, TASK_LOCATION, TASK_REACH, TASK_STRIKE = range(4)     # ASE_TASK_*
+TASK_OBS_COLS = (5, 2, 3, 15)                                       # columns ase_hip_task_obs writes per kind
 
 # accumulator slots (ASE_ACC_*)
 (ACC_MASK_SUM, ACC_A_LOSS, ACC_B_LOSS, ACC_ENTROPY, ACC_CLIPPED, ACC_C_LOSS, ACC_KL, ACC_DIV, ACC_BCE_AGENT,
@@ -78,6 +80,10 @@ SIGNATURES = {
     "ase_hip_debug_nt_profile_clock": [_i],
     "ase_hip_motion_state": [_p] * 6 + [_i] + [_p] * 6 + [_i, _p, _p, _i, _p, _i] + [_p] * 8,
     "ase_hip_build_amp_obs": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _p],
+    "ase_hip_humanoid_obs_max": [_p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _i64, _i, _p],
+    "ase_hip_humanoid_reset": [_p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _f, _i, _p, _p, _p],
+    "ase_hip_task_obs": [_i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i64, _i, _p],
+    "ase_hip_task_reward": [_i, _p, _p, _p, _p, _p, _f, _p, _p, _i, _i, _f, _i, _p, _p],
     "ase_hip_gemm_nt_kernel_id": [_i, _i, _i, _i],
     "ase_hip_apply_multi": [_p, _i, _p, _p, _i, _p],
     "ase_hip_gemm_tn_grouped_plan": [_p, _i, _i, _p, _i, _p, _p, _i, _p],

@@ -33,6 +33,14 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
   enc_div_loss(enc_pred, enc_z, mu, mu_div, z, z_new, enc_coef, div_coef, div_tar)
       -> (stats [2], d_enc, d_mu, d_mu_div)            ASEAgent._enc_loss + _diversity_loss (learning/ase_agent.py:413-418,445-467)
 
+  humanoid_obs_max(body_pos, body_rot, body_vel, body_ang_vel, local_root_obs, root_height_obs) -> obs [n, 15 B - 2]
+                                                      compute_humanoid_observations_max (env/tasks/humanoid.py:592-636)
+  humanoid_reset(progress_buf, contact_forces, body_pos, termination_heights, contact_body_ids, max_episode_length,
+                 enable_early_termination, tar_contact_forces=None, strike_body_ids=None) -> (reset, terminated)
+                                                      compute_humanoid_reset, plain and strike form
+  task_obs(kind, root_states, ...) -> obs / task_reward(kind, n_envs, ...) -> reward
+                                                      the observation / reward functions of humanoid_heading / _location / _reach / _strike
+
 ``HipLinear`` is an ``nn.Linear`` whose forward is ``linear_act`` (optionally with a fused ReLU / tanh).
 """
 import torch
@@ -494,3 +502,100 @@ def enc_div_loss(enc_pred: torch.Tensor, enc_z: torch.Tensor, mu: torch.Tensor, 
 @enc_div_loss.register_fake
 def _(enc_pred, enc_z, mu, mu_div, z, z_new, enc_coef, div_coef, div_tar):
     return mu.new_empty(2), torch.empty_like(enc_pred), torch.empty_like(mu), torch.empty_like(mu)
+
+
+# ---- environment side: functional forms of the tensor functions a task runs every simulator step ----
+_TASKS = {'heading': L.TASK_HEADING, 'location': L.TASK_LOCATION, 'reach': L.TASK_REACH, 'strike': L.TASK_STRIKE}
+
+
+def _task_kind(kind):
+    _check(kind in _TASKS, f"task kind must be one of {sorted(_TASKS)}, got {kind!r}")
+    return _TASKS[kind]
+
+
+def _opt_f32c(t, name):
+    return None if t is None else _f32c(t, name)
+
+
+@torch.library.custom_op('ase_hip::humanoid_obs_max', mutates_args=(), device_types='cuda')
+def humanoid_obs_max(body_pos: torch.Tensor, body_rot: torch.Tensor, body_vel: torch.Tensor, body_ang_vel: torch.Tensor,
+                     local_root_obs: bool, root_height_obs: bool) -> torch.Tensor:
+    """compute_humanoid_observations_max (env/tasks/humanoid.py:592-636): [n, B, 3 | 4] state -> [n, 15 B - 2]."""
+    _check(body_pos.dim() == 3 and body_pos.shape[2] == 3 and body_rot.shape == (*body_pos.shape[:2], 4) and
+           body_vel.shape == body_pos.shape and body_ang_vel.shape == body_pos.shape,
+           'humanoid_obs_max: body_pos / body_vel / body_ang_vel [n, B, 3], body_rot [n, B, 4]')
+    n, B = body_pos.shape[0], body_pos.shape[1]
+    obs = torch.empty(n, 15 * B - 2, dtype=torch.float32, device=body_pos.device)
+    _backend().humanoid_obs_max(_f32c(body_pos, 'body_pos'), _f32c(body_rot, 'body_rot'), _f32c(body_vel, 'body_vel'),
+                                _f32c(body_ang_vel, 'body_ang_vel'), local_root_obs, root_height_obs, obs)
+    return obs
+
+
+@humanoid_obs_max.register_fake
+def _(body_pos, body_rot, body_vel, body_ang_vel, local_root_obs, root_height_obs):
+    return body_pos.new_empty(body_pos.shape[0], 15 * body_pos.shape[1] - 2, dtype=torch.float32)
+
+
+@torch.library.custom_op('ase_hip::humanoid_reset', mutates_args=(), device_types='cuda')
+def humanoid_reset(progress_buf: torch.Tensor, contact_forces: torch.Tensor, body_pos: torch.Tensor,
+                   termination_heights: torch.Tensor, contact_body_ids: list[int], max_episode_length: float,
+                   enable_early_termination: bool, tar_contact_forces: torch.Tensor | None = None,
+                   strike_body_ids: list[int] | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """compute_humanoid_reset (env/tasks/humanoid.py:645-672; strike form env/tasks/humanoid_strike.py:255-297 when
+    tar_contact_forces and strike_body_ids are given) -> (reset, terminated), int64 [n]."""
+    _check(progress_buf.dtype == torch.int64 and progress_buf.dim() == 1, 'humanoid_reset: progress_buf int64 [n]')
+    _check(contact_forces.shape == body_pos.shape and body_pos.dim() == 3 and body_pos.shape[0] == progress_buf.shape[0] and
+           termination_heights.numel() == body_pos.shape[1], 'humanoid_reset: contact_forces / body_pos [n, B, 3], termination_heights [B]')
+    _check((tar_contact_forces is None) == (strike_body_ids is None), 'humanoid_reset: the strike form takes tar_contact_forces AND strike_body_ids')
+    reset, terminated = torch.empty_like(progress_buf), torch.empty_like(progress_buf)
+    _backend().humanoid_reset(progress_buf.contiguous(), _f32c(contact_forces, 'contact_forces'), _f32c(body_pos, 'body_pos'),
+                              _f32c(termination_heights, 'termination_heights'), contact_body_ids, max_episode_length,
+                              enable_early_termination, reset, terminated, _opt_f32c(tar_contact_forces, 'tar_contact_forces'),
+                              strike_body_ids)
+    return reset, terminated
+
+
+@humanoid_reset.register_fake
+def _(progress_buf, contact_forces, body_pos, termination_heights, contact_body_ids, max_episode_length, enable_early_termination,
+      tar_contact_forces=None, strike_body_ids=None):
+    return torch.empty_like(progress_buf), torch.empty_like(progress_buf)
+
+
+@torch.library.custom_op('ase_hip::task_obs', mutates_args=(), device_types='cuda')
+def task_obs(kind: str, root_states: torch.Tensor, tar_a: torch.Tensor | None = None, tar_b: torch.Tensor | None = None,
+             tar_speed: torch.Tensor | None = None, tar_states: torch.Tensor | None = None) -> torch.Tensor:
+    """Task observation of 'heading' | 'location' | 'reach' | 'strike' -> [n, 5 | 2 | 3 | 15] (operands: see ase_hip_task_obs)."""
+    k = _task_kind(kind)
+    obs = torch.empty(root_states.shape[0], L.TASK_OBS_COLS[k], dtype=torch.float32, device=root_states.device)
+    _backend().task_obs(k, obs, 0, None, _f32c(root_states, 'root_states', 13), _opt_f32c(tar_a, 'tar_a'), _opt_f32c(tar_b, 'tar_b'),
+                        _opt_f32c(tar_speed, 'tar_speed'), _opt_f32c(tar_states, 'tar_states'))
+    return obs
+
+
+@task_obs.register_fake
+def _(kind, root_states, tar_a=None, tar_b=None, tar_speed=None, tar_states=None):
+    return root_states.new_empty(root_states.shape[0], L.TASK_OBS_COLS[_task_kind(kind)], dtype=torch.float32)
+
+
+@torch.library.custom_op('ase_hip::task_reward', mutates_args=(), device_types='cuda')
+def task_reward(kind: str, n_envs: int, root_states: torch.Tensor | None = None, prev_root_pos: torch.Tensor | None = None,
+                tar_a: torch.Tensor | None = None, tar_b: torch.Tensor | None = None, tar_speed: torch.Tensor | None = None,
+                tar_speed_scalar: float = 0.0, tar_states: torch.Tensor | None = None, body_pos: torch.Tensor | None = None,
+                body_id: int = 0, dt: float = 0.0) -> torch.Tensor:
+    """Task reward of 'heading' | 'location' | 'reach' | 'strike' -> [n_envs] (operands: see ase_hip_task_reward)."""
+    k = _task_kind(kind)
+    some = next((t for t in (root_states, tar_a, tar_states, body_pos) if t is not None), None)
+    _check(some is not None, 'task_reward: no operands')
+    reward = torch.empty(n_envs, dtype=torch.float32, device=some.device)
+    _backend().task_reward(k, reward, _opt_f32c(root_states, 'root_states'), _opt_f32c(prev_root_pos, 'prev_root_pos'),
+                           _opt_f32c(tar_a, 'tar_a'), _opt_f32c(tar_b, 'tar_b'),
+                           _opt_f32c(tar_speed, 'tar_speed') if tar_speed is not None else (tar_speed_scalar if k == L.TASK_LOCATION else None),
+                           _opt_f32c(tar_states, 'tar_states'), _opt_f32c(body_pos, 'body_pos'), body_id, dt)
+    return reward
+
+
+@task_reward.register_fake
+def _(kind, n_envs, root_states=None, prev_root_pos=None, tar_a=None, tar_b=None, tar_speed=None, tar_speed_scalar=0.0,
+      tar_states=None, body_pos=None, body_id=0, dt=0.0):
+    some = next(t for t in (root_states, tar_a, tar_states, body_pos) if t is not None)
+    return some.new_empty(n_envs, dtype=torch.float32)

@@ -491,6 +491,72 @@ int ase_hip_motion_state(const float* gts, const float* grs, const float* lrs, c
                          float* root_vel, float* root_ang_vel, float* dof_vel, float* key_pos, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Environment side: the tensor functions a task runs every simulator step on the rigid-body state.
+ * Quaternions xyzw, every state tensor contiguous f32 on the device.  The observation entries write rows of a caller's
+ * buffer: row e of the output starts at obs + e * ld_obs + col_offset, so the humanoid and the task observation sit side
+ * by side in one obs_buf (env/tasks/humanoid_amp_task.py:51-64).  env_ids (DEVICE int32[n_ids], NULL with n_ids = 0: every
+ * environment) names the environments to compute; only their rows are written (obs_buf[env_ids] = obs), ids outside
+ * [0, n_envs) are skipped.
+ * ------------------------------------------------------------------------------------------- */
+
+/* The policy observation of the humanoid, F = 15 n_bodies - 2 columns (253 for 17 bodies): {root height (0 unless
+ * root_height_obs), heading-local positions of bodies 1.. relative to the root (the root's own three columns are dropped),
+ * tangent + normal of every body's heading-local rotation (6 each), heading-local linear and angular velocities}.  With
+ * local_root_obs the root's six rotation columns are the tangent / normal of its RAW rotation, as in the reference.
+ * body_pos / body_vel / body_ang_vel [n_envs, n_bodies, 3], body_rot [n_envs, n_bodies, 4]; n_bodies <= 64.
+ * Replaces: compute_humanoid_observations_max + _compute_humanoid_obs / _compute_observations
+ *   (env/tasks/humanoid.py:385-413,592-636). */
+int ase_hip_humanoid_obs_max(const float* body_pos, const float* body_rot, const float* body_vel,
+                             const float* body_ang_vel, int n_envs, int n_bodies, int local_root_obs,
+                             int root_height_obs, const int32_t* env_ids, int n_ids, float* obs, int64_t ld_obs,
+                             int col_offset, void* stream);
+
+/* Termination test: terminated = early termination && progress > 1 && (a body outside contact_body_ids carries a contact force
+ * component above 0.1 AND one of them is below its termination height); reset = progress >= max_episode_length - 1 ? 1 :
+ * terminated.  Strike form (tar_contact_forces [n_envs, 3] and strike_body_ids both non-NULL): also terminated when the
+ * target is touched (|x| or |y| force above 1) while a body that is neither a contact nor a strike body carries a force
+ * above 1.  contact_body_ids / strike_body_ids: HOST int32 arrays (turned into body bit masks: n_bodies <= 64);
+ * progress_buf / reset / terminated: int64 [n_envs]; contact_forces, body_pos [n_envs, n_bodies, 3];
+ * termination_heights [n_bodies].
+ * Replaces: compute_humanoid_reset (env/tasks/humanoid.py:645-672) and its strike form
+ *   (env/tasks/humanoid_strike.py:255-297). */
+int ase_hip_humanoid_reset(const int64_t* progress_buf, const float* contact_forces, const float* body_pos,
+                           const float* termination_heights, const int32_t* contact_body_ids, int n_contact,
+                           const float* tar_contact_forces, const int32_t* strike_body_ids, int n_strike, int n_envs,
+                           int n_bodies, float max_episode_length, int enable_early_termination, int64_t* reset,
+                           int64_t* terminated, void* stream);
+
+/* The tasks of the high-level controller.  An operand a kind does not use must be NULL, one it uses must not be. */
+enum { ASE_TASK_HEADING = 0, ASE_TASK_LOCATION = 1, ASE_TASK_REACH = 2, ASE_TASK_STRIKE = 3 };
+
+/* Task observation, 5 / 2 / 3 / 15 columns (root_states [n_envs, 13] = position, rotation, velocity, angular velocity):
+ *   HEADING : tar_a = target direction [n, 2], tar_b = target facing direction [n, 2], tar_speed [n]
+ *             -> {local direction xy, speed, local facing direction xy}
+ *   LOCATION: tar_a = target position [n, 2] -> heading-local xy of (target - root)
+ *   REACH   : tar_a = target position [n, 3] (already relative) -> heading-local xyz
+ *   STRIKE  : tar_states [n, 13] -> heading-local {position (height absolute), rotation tangent + normal, velocity,
+ *             angular velocity}
+ * Replaces: compute_heading_observations (env/tasks/humanoid_heading.py:231-250), compute_location_observations
+ *   (env/tasks/humanoid_location.py:169-183 and env/tasks/humanoid_reach.py:174-182), compute_strike_observations
+ *   (env/tasks/humanoid_strike.py:193-219) + the _compute_task_obs of each task. */
+int ase_hip_task_obs(int kind, const float* root_states, const float* tar_a, const float* tar_b, const float* tar_speed,
+                     const float* tar_states, int n_envs, const int32_t* env_ids, int n_ids, float* obs, int64_t ld_obs,
+                     int col_offset, void* stream);
+
+/* Task reward [n_envs] with the reference's literal weights and scales:
+ *   HEADING : root_states, prev_root_pos [n, 3], tar_a, tar_b, tar_speed [n], dt
+ *   LOCATION: root_states, prev_root_pos, tar_a [n, 2], tar_speed_scalar, dt
+ *   REACH   : body_pos [n, n_bodies, 3] (body_id = the reaching body), tar_a [n, 3]
+ *   STRIKE  : root_states, prev_root_pos, tar_states [n, 13], dt
+ * Replaces: compute_heading_reward (env/tasks/humanoid_heading.py:252-289), compute_location_reward
+ *   (env/tasks/humanoid_location.py:185-232), compute_reach_reward (env/tasks/humanoid_reach.py:184-196),
+ *   compute_strike_reward (env/tasks/humanoid_strike.py:221-252). */
+int ase_hip_task_reward(int kind, const float* root_states, const float* prev_root_pos, const float* tar_a,
+                        const float* tar_b, const float* tar_speed, float tar_speed_scalar, const float* tar_states,
+                        const float* body_pos, int n_bodies, int body_id, float dt, int n_envs, float* reward,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Launch programs: record a sequence of the calls above ONCE (nothing is launched while recording), replay it with 4-5 us
  * of host work per launch on the same HIP streams - the optimisation step as one call, with OUR branch -> stream mapping
  * (a captured hipGraph picks its own; eager launches from Python fall behind the GPU).  Recording is per thread.

@@ -12,6 +12,8 @@ rollout-time inference path.  One JSON line per measurement on stdout.
   shard : ONE rank's share of the sharded data-parallel update (BASELINE configs[2]) on one GPU, for R = 2, 4, 8 ranks: the
           48 optimisation steps of an update at minibatch 16384 / R, amp minibatch 4096 / R (--shard-of R[,R...]); no collectives
           - the compute side of the scaling curve the driver's 8-GPU run would take, and the launch count it has to hide
+  env-tensors: the environment-side launches (policy observation, reset test, task observations / rewards) at 4096 and 16384
+          environments under a launch program, next to the same functions as plain torch ops on the device (reported, not gated)
   infer : get_action_values (eval-mode normalisation + actor + critic forward + sample) on 4096 observations
 """
 import argparse
@@ -95,6 +97,70 @@ def time_updates(ag, n):
         one()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / n
+
+
+def env_tensors_case():
+    """N5: every environment-side launch at 4096 and 16384 environments - HIP events around replays of a launch program that
+    holds the call 50 times - next to the same function as plain torch ops on the same device (tests/emu_env_tensors.py, eager)."""
+    from ase_amd import lib as L
+    from ase_amd.backend import HipBackend
+    from tests.emu_env_tensors import EmuEnvTensors
+    be, emu, dev = HipBackend('cuda:0'), EmuEnvTensors(), 'cuda:0'
+    B, F, REP = 17, 253, 50
+
+    def events(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n * 1e3
+
+    for N in (4096, 16384):
+        g = torch.Generator().manual_seed(N)
+        r = lambda *s: torch.randn(*s, generator=g).to(dev)
+        unit = lambda x: x / x.norm(dim=-1, keepdim=True)
+        pos, rot, vel, ang = r(N, B, 3), unit(r(N, B, 4)), r(N, B, 3), r(N, B, 3)
+        rs = torch.cat([pos[:, 0], rot[:, 0], vel[:, 0], ang[:, 0]], -1).contiguous()
+        prev, tar_states = pos[:, 0] - r(N, 3) / 30, torch.cat([r(N, 3), unit(r(N, 4)), r(N, 6)], -1).contiguous()
+        tar_dir, face, speed, tar2, tar3 = unit(r(N, 2)), unit(r(N, 2)), r(N).abs() + 1, r(N, 2), r(N, 3)
+        contact, tar_contact, heights = r(N, B, 3), r(N, 3), torch.full((B,), 0.15, device=dev)
+        progress = torch.randint(0, 300, (N,), generator=g).to(dev)
+        obs, rew = torch.zeros(N, F + 15, device=dev), torch.zeros(N, device=dev)
+        reset, term = torch.zeros(N, dtype=torch.int64, device=dev), torch.zeros(N, dtype=torch.int64, device=dev)
+        dt = 1.0 / 30.0
+        cases = [('humanoid_obs_max', lambda b: b.humanoid_obs_max(pos, rot, vel, ang, True, True, obs), N * (B * 13 + F) * 4),
+                 ('humanoid_reset', lambda b: b.humanoid_reset(progress, contact, pos, heights, [11, 14], 300.0, True, reset, term),
+                  N * (B * 6 * 4 + 24)),
+                 ('humanoid_reset (strike form)', lambda b: b.humanoid_reset(progress, contact, pos, heights, [11, 14], 300.0, True, reset,
+                                                                             term, tar_contact, [4, 5, 6, 8, 9, 10]), N * (B * 6 * 4 + 36))]
+        ops = {'heading': (dict(root_states=rs, tar_a=tar_dir, tar_b=face, tar_speed=speed),
+                           dict(root_states=rs, prev_root_pos=prev, tar_a=tar_dir, tar_b=face, tar_speed=speed, dt=dt)),
+               'location': (dict(root_states=rs, tar_a=tar2), dict(root_states=rs, prev_root_pos=prev, tar_a=tar2, tar_speed=1.0, dt=dt)),
+               'reach': (dict(root_states=rs, tar_a=tar3), dict(tar_a=tar3, body_pos=pos, body_id=5)),
+               'strike': (dict(root_states=rs, tar_states=tar_states), dict(root_states=rs, prev_root_pos=prev, tar_states=tar_states, dt=dt))}
+        for k, (task, (okw, rkw)) in enumerate(ops.items()):
+            cases.append((f'task_obs {task}', lambda b, k=k, okw=okw: b.task_obs(k, obs, F, None, **okw), None))
+            cases.append((f'task_reward {task}', lambda b, k=k, rkw=rkw: b.task_reward(k, rew, **rkw), None))
+        assert list(ops) == ['heading', 'location', 'reach', 'strike'] and L.TASK_STRIKE == 3
+        for name, call, byt in cases:
+            prog = be.prog_create()
+            be.prog_begin(prog)
+            for _ in range(REP):
+                call(be)
+            be.prog_end(prog)
+            us = events(lambda: be.prog_launch(prog), 400) / REP
+            be.prog_destroy(prog)
+            us_torch = events(lambda: call(emu), 100)
+            line = {'measurement': 'env-tensors ' + name, 'envs': N, 'us_per_call': round(us, 2), 'torch_ops_us_per_call': round(us_torch, 1),
+                    'ratio': round(us_torch / us, 1), 'how': f'HIP events around 400 replays of a launch program of {REP} calls (operands stay cache-resident); '
+                    'torch leg: the same function as eager torch ops on the device, 100 calls', 'device': torch.cuda.get_device_name(0)}
+            if byt:
+                line.update(bytes=byt, GB_per_s=round(byt / us / 1e3, 1))
+            print(json.dumps(line), flush=True)
 
 
 def main():
@@ -187,6 +253,8 @@ def main():
         print(json.dumps({'measurement': 'infer', 'metric': 'rollout inference (get_action_values) env-steps/sec',
                           'value': round(4096 / dt, 1), 'unit': 'env-steps/s', 'us_per_call': round(dt * 1e6, 1), 'envs': 4096,
                           'precision': 'bf16', 'hipgraph': False}), flush=True)
+    if not args.only or 'env-tensors' in args.only.split(','):
+        env_tensors_case()
     if not args.only or 'ampobs' in args.only.split(','):
         # N2: observation production for 4096 envs (one frame + history push) and 5120 demo samples (512 x 10 steps)
         from ase_amd.backend import HipBackend
