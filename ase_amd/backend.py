@@ -321,6 +321,51 @@ class HipBackend:
                                              _ptr(body_pos), 0 if body_pos is None else body_pos.shape[1], int(body_id), float(dt), n,
                                              _ptr(reward), self._stream()), "task_reward")
 
+    # ------------------------------------------------------------------ resets (N6)
+    def amp_reset(self, clips, env_ids, kind, motion_ids, motion_times, src_rows, table, root_states, dof_pos, dof_vel, body_pos,
+                  body_rot, body_vel, body_ang_vel, local_root_obs, root_height_obs, env_dt, hist,
+                  kinds=L.RESET_HAS_TABLE | L.RESET_HAS_MOTION):
+        """HumanoidAMP / HumanoidAMPGetup resets in one launch (env/tasks/humanoid_amp.py:141-246, humanoid_amp_getup.py:
+        109-129; operands: see ase_hip_amp_reset).  clips: the dict of motion_state (its python lists dof_offsets /
+        key_body_ids are always read, dof_body_ids and the tensors only with RESET_HAS_MOTION in kinds).  The plan arrays
+        env_ids / kind / motion_ids / src_rows (int32) and motion_times (f32) have one element per reset row; table =
+        (root_states [T, 13], dof_pos [T, D], dof_vel [T, D]) or None.  root_states [N, 13], dof_pos / dof_vel [N, D] are
+        written in place and may be strided views (dof: both with the same strides, element stride 1 or 2); hist [N, S, F]."""
+        n, S, F = hist.shape
+        B, D = body_pos.shape[1], int(clips['dof_offsets'][-1])
+        J, K = len(clips['dof_offsets']) - 1, len(clips['key_body_ids'])
+        has_table, has_motion = bool(kinds & L.RESET_HAS_TABLE), bool(kinds & L.RESET_HAS_MOTION)
+        ia = lambda xs: (C.c_int32 * len(xs))(*[int(x) for x in xs])
+        self._f32c(body_pos, body_rot, body_vel, body_ang_vel, hist)
+        assert body_rot.shape == (n, B, 4) and body_vel.shape == body_ang_vel.shape == body_pos.shape == (n, B, 3)
+        assert F == 13 + 6 * J + D + 3 * K, "hist: [n_envs, n_steps, 13 + 6 J + D + 3 K]"
+        n_ids = env_ids.numel()
+        for t, dt in ((env_ids, torch.int32), (kind, torch.int32), (motion_ids, torch.int32), (src_rows, torch.int32),
+                      (motion_times, torch.float32)):
+            assert t is None or (t.dtype == dt and t.is_contiguous() and t.numel() == n_ids), "plan: int32 / f32 [n_ids]"
+        for t in (root_states, dof_pos, dof_vel):
+            assert t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == n
+        assert root_states.shape[1] == 13 and root_states.stride(1) == 1
+        assert dof_pos.shape == dof_vel.shape == (n, D) and dof_pos.stride() == dof_vel.stride()
+        tab = (None, None, None)
+        if has_table:
+            tab = table
+            self._f32c(*tab)
+            assert tab[0].dim() == 2 and tab[0].shape[1] == 13 and tab[1].shape == tab[2].shape == (tab[0].shape[0], D)
+        cl = {k: (clips[k] if has_motion else None) for k in ('gts', 'grs', 'lrs', 'grvs', 'gravs', 'dvs', 'lengths', 'num_frames',
+                                                                'dt', 'length_starts')}
+        assert not has_motion or cl['gts'].shape[1] == B, "the clips' skeleton is the simulator's"
+        L.check(self.lib.ase_hip_amp_reset(_ptr(cl['gts']), _ptr(cl['grs']), _ptr(cl['lrs']), _ptr(cl['grvs']), _ptr(cl['gravs']),
+                                           _ptr(cl['dvs']), B, _ptr(cl['lengths']), _ptr(cl['num_frames']), _ptr(cl['dt']),
+                                           _ptr(cl['length_starts']), ia(clips['dof_body_ids']) if has_motion else None,
+                                           ia(clips['dof_offsets']), J, ia(clips['key_body_ids']), K, _ptr(env_ids), _ptr(kind),
+                                           _ptr(motion_ids), _ptr(motion_times), _ptr(src_rows), n_ids, int(kinds), _ptr(tab[0]),
+                                           _ptr(tab[1]), _ptr(tab[2]), 0 if tab[0] is None else tab[0].shape[0],
+                                           _ptr(root_states), root_states.stride(0), _ptr(dof_pos), _ptr(dof_vel), dof_pos.stride(0),
+                                           dof_pos.stride(1), _ptr(body_pos), _ptr(body_rot), _ptr(body_vel), _ptr(body_ang_vel), n,
+                                           int(local_root_obs), int(root_height_obs), float(env_dt), _ptr(hist), S, self._stream()),
+                "amp_reset")
+
     # ------------------------------------------------------------------ normaliser / gather
     def rms_moments(self, src, D, idx, remap, M, state, sums):
         L.check(self.lib.ase_hip_rms_moments(_ptr(src), _ld(src), D, _ptr(idx), remap[0], remap[1], M, _ptr(state),

@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libase_hip.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 PPO_SCRATCH = 1024 * 72 + 8       # ASE_PPO_SCRATCH: doubles of ase_hip_ppo_head's workspace
 PPO_SCRATCH_LS = 1024 * 136 + 8   # ASE_PPO_SCRATCH_LS: the same with a learned log-std
 LS_FROZEN, LS_VECTOR, LS_ROWS = 0, 1, 2     # ASE_LS_*: ase_hip_ppo_head's log-std modes
@@ -19,6 +19,8 @@ ACT_NONE, ACT_RELU, ACT_TANH, ACT_SILU, ACT_ELU, ACT_GELU, ACT_SIGMOID, ACT_SELU
 AUX_NONE, AUX_RELU_MASK, AUX_TANH_GRAD, AUX_RELU_BITS, AUX_PREACT = 0, 1, 2, 3, 4
 TASK_HEADING, TASK_LOCATION, TASK_REACH, TASK_STRIKE = range(4)     # ASE_TASK_*
 TASK_OBS_COLS = (5, 2, 3, 15)                                       # columns ase_hip_task_obs writes per kind
+RESET_FRAME, RESET_TABLE, RESET_MOTION = range(3)                   # ASE_RESET_*: the kinds of a row of ase_hip_amp_reset
+RESET_HAS_TABLE, RESET_HAS_MOTION = 1, 2                            # ASE_RESET_HAS_*: the host mask of kinds that may occur
 
 # accumulator slots (ASE_ACC_*)
 (ACC_MASK_SUM, ACC_A_LOSS, ACC_B_LOSS, ACC_ENTROPY, ACC_CLIPPED, ACC_C_LOSS, ACC_KL, ACC_DIV, ACC_BCE_AGENT,
@@ -84,6 +86,8 @@ SIGNATURES = {
     "ase_hip_humanoid_reset": [_p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _f, _i, _p, _p, _p],
     "ase_hip_task_obs": [_i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i64, _i, _p],
     "ase_hip_task_reward": [_i, _p, _p, _p, _p, _p, _f, _p, _p, _i, _i, _f, _i, _p, _p],
+    "ase_hip_amp_reset": [_p] * 6 + [_i] + [_p] * 6 + [_i, _p, _i] + [_p] * 5 + [_i, _i, _p, _p, _p, _i, _p, _i64, _p, _p, _i64, _i,
+                          _p, _p, _p, _p, _i, _i, _i, _f, _p, _i, _p],
     "ase_hip_gemm_nt_kernel_id": [_i, _i, _i, _i],
     "ase_hip_apply_multi": [_p, _i, _p, _p, _i, _p],
     "ase_hip_gemm_tn_grouped_plan": [_p, _i, _i, _p, _i, _p, _p, _i, _p],

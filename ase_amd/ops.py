@@ -40,6 +40,11 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
                                                       compute_humanoid_reset, plain and strike form
   task_obs(kind, root_states, ...) -> obs / task_reward(kind, n_envs, ...) -> reward
                                                       the observation / reward functions of humanoid_heading / _location / _reach / _strike
+  amp_reset(root_states, dof_pos, dof_vel, hist, body_pos, body_rot, body_vel, body_ang_vel, env_ids, kind, motion_ids,
+            motion_times, src_rows, clip tensors ..., tab_root_states, tab_dof_pos, tab_dof_vel, dof_body_ids, dof_offsets,
+            key_body_ids, local_root_obs, root_height_obs, env_dt) -> ()      (root_states, dof_pos, dof_vel, hist written in place)
+                                                      HumanoidAMP._reset_actors + _init_amp_obs, the get-up task's fall episodes
+                                                      (env/tasks/humanoid_amp.py:141-246, humanoid_amp_getup.py:109-129)
 
 ``HipLinear`` is an ``nn.Linear`` whose forward is ``linear_act`` (optionally with a fused ReLU / tanh).
 """
@@ -599,3 +604,30 @@ def _(kind, n_envs, root_states=None, prev_root_pos=None, tar_a=None, tar_b=None
       tar_states=None, body_pos=None, body_id=0, dt=0.0):
     some = next(t for t in (root_states, tar_a, tar_states, body_pos) if t is not None)
     return some.new_empty(n_envs, dtype=torch.float32)
+
+
+@torch.library.custom_op('ase_hip::amp_reset', mutates_args=('root_states', 'dof_pos', 'dof_vel', 'hist'), device_types='cuda')
+def amp_reset(root_states: torch.Tensor, dof_pos: torch.Tensor, dof_vel: torch.Tensor, hist: torch.Tensor, body_pos: torch.Tensor,
+              body_rot: torch.Tensor, body_vel: torch.Tensor, body_ang_vel: torch.Tensor, env_ids: torch.Tensor, kind: torch.Tensor,
+              motion_ids: torch.Tensor | None, motion_times: torch.Tensor | None, src_rows: torch.Tensor | None,
+              gts: torch.Tensor | None, grs: torch.Tensor | None, lrs: torch.Tensor | None, grvs: torch.Tensor | None,
+              gravs: torch.Tensor | None, dvs: torch.Tensor | None, lengths: torch.Tensor | None, num_frames: torch.Tensor | None,
+              dt: torch.Tensor | None, length_starts: torch.Tensor | None, tab_root_states: torch.Tensor | None,
+              tab_dof_pos: torch.Tensor | None, tab_dof_vel: torch.Tensor | None, dof_body_ids: list[int], dof_offsets: list[int],
+              key_body_ids: list[int], local_root_obs: bool, root_height_obs: bool, env_dt: float) -> None:
+    """HumanoidAMP / HumanoidAMPGetup resets in one launch (operands: see ase_hip_amp_reset): root_states [N, 13], dof_pos /
+    dof_vel [N, D] (strided views allowed) and hist [N, S, F] are written in place.  Rows of kind 'table' need the three tab_*
+    tensors and src_rows, rows of kind 'motion' the clip tensors, motion_ids and motion_times; without them such rows are skipped."""
+    clip = (gts, grs, lrs, grvs, gravs, dvs, lengths, num_frames, dt, length_starts, motion_ids, motion_times)
+    tab = (tab_root_states, tab_dof_pos, tab_dof_vel, src_rows)
+    has_motion, has_table = all(t is not None for t in clip), all(t is not None for t in tab)
+    _check(has_motion or all(t is None for t in clip), 'amp_reset: the clip tensors, motion_ids and motion_times come together')
+    _check(has_table or all(t is None for t in tab), 'amp_reset: the state table and src_rows come together')
+    clips = {'dof_body_ids': dof_body_ids, 'dof_offsets': dof_offsets, 'key_body_ids': key_body_ids}
+    if has_motion:
+        clips.update(gts=gts, grs=grs, lrs=lrs, grvs=grvs, gravs=gravs, dvs=dvs, lengths=lengths, num_frames=num_frames, dt=dt,
+                     length_starts=length_starts)
+    _backend().amp_reset(clips, env_ids, kind, motion_ids, motion_times, src_rows, tab[:3] if has_table else None, root_states, dof_pos,
+                         dof_vel, _f32c(body_pos, 'body_pos'), _f32c(body_rot, 'body_rot'), _f32c(body_vel, 'body_vel'),
+                         _f32c(body_ang_vel, 'body_ang_vel'), local_root_obs, root_height_obs, env_dt, hist,
+                         (L.RESET_HAS_TABLE if has_table else 0) | (L.RESET_HAS_MOTION if has_motion else 0))

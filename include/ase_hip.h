@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ASE_HIP_ABI_VERSION 8
+#define ASE_HIP_ABI_VERSION 9
 
 enum { ASE_F32 = 0, ASE_BF16 = 1, ASE_F32X3 = 2 /* f32 storage, products as 3 bf16 MFMAs on a hi/lo split (GEMMs only) */,
        ASE_F32H3 = 4 /* 4-byte storage, products as 3 f16 MFMAs on hi/lo splits of operands scaled by 2^ea / 2^eb (the exponents ride in
@@ -555,6 +555,47 @@ int ase_hip_task_reward(int kind, const float* root_states, const float* prev_ro
                         const float* tar_b, const float* tar_speed, float tar_speed_scalar, const float* tar_states,
                         const float* body_pos, int n_bodies, int body_id, float dt, int n_envs, float* reward,
                         void* stream);
+
+/* HumanoidAMP / HumanoidAMPGetup resets (ABI 9): for n_ids environments, state initialisation and the refill of
+ * their AMP observation history hist [n_envs, n_steps, F] (F as in ase_hip_build_amp_obs), all in ONE launch.
+ * Row i of the plan (DEVICE arrays of length n_ids, read when the launch runs - a recorded launch follows their
+ * contents; n_ids is fixed when it is recorded) resets environment e = env_ids[i] the way kind[i] says:
+ *   ASE_RESET_FRAME : slot 0 of e's history is recomputed, nothing else is touched (_compute_amp_observations(env_ids);
+ *                     the recovery episodes of the get-up task)
+ *   ASE_RESET_TABLE : root_states / dof_pos / dof_vel of e are copied from row src_rows[i] of the state table
+ *                     (tab_root_states [n_tab, 13], tab_dof_pos / tab_dof_vel [n_tab, D]: the initial state with
+ *                     src_rows[i] = e for _reset_default, the fall states for _reset_fall_episode), slot 0 is computed and
+ *                     copied into slots 1 .. n_steps - 1 (_init_amp_obs_default)
+ *   ASE_RESET_MOTION: the pose of motion motion_ids[i] at motion_times[i] (the sampler of ase_hip_motion_state, same clip
+ *                     tensors and HOST index arrays) goes to root_states[e, 0:13], dof_pos[e], dof_vel[e]
+ *                     (_reset_ref_state_init + _set_env_state); slot 0 is computed, slot k = 1 .. n_steps - 1 is the frame
+ *                     of the motion at the f32 time motion_times[i] + (float)(-env_dt) * (float)k, used UNCLAMPED as the
+ *                     reference does (_init_amp_obs_ref): before the clip's start the phase clips to frame 0 and the
+ *                     blend turns negative, i.e. the interpolation extrapolates.
+ * Slot 0 always comes from the simulator tensors body_pos / body_vel / body_ang_vel [n_envs, n_bodies, 3], body_rot
+ * [n_envs, n_bodies, 4] (root = body 0, key bodies = key_body_ids) and e's dof_pos / dof_vel as this call leaves them.
+ * env_ids MUST BE DISTINCT (two rows of one environment race).  A row whose id lies outside [0, n_envs), whose kind is
+ * unknown or not announced in `kinds`, or whose src_rows[i] lies outside the table is skipped; motion_ids must be valid.
+ * kinds: HOST mask of the kinds that may occur, ASE_RESET_HAS_TABLE | ASE_RESET_HAS_MOTION; without a bit the operands of
+ * that kind (table + src_rows; clip tensors + dof_body_ids + motion_ids + motion_times) may be NULL.
+ * root_states: row e at root_states + e * ld_root.  Dof d of environment e: dof_pos[e * ld_dof + d * dof_stride], same
+ * for dof_vel; dof_stride = 1: two plain tensors, 2: the simulator's interleaved [n_envs, D, 2] tensor (dof_vel =
+ * dof_pos + 1).  n_steps <= 64; n_joints, n_key <= 32.
+ * Replaces: HumanoidAMP._reset_actors / _reset_default / _reset_ref_state_init / _set_env_state / _init_amp_obs /
+ *   _init_amp_obs_default / _init_amp_obs_ref / _compute_amp_observations(env_ids) (env/tasks/humanoid_amp.py:141-246,
+ *   257-275), HumanoidAMPGetup._reset_fall_episode / _init_amp_obs (env/tasks/humanoid_amp_getup.py:109-129). */
+enum { ASE_RESET_FRAME = 0, ASE_RESET_TABLE = 1, ASE_RESET_MOTION = 2 };
+enum { ASE_RESET_HAS_TABLE = 1, ASE_RESET_HAS_MOTION = 2 };
+int ase_hip_amp_reset(const float* gts, const float* grs, const float* lrs, const float* grvs, const float* gravs,
+                      const float* dvs, int n_bodies, const float* lengths, const int32_t* num_frames, const float* dt,
+                      const int32_t* length_starts, const int32_t* dof_body_ids, const int32_t* dof_offsets, int n_joints,
+                      const int32_t* key_body_ids, int n_key, const int32_t* env_ids, const int32_t* kind,
+                      const int32_t* motion_ids, const float* motion_times, const int32_t* src_rows, int n_ids, int kinds,
+                      const float* tab_root_states, const float* tab_dof_pos, const float* tab_dof_vel, int n_tab,
+                      float* root_states, int64_t ld_root, float* dof_pos, float* dof_vel, int64_t ld_dof, int dof_stride,
+                      const float* body_pos, const float* body_rot, const float* body_vel, const float* body_ang_vel,
+                      int n_envs, int local_root_obs, int root_height_obs, float env_dt, float* hist, int n_steps,
+                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Launch programs: record a sequence of the calls above ONCE (nothing is launched while recording), replay it with 4-5 us

@@ -14,6 +14,8 @@ rollout-time inference path.  One JSON line per measurement on stdout.
           - the compute side of the scaling curve the driver's 8-GPU run would take, and the launch count it has to hide
   env-tensors: the environment-side launches (policy observation, reset test, task observations / rewards) at 4096 and 16384
           environments under a launch program, next to the same functions as plain torch ops on the device (reported, not gated)
+  amp-reset: the fused HumanoidAMP reset launch (motion-state rows, 10 history slots) for 64 and 4096 of 4096 environments under a
+          launch program, next to the same result composed from the sampler and the frame builder (reported, not gated)
   infer : get_action_values (eval-mode normalisation + actor + critic forward + sample) on 4096 observations
 """
 import argparse
@@ -163,6 +165,90 @@ def env_tensors_case():
             print(json.dumps(line), flush=True)
 
 
+def amp_reset_case():
+    """N6: ase_hip_amp_reset for n_ids of 4096 environments, every row a motion-state row - HIP events around replays of a launch
+    program that holds the call 50 times - next to the same result built from the entries that existed before it: motion_state at
+    the sampled times, three indexed writes, build_amp_obs of the current frame, motion_state at the S - 1 earlier times per row,
+    build_amp_obs into a temporary, two indexed writes into the history (eager: the torch ops between the launches cannot be
+    recorded)."""
+    from ase_amd import lib as L
+    from ase_amd.backend import HipBackend
+    from ase_amd.motion_lib import DeviceMotionLib
+    be, dev = HipBackend('cuda:0'), 'cuda:0'
+    clips = torch.load(os.path.join(ROOT, 'tests', 'golden', 'motion_state.pt'), weights_only=False)['clips']
+    ml = DeviceMotionLib.from_arrays(clips, be, dev)
+    c = ml.clips
+    N, B, S, REP, dt = 4096, c['gts'].shape[1], 10, 50, 1.0 / 30.0
+    D, J, K, kb = c['dof_offsets'][-1], len(c['dof_body_ids']), len(c['key_body_ids']), c['key_body_ids']
+    F = 13 + 6 * J + D + 3 * K
+
+    def events(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(n):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n * 1e3
+
+    g = torch.Generator().manual_seed(6)
+    r = lambda *s: torch.randn(*s, generator=g).to(dev)
+    pos, rot, vel, ang = r(N, B, 3), r(N, B, 4), r(N, B, 3), r(N, B, 3)
+    rot = (rot / rot.norm(dim=-1, keepdim=True)).contiguous()
+    root, dof_pos, dof_vel, hist = r(N, 13), r(N, D), r(N, D), torch.zeros(N, S, F, device=dev)
+    for n_ids in (64, 4096):
+        ids = torch.randperm(N, generator=g)[:n_ids].to(torch.int32).to(dev)
+        mids = torch.randint(0, ml.num_motions(), (n_ids,), generator=g).to(torch.int32).to(dev)
+        times = (torch.rand(n_ids, generator=g).to(dev) * c['lengths'][mids.long()]).contiguous()
+        kind = torch.full_like(ids, L.RESET_MOTION)
+
+        def fused():
+            be.amp_reset(c, ids, kind, mids, times, None, None, root, dof_pos, dof_vel, pos, rot, vel, ang, True, True, dt, hist,
+                         L.RESET_HAS_MOTION)
+
+        idl = ids.long()
+        cur, past = torch.zeros(n_ids, 1, F, device=dev), torch.zeros(n_ids * (S - 1), 1, F, device=dev)
+        mids_h = mids.view(-1, 1).expand(n_ids, S - 1).reshape(-1).contiguous()
+        steps = -dt * (torch.arange(0, S - 1, device=dev) + 1)
+
+        def composed():
+            rp, rq, dp, rv, rw, dv, _ = be.motion_state(c, mids, times)
+            root[idl] = torch.cat([rp, rq, rv, rw], -1)
+            dof_pos[idl] = dp
+            dof_vel[idl] = dv
+            be.build_amp_obs(pos[idl, 0], rot[idl, 0], vel[idl, 0], ang[idl, 0], dp, dv, pos[idl][:, kb].contiguous(), c['dof_offsets'],
+                             True, True, cur, shift=False)
+            st = be.motion_state(c, mids_h, (times.unsqueeze(-1) + steps).reshape(-1))
+            be.build_amp_obs(st[0], st[1], st[3], st[4], st[2], st[5], st[6], c['dof_offsets'], True, True, past, shift=False)
+            hist[idl, 0] = cur[:, 0]
+            hist[idl, 1:] = past.view(n_ids, S - 1, F)
+
+        composed()
+        want = (root.clone(), dof_pos.clone(), hist.clone())
+        hist.zero_()
+        fused()
+        torch.cuda.synchronize()
+        diff = max(float((a - b).abs().max()) for a, b in zip(want, (root, dof_pos, hist)))
+        prog = be.prog_create()
+        be.prog_begin(prog)
+        for _ in range(REP):
+            fused()
+        be.prog_end(prog)
+        us = events(lambda: be.prog_launch(prog), 400) / REP
+        be.prog_destroy(prog)
+        us_eager = events(fused, 200)
+        us_comp = events(composed, 100)
+        byt = n_ids * (S * F + 13 + 2 * D) * 4
+        print(json.dumps({'measurement': 'amp-reset motion rows', 'envs': N, 'n_ids': n_ids, 'history_slots': S, 'us_per_call': round(us, 2),
+                          'eager_us_per_call': round(us_eager, 1), 'composed_us_per_call': round(us_comp, 1),
+                          'ratio': round(us_comp / us, 1), 'max_abs_diff_to_composed': diff, 'bytes_written': byt,
+                          'how': f'HIP events around 400 replays of a launch program of {REP} calls (operands stay cache-resident); eager: '
+                          '200 calls from Python; composed: motion_state x2, build_amp_obs x2 and the torch indexed writes, eager, 100 calls',
+                          'device': torch.cuda.get_device_name(0)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--updates', type=int, default=4)
@@ -255,6 +341,8 @@ def main():
                           'precision': 'bf16', 'hipgraph': False}), flush=True)
     if not args.only or 'env-tensors' in args.only.split(','):
         env_tensors_case()
+    if not args.only or 'amp-reset' in args.only.split(','):
+        amp_reset_case()
     if not args.only or 'ampobs' in args.only.split(','):
         # N2: observation production for 4096 envs (one frame + history push) and 5120 demo samples (512 x 10 steps)
         from ase_amd.backend import HipBackend
