@@ -252,6 +252,34 @@ class HipBackend:
                                               ia(clips['key_body_ids']), K, *[_ptr(o) for o in out], self._stream()), "motion_state")
         return out
 
+    def clip_frames(self, rotation, root_translation, root_velocity, root_angular_velocity, local_translation, parent_indices,
+                    clip_first, clip_num_frames, clip_fps, frame_clip, dof_body_ids, dof_offsets, out=None):
+        """The frame arrays of motion_state from the raw contents of clip files (MotionLib._load_motions +
+        _compute_motion_dof_vels, utils/motion_lib.py:75-80,174-236,279-294; operands: see ase_hip_clip_frames), one launch.
+        rotation [T, B, 4], root_translation / root_velocity / root_angular_velocity [T, 3], clip_fps [C]: f64;
+        local_translation [C, B, 3]: f32; clip_first, clip_num_frames [C], frame_clip [T]: int32; parent_indices, dof_body_ids,
+        dof_offsets: python lists.  Returns (gts, grs, lrs, grvs, gravs, dvs), f32 (out: the six tensors to write instead)."""
+        T, B = rotation.shape[0], rotation.shape[1]
+        Cn, J, D = clip_first.numel(), len(dof_body_ids), int(dof_offsets[-1])
+        for t, dt, shape in ((rotation, torch.float64, (T, B, 4)), (root_translation, torch.float64, (T, 3)),
+                             (root_velocity, torch.float64, (T, 3)), (root_angular_velocity, torch.float64, (T, 3)),
+                             (local_translation, torch.float32, (Cn, B, 3)), (clip_first, torch.int32, (Cn,)),
+                             (clip_num_frames, torch.int32, (Cn,)), (clip_fps, torch.float64, (Cn,)), (frame_clip, torch.int32, (T,))):
+            assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device.type == self.device.type, \
+                f"clip_frames: operand {tuple(t.shape)} {t.dtype}, expected {shape} {dt} on {self.device}"
+        assert len(parent_indices) == B and len(dof_offsets) == J + 1
+        f = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        if out is None:
+            out = (f(T, B, 3), f(T, B, 4), f(T, B, 4), f(T, 3), f(T, 3), f(T, D))
+        for o, shape in zip(out, ((T, B, 3), (T, B, 4), (T, B, 4), (T, 3), (T, 3), (T, D))):
+            assert o.dtype == torch.float32 and tuple(o.shape) == shape and o.is_contiguous() and o.device.type == self.device.type
+        ia = lambda xs: (C.c_int32 * len(xs))(*[int(x) for x in xs])
+        L.check(self.lib.ase_hip_clip_frames(_ptr(rotation), _ptr(root_translation), _ptr(root_velocity), _ptr(root_angular_velocity),
+                                             _ptr(local_translation), ia(parent_indices), B, _ptr(clip_first), _ptr(clip_num_frames),
+                                             _ptr(clip_fps), _ptr(frame_clip), Cn, T, ia(dof_body_ids), ia(dof_offsets), J,
+                                             *[_ptr(o) for o in out], self._stream()), "clip_frames")
+        return tuple(out)
+
     # ------------------------------------------------------------------ environment side (N5)
     @staticmethod
     def _f32c(*ts):

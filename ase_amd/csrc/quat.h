@@ -43,4 +43,33 @@ __device__ __forceinline__ Q4 heading_quat(const Q4& q) { return from_angle_axis
 // the inverse heading rotation: takes world vectors into the character's heading frame
 __device__ __forceinline__ Q4 heading_quat_inv(const Q4& q) { return from_angle_axis(-heading(q), V3{0.f, 0.f, 1.f}); }
 
+// ---- f64, the clip loader (motion_load.hip): poselib/core/rotation3d.py term by term, left to right.  These are separate
+// functions, not overloads of the f32 ones above: the loader's products follow poselib's term order, the observation side
+// isaacgym's.
+struct V3d { double x, y, z; };
+struct Q4d { double x, y, z, w; };
+
+// quat_mul (rotation3d.py:8-20)
+__device__ __forceinline__ Q4d quat_mul(const Q4d& a, const Q4d& b) {
+    const double w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
+    const double x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
+    const double y = a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z;
+    const double z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
+    return Q4d{x, y, z, w};
+}
+__device__ __forceinline__ Q4d quat_conj(const Q4d& q) { return Q4d{-q.x, -q.y, -q.z, q.w}; }
+// quat_normalize = quat_unit(quat_pos(q)) (rotation3d.py:24-49,88-93): the whole quaternion changes sign when w < 0,
+// then every component is divided by max(norm, 1e-9)
+__device__ __forceinline__ Q4d quat_normalize(Q4d q) {
+    if (q.w < 0.0) q = Q4d{-q.x, -q.y, -q.z, -q.w};
+    const double n = fmax(sqrt(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-9);
+    return Q4d{q.x / n, q.y / n, q.z / n, q.w / n};
+}
+__device__ __forceinline__ Q4d quat_mul_norm(const Q4d& a, const Q4d& b) { return quat_normalize(quat_mul(a, b)); }
+// quat_rotate (rotation3d.py:201-206): the imaginary part of r (v, 0) conj(r), both products written out in full
+__device__ __forceinline__ V3d quat_rotate(const Q4d& r, const V3d& v) {
+    const Q4d p = quat_mul(quat_mul(r, Q4d{v.x, v.y, v.z, 0.0}), quat_conj(r));
+    return V3d{p.x, p.y, p.z};
+}
+
 }  // namespace

@@ -1,21 +1,128 @@
-"""Demo-side AMP-observation production on the device: the sampling / state interface of the reference's
-``MotionLib`` (utils/motion_lib.py:100-172 under /root/reference/ase) and ``HumanoidAMP.fetch_amp_obs_demo`` /
-``build_amp_obs_demo`` (env/tasks/humanoid_amp.py:63-105) over clip arrays resident in HBM.
+"""Motion clips on the device: the reference's ``MotionLib`` (utils/motion_lib.py) - loader, sampling and
+state interface - and ``HumanoidAMP.fetch_amp_obs_demo`` / ``build_amp_obs_demo`` (env/tasks/humanoid_amp.py:63-105) over
+clip arrays resident in HBM.
 
-The clip arrays (per-frame global translations / rotations, local rotations, root velocities, dof velocities of all clips
-concatenated, plus per-clip length / frame count / dt / first frame) are what the reference's loader
-(``MotionLib._load_motions``: poselib ``SkeletonMotion.from_file`` + ``_compute_motion_dof_vels``) leaves in
-``ml.gts, ml.grs, ml.lrs, ml.grvs, ml.gravs, ml.dvs`` - the loader stays reference code (it runs once, on the host);
-``DeviceMotionLib.from_reference`` takes such an object, ``from_arrays`` the arrays themselves.  Everything per sample -
-frame blend, slerp of the root and every local rotation, exponential-map dof positions, key-body interpolation, then the
-140-float observation frame (root height, tangent-normal root rotation, local velocities, dof observations, key bodies) -
-runs in two HIP kernels (``ase_hip_motion_state``, ``ase_hip_build_amp_obs``); there is no host fallback.
+Loading (``DeviceMotionLib.from_file``): the host READS the files - a dataset ``.yaml`` or one ``.npy`` clip, poselib's
+``SkeletonMotion`` dictionaries, with numpy / yaml only - checks them, concatenates the raw f64 arrays of all clips and
+uploads them once; it does no arithmetic on frames.  One HIP launch (``ase_hip_clip_frames``) then computes what
+``MotionLib._load_motions`` leaves in ``ml.gts, ml.grs, ml.lrs, ml.grvs, ml.gravs, ml.dvs``: the forward-kinematics chain of
+every frame (global rotation / translation of every body) and the joint velocities from consecutive frames, in f64 as poselib
+does, stored f32.  ``from_reference`` takes a loaded reference ``MotionLib`` instead, ``from_arrays`` the arrays themselves.
+
+Sampling: everything per sample - frame blend, slerp of the root and every local rotation, exponential-map dof positions,
+key-body interpolation, then the 140-float observation frame (root height, tangent-normal root rotation, local velocities,
+dof observations, key bodies) - runs in two HIP kernels (``ase_hip_motion_state``, ``ase_hip_build_amp_obs``).
+
+There is no host fallback for either.  Not here: FBX / MJCF import, retargeting, clips that store global rotations.
 """
+import os
+
+import numpy as np
 import torch
 
 
+def fetch_motion_files(motion_file):
+    """MotionLib._fetch_motion_files (utils/motion_lib.py:238-261) -> (files, weights): a ``.yaml`` lists ``motions: [{file,
+    weight}]`` with files relative to its own directory; anything else is one clip of weight 1.  The path is taken as given."""
+    motion_file = os.fspath(motion_file)
+    if os.path.splitext(motion_file)[1] != '.yaml':
+        return [motion_file], [1.0]
+    import yaml
+    with open(motion_file, 'r') as f:
+        cfg = yaml.load(f, Loader=yaml.SafeLoader)
+    if not isinstance(cfg, dict) or not cfg.get('motions'):
+        raise ValueError(f"{motion_file}: no 'motions' list")
+    dir_name = os.path.dirname(motion_file)
+    files, weights = [], []
+    for entry in cfg['motions']:
+        w = float(entry['weight'])
+        if not w >= 0:
+            raise ValueError(f"{motion_file}: weight {entry['weight']!r} of {entry['file']} is negative")
+        files.append(os.path.join(dir_name, entry['file']))
+        weights.append(w)
+    if not sum(weights) > 0:
+        raise ValueError(f'{motion_file}: all weights are zero')
+    return files, weights
+
+
+def read_clip(path):
+    """One ``SkeletonMotion`` file as poselib writes it (``numpy.save`` of an ordered dict, arrays under ``['arr']``) -> dict of
+    numpy arrays: rotation [F, J, 4], root_translation [F, 3], global_velocity / global_angular_velocity [F, J, 3] (f64),
+    parent_indices [J], local_translation [J, 3] (f32), fps.  Nothing is computed.
+
+    The format is a PICKLE (``allow_pickle=True``): loading a file runs code it names.  Read trusted files only."""
+    try:
+        d = np.load(path, allow_pickle=True).item()
+    except (ValueError, AttributeError, EOFError) as e:
+        raise ValueError(f'{path}: not a SkeletonMotion file ({e})') from e
+    if not isinstance(d, dict) or d.get('__name__') != 'SkeletonMotion':
+        name = d.get('__name__') if isinstance(d, dict) else type(d).__name__
+        raise ValueError(f"{path}: holds a {name!r}, not a 'SkeletonMotion'")
+    if not d['is_local']:
+        raise ValueError(f'{path}: the clip stores global rotations (is_local == False), which are not loaded; '
+                         're-save it in local form (rotations relative to the parent body, is_local == True)')
+    tree = d['skeleton_tree']
+    arr = lambda x, dt: np.ascontiguousarray(np.asarray(x['arr']), dtype=dt)
+    c = {'rotation': arr(d['rotation'], np.float64), 'root_translation': arr(d['root_translation'], np.float64),
+         'global_velocity': arr(d['global_velocity'], np.float64),
+         'global_angular_velocity': arr(d['global_angular_velocity'], np.float64),
+         'parent_indices': arr(tree['parent_indices'], np.int64), 'local_translation': arr(tree['local_translation'], np.float32),
+         'node_names': list(tree['node_names']), 'fps': float(d['fps'])}
+    F, J = c['rotation'].shape[:2]
+    if c['rotation'].shape != (F, J, 4) or c['root_translation'].shape != (F, 3) or c['global_velocity'].shape != (F, J, 3) or \
+            c['global_angular_velocity'].shape != (F, J, 3) or c['parent_indices'].shape != (J,) or c['local_translation'].shape != (J, 3):
+        raise ValueError(f'{path}: array shapes do not describe {F} frames of {J} bodies')
+    if F < 2:
+        raise ValueError(f'{path}: {F} frame(s); a clip has 2 or more')
+    if not c['fps'] > 0:
+        raise ValueError(f"{path}: fps {d['fps']!r}")
+    for b, p in enumerate(c['parent_indices']):
+        if not (-1 <= p < b) or (b == 0 and p != -1):
+            raise ValueError(f'{path}: parent {p} of body {b} does not precede it')
+    return c
+
+
+def read_motion_files(motion_file, dof_body_ids, dof_offsets, key_body_ids):
+    """The host side of ``DeviceMotionLib.from_file``: file list, per-clip tables as ``MotionLib._load_motions``
+    (utils/motion_lib.py:192-228,82-85) and the raw arrays of all clips concatenated along the frame axis.  Raises
+    ``ValueError`` naming the file for everything the loader refuses."""
+    files, weights = fetch_motion_files(motion_file)
+    dof_body_ids, dof_offsets, key_body_ids = [int(x) for x in dof_body_ids], [int(x) for x in dof_offsets], [int(x) for x in key_body_ids]
+    if len(dof_offsets) != len(dof_body_ids) + 1 or dof_offsets[0] != 0:
+        raise ValueError(f'{motion_file}: dof_offsets {dof_offsets} do not describe the {len(dof_body_ids)} joints of dof_body_ids')
+    for j in range(len(dof_body_ids)):
+        if dof_offsets[j + 1] - dof_offsets[j] not in (1, 3):
+            raise ValueError(f'{motion_file}: joint {j} has {dof_offsets[j + 1] - dof_offsets[j]} dofs (1 or 3 supported)')
+    clips = [read_clip(f) for f in files]
+    first = clips[0]
+    J = first['rotation'].shape[1]
+    for name, ids in (('dof_body_id', dof_body_ids), ('key_body_id', key_body_ids)):
+        for b in ids:
+            if not 0 <= b < J:
+                raise ValueError(f'{files[0]}: {name} {b} outside the skeleton of {J} bodies')
+    for f, c in zip(files, clips):
+        if c['rotation'].shape[1] != J or not np.array_equal(c['parent_indices'], first['parent_indices']):
+            raise ValueError(f"{f}: skeleton ({c['rotation'].shape[1]} bodies, parents {c['parent_indices'].tolist()}) differs from "
+                             f'that of {files[0]}')
+    num_frames = [c['rotation'].shape[0] for c in clips]
+    fps = [c['fps'] for c in clips]
+    starts = np.concatenate([[0], np.cumsum(num_frames)[:-1]])
+    cat = lambda k: np.concatenate([c[k] for c in clips], axis=0)
+    return {'motion_files': files, 'weights': weights, 'fps': fps, 'num_frames': num_frames,
+            'dt': [1.0 / x for x in fps],                                                  # motion_lib.py:193
+            'lengths': [1.0 / x * (n - 1) for x, n in zip(fps, num_frames)],               # motion_lib.py:196
+            'length_starts': starts.tolist(),
+            'frame_clip': np.repeat(np.arange(len(clips), dtype=np.int32), num_frames),
+            'parent_indices': first['parent_indices'].tolist(),
+            'rotation': cat('rotation'), 'root_translation': cat('root_translation'),
+            'root_velocity': np.ascontiguousarray(cat('global_velocity')[:, 0]),           # motion_lib.py:78-79: body 0
+            'root_angular_velocity': np.ascontiguousarray(cat('global_angular_velocity')[:, 0]),
+            'local_translation': np.stack([c['local_translation'] for c in clips]),        # each clip's own skeleton offsets
+            'dof_body_ids': dof_body_ids, 'dof_offsets': dof_offsets, 'key_body_ids': key_body_ids}
+
+
 class DeviceMotionLib:
-    """``MotionLib`` (utils/motion_lib.py:57) without the loader: same method names, argument meaning and return order."""
+    """``MotionLib`` (utils/motion_lib.py:57): same method names, argument meaning and return order."""
 
     CLIP_F32 = ('gts', 'grs', 'lrs', 'grvs', 'gravs', 'dvs', 'lengths', 'dt')
     CLIP_I32 = ('num_frames', 'length_starts')
@@ -33,6 +140,29 @@ class DeviceMotionLib:
     @classmethod
     def from_arrays(cls, clips, backend, device, **kw):
         return cls(clips, backend, device, **kw)
+
+    @classmethod
+    def from_file(cls, motion_file, dof_body_ids, dof_offsets, key_body_ids, backend, device, **kw):
+        """``MotionLib(motion_file, dof_body_ids, dof_offsets, key_body_ids, device)`` (utils/motion_lib.py:65-89): a dataset
+        ``.yaml`` or one ``.npy`` clip.  The files are read on the host (``read_motion_files``; pickles - trusted files only),
+        their raw f64 arrays uploaded once, and every frame array computed by ONE launch of ``backend.clip_frames``.
+        ``motion_files`` and ``fps`` are kept as attributes.  Raises ``ValueError`` naming the file for what is refused."""
+        h = read_motion_files(motion_file, dof_body_ids, dof_offsets, key_body_ids)
+        dev = torch.device(device)
+        up = lambda k, dt: torch.as_tensor(h[k], dtype=dt).contiguous().to(dev)
+        out = backend.clip_frames(up('rotation', torch.float64), up('root_translation', torch.float64),
+                                  up('root_velocity', torch.float64), up('root_angular_velocity', torch.float64),
+                                  up('local_translation', torch.float32), h['parent_indices'], up('length_starts', torch.int32),
+                                  up('num_frames', torch.int32), up('fps', torch.float64), up('frame_clip', torch.int32),
+                                  h['dof_body_ids'], h['dof_offsets'])
+        clips = dict(zip(('gts', 'grs', 'lrs', 'grvs', 'gravs', 'dvs'), out))
+        clips.update(lengths=torch.tensor(h['lengths'], dtype=torch.float32), dt=torch.tensor(h['dt'], dtype=torch.float32),
+                     num_frames=torch.tensor(h['num_frames']), length_starts=torch.tensor(h['length_starts']),
+                     dof_body_ids=h['dof_body_ids'], dof_offsets=h['dof_offsets'], key_body_ids=h['key_body_ids'])
+        kw.setdefault('weights', h['weights'])
+        ml = cls(clips, backend, dev, **kw)
+        ml.motion_files, ml.fps = h['motion_files'], torch.tensor(h['fps'], dtype=torch.float32)
+        return ml
 
     @classmethod
     def from_reference(cls, ml, backend, device, dof_body_ids, dof_offsets, key_body_ids, **kw):

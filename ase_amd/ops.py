@@ -45,6 +45,10 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
             key_body_ids, local_root_obs, root_height_obs, env_dt) -> ()      (root_states, dof_pos, dof_vel, hist written in place)
                                                       HumanoidAMP._reset_actors + _init_amp_obs, the get-up task's fall episodes
                                                       (env/tasks/humanoid_amp.py:141-246, humanoid_amp_getup.py:109-129)
+  clip_frames(rotation, root_translation, root_velocity, root_angular_velocity, local_translation, clip_first, clip_num_frames,
+              clip_fps, frame_clip, parent_indices, dof_body_ids, dof_offsets) -> (gts, grs, lrs, grvs, gravs, dvs)
+                                                      the clip loader: forward kinematics and joint velocities of every frame of
+                                                      every clip (MotionLib._load_motions, utils/motion_lib.py:174-236,279-294)
 
 ``HipLinear`` is an ``nn.Linear`` whose forward is ``linear_act`` (optionally with a fused ReLU / tanh).
 """
@@ -631,3 +635,40 @@ def amp_reset(root_states: torch.Tensor, dof_pos: torch.Tensor, dof_vel: torch.T
                          dof_vel, _f32c(body_pos, 'body_pos'), _f32c(body_rot, 'body_rot'), _f32c(body_vel, 'body_vel'),
                          _f32c(body_ang_vel, 'body_ang_vel'), local_root_obs, root_height_obs, env_dt, hist,
                          (L.RESET_HAS_TABLE if has_table else 0) | (L.RESET_HAS_MOTION if has_motion else 0))
+
+
+@torch.library.custom_op('ase_hip::clip_frames', mutates_args=(), device_types='cuda')
+def clip_frames(rotation: torch.Tensor, root_translation: torch.Tensor, root_velocity: torch.Tensor,
+                root_angular_velocity: torch.Tensor, local_translation: torch.Tensor, clip_first: torch.Tensor,
+                clip_num_frames: torch.Tensor, clip_fps: torch.Tensor, frame_clip: torch.Tensor, parent_indices: list[int],
+                dof_body_ids: list[int], dof_offsets: list[int]
+                ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The clip loader in one launch (operands: see ase_hip_clip_frames): the raw f64 contents of SkeletonMotion clips,
+    concatenated -> (gts [T, B, 3], grs, lrs [T, B, 4], grvs, gravs [T, 3], dvs [T, D]), f32."""
+    _check(rotation.dim() == 3 and rotation.shape[2] == 4, 'clip_frames: rotation [T, B, 4]')
+    T, B = rotation.shape[0], rotation.shape[1]
+    for t, name, dt in ((rotation, 'rotation', torch.float64), (root_translation, 'root_translation', torch.float64),
+                        (root_velocity, 'root_velocity', torch.float64), (root_angular_velocity, 'root_angular_velocity', torch.float64),
+                        (local_translation, 'local_translation', torch.float32), (clip_first, 'clip_first', torch.int32),
+                        (clip_num_frames, 'clip_num_frames', torch.int32), (clip_fps, 'clip_fps', torch.float64),
+                        (frame_clip, 'frame_clip', torch.int32)):
+        _check(t.dtype == dt and t.is_cuda, f'clip_frames: {name} is a {dt} device tensor')
+    Cn = clip_first.numel()
+    _check(all(t.shape == (T, 3) for t in (root_translation, root_velocity, root_angular_velocity)),
+           'clip_frames: root_translation / root_velocity / root_angular_velocity [T, 3]')
+    _check(local_translation.shape == (Cn, B, 3) and clip_num_frames.shape == clip_fps.shape == clip_first.shape == (Cn,) and
+           frame_clip.shape == (T,), 'clip_frames: local_translation [C, B, 3], clip_first / clip_num_frames / clip_fps [C], frame_clip [T]')
+    _check(len(parent_indices) == B and len(dof_offsets) == len(dof_body_ids) + 1 and len(dof_body_ids) >= 1,
+           'clip_frames: parent_indices [B], dof_body_ids [J], dof_offsets [J + 1]')
+    return _backend().clip_frames(rotation.contiguous(), root_translation.contiguous(), root_velocity.contiguous(),
+                                  root_angular_velocity.contiguous(), local_translation.contiguous(), parent_indices,
+                                  clip_first.contiguous(), clip_num_frames.contiguous(), clip_fps.contiguous(),
+                                  frame_clip.contiguous(), dof_body_ids, dof_offsets)
+
+
+@clip_frames.register_fake
+def _(rotation, root_translation, root_velocity, root_angular_velocity, local_translation, clip_first, clip_num_frames, clip_fps,
+      frame_clip, parent_indices, dof_body_ids, dof_offsets):
+    T, B = rotation.shape[0], rotation.shape[1]
+    f = lambda *shape: rotation.new_empty(*shape, dtype=torch.float32)
+    return f(T, B, 3), f(T, B, 4), f(T, B, 4), f(T, 3), f(T, 3), f(T, dof_offsets[-1])

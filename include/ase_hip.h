@@ -597,6 +597,34 @@ int ase_hip_amp_reset(const float* gts, const float* grs, const float* lrs, cons
                       int n_envs, int local_root_obs, int root_height_obs, float env_dt, float* hist, int n_steps,
                       void* stream);
 
+/* Motion-clip loader: the frame arrays of ase_hip_motion_state / ase_hip_amp_reset from the raw contents of
+ * SkeletonMotion clip files, every frame of every clip in ONE launch.  Inputs (DEVICE, all clips concatenated along the
+ * frame axis, n_frames rows): rotation [n_frames, n_bodies, 4] f64, the stored LOCAL rotations xyzw; root_translation,
+ * root_velocity, root_angular_velocity [n_frames, 3] f64 (body 0 of the stored global velocities); local_translation
+ * [n_clips, n_bodies, 3] f32, each clip's skeleton offsets; per clip clip_first (its first row), clip_num_frames (>= 2),
+ * clip_fps (f64); frame_clip [n_frames]: the clip of a row.  parent_indices [n_bodies], dof_body_ids [n_joints],
+ * dof_offsets [n_joints + 1]: HOST int32 arrays; body 0 is a root, a parent precedes its child, a joint has 1 or 3 dofs.
+ * Outputs (f32): gts [n_frames, n_bodies, 3], grs / lrs [n_frames, n_bodies, 4], grvs / gravs [n_frames, 3], dvs
+ * [n_frames, D = dof_offsets[n_joints]].
+ * Arithmetic: f64, operation by operation as poselib, rounded to f32 at the store.  grs / gts: a root's transform is its
+ * local one (stored rotation; body 0's translation is root_translation rounded to f32 first, as poselib's f32
+ * local_translation tensor does), a child's is transform_mul(global[parent], local[child]) with the rotation
+ * re-normalised (sign flipped when w < 0, divided by max(norm, 1e-9)).  dvs: for frame f < F - 1 of a clip,
+ * d = quat_mul_norm(conj(l[f]), l[f + 1]), angle = acos(clamp(2 d.w^2 - 1)), velocity = d.xyz / max(|d.xyz|, 1e-9) *
+ * angle / (1.0 / fps); a 3-dof joint takes the vector, a 1-dof joint its y component; the last frame repeats the one
+ * before; frames of different clips never pair.  lrs, grvs, gravs: the stored values cast.  Rows whose frame_clip lies
+ * outside [0, n_clips) are skipped; n_bodies, n_joints <= 32.
+ * Replaces: MotionLib._load_motions / _compute_motion_dof_vels / _local_rotation_to_dof_vel and the concatenation of
+ *   MotionLib.__init__ (utils/motion_lib.py:75-80,174-236,279-294,326-355); SkeletonState.global_transformation /
+ *   local_translation (poselib/skeleton/skeleton3d.py:403-424,495-510); quat_mul, quat_normalize, quat_rotate,
+ *   quat_angle_axis, transform_mul (poselib/core/rotation3d.py:8-49,88-93,201-206,226-235,318-327). */
+int ase_hip_clip_frames(const double* rotation, const double* root_translation, const double* root_velocity,
+                        const double* root_angular_velocity, const float* local_translation,
+                        const int32_t* parent_indices, int n_bodies, const int32_t* clip_first,
+                        const int32_t* clip_num_frames, const double* clip_fps, const int32_t* frame_clip, int n_clips,
+                        int n_frames, const int32_t* dof_body_ids, const int32_t* dof_offsets, int n_joints, float* gts,
+                        float* grs, float* lrs, float* grvs, float* gravs, float* dvs, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Launch programs: record a sequence of the calls above ONCE (nothing is launched while recording), replay it with 4-5 us
  * of host work per launch on the same HIP streams - the optimisation step as one call, with OUR branch -> stream mapping
