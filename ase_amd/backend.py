@@ -36,6 +36,7 @@ def _code(dtype):
 
 class HipBackend:
     name = "hip"
+    nt_fused_epilogue = True     # gemm_nt(seed=, twin=, sq=): UpdateEngine's engine_opts gp_fuse needs it
 
     def __init__(self, device=None, x3=False):
         # x3: f32-stored GEMM operands are multiplied as three 16-bit MFMAs on a hi/lo split - True: bf16 parts (ASE_F32X3, any
@@ -128,8 +129,14 @@ class HipBackend:
 
     # ------------------------------------------------------------------ GEMMs
     def gemm_nt(self, A, B, Cm, M, N, K, bias=None, aux=None, aux_mode=L.AUX_NONE, colsum=None, colsum_n=0,
-                act=L.ACT_NONE, alpha=1.0, aux_split=0, aux_delta=0, mask_out=None, x3_exps=None, alpha_dev=None):
-        """alpha_dev (all `*_dev` / `dyn` arguments of this class): a scale RECORD on the device, f32 {factor, overflow count} - an
+                act=L.ACT_NONE, alpha=1.0, aux_split=0, aux_delta=0, mask_out=None, x3_exps=None, alpha_dev=None,
+                seed=None, twin=None, sq=None, store=True):
+        """seed / twin / sq (nt_fused_epilogue; ASE_F32H3 launches only - ase_hip_gemm_nt_ex): duties of the launch's epilogue that
+        were launches of their own.  seed = (w f32[n], scale): store scale * w[col] * [act(z) > 0] instead of the activation (gp_seed);
+        twin = a 16-bit tensor that receives the stored values once more (the conversion of gather_multi; store=False with a twin: Cm
+        names the shape only and is NOT written);
+        sq = (acc, slot, scale, dyn): acc[slot] += scale * dyn's factor * sum of the stored values' squares (sqnorm).
+        alpha_dev (all `*_dev` / `dyn` arguments of this class): a scale RECORD on the device, f32 {factor, overflow count} - an
         entry of the dynamic loss scale's table (UpdateEngine.scale_tab: S, 1 / S, 1 / S^2, 1).  The launch multiplies its scale by the
         factor when it RUNS and adds to the count when an element it stored overflowed (include/ase_hip.h, ABI 7)."""
         dt = self._gemm_code(A.dtype, x3_exps)
@@ -140,6 +147,21 @@ class HipBackend:
             assert aux is None or aux.dtype == A.dtype
         # twin output: the ReLU bit matrix (int32 words), or for the smooth activations the pre-activation in the storage type
         assert mask_out is None or mask_out.dtype == (A.dtype if act >= L.ACT_SILU else torch.int32)
+        if seed is not None or twin is not None or sq is not None:
+            assert (dt & 0xFF) == L.F32H3, "seed / twin / sq belong to the half-split f32 launches (x3 = 'f16', x3_exps)"
+            assert Cm.dtype == torch.float32 and (store or twin is not None)
+            sw, ss = seed if seed is not None else (None, 0.0)
+            acc, slot, sscale, dyn = sq if sq is not None else (None, 0, 0.0, None)
+            assert acc is None or acc.dtype == torch.float64
+            L.check(self.lib.ase_hip_gemm_nt_ex(_ptr(A), _ld(A), _ptr(B), _ld(B), _ptr(Cm) if store else None, _ld(Cm), _ptr(bias), _ptr(aux),
+                                                _ld(aux), int(aux_split), int(aux_delta), _ptr(colsum), int(colsum_n),
+                                                _ptr(mask_out), _ld(mask_out), M, N, K, act, aux_mode, 0,
+                                                float(alpha), _ptr(alpha_dev), dt,
+                                                _ptr(sw), 0 if sw is None else sw.numel(), float(ss),
+                                                _ptr(twin), _ld(twin), 0 if twin is None else _code(twin.dtype),
+                                                None if acc is None else C.c_void_p(acc.data_ptr() + 8 * int(slot)), float(sscale),
+                                                _ptr(dyn), self._stream()), "gemm_nt_ex")
+            return
         out_f32 = int(Cm.dtype == torch.float32 and A.dtype != torch.float32)
         L.check(self.lib.ase_hip_gemm_nt(_ptr(A), _ld(A), _ptr(B), _ld(B), _ptr(Cm), _ld(Cm), _ptr(bias), _ptr(aux),
                                          _ld(aux), int(aux_split), int(aux_delta), _ptr(colsum), int(colsum_n),
@@ -217,6 +239,13 @@ class HipBackend:
         """Fused optimizer step + shadow refresh of every layer (desc: device int64 [n, 24], see ase_hip.h)."""
         L.check(self.lib.ase_hip_apply_multi(_ptr(desc), desc.shape[0], _ptr(opt_state), _ptr(acc), _code(dtype),
                                              self._stream()), "apply_multi")
+
+    def apply_multi_split(self, desc, items, dtype, opt_state, acc, desc2, items2):
+        """apply_multi that also writes a second, half-split (ASE_F32H3) shadow pair per layer (desc2: device int64 [n, 8] rows
+        {Ws3, ldws3, Wts3, ldwts3, exponent, 0, 0, 0}, zeros = none; see ase_hip.h; items2: the same tensors as (Ws3, Wts3, exponent) or None per row, kept alive by the caller)."""
+        assert desc2.shape == (desc.shape[0], 8) and desc2.is_contiguous()
+        L.check(self.lib.ase_hip_apply_multi_v2(_ptr(desc), desc.shape[0], _ptr(desc2), _ptr(opt_state), _ptr(acc), _code(dtype),
+                                                self._stream()), "apply_multi_v2")
 
     def gather_multi(self, desc, items, idx, remap, M):
         L.check(self.lib.ase_hip_gather_multi(_ptr(desc), desc.shape[0], _ptr(idx), remap[0], remap[1], M,
@@ -424,6 +453,19 @@ class HipBackend:
         lo = (C.c_int64 * n)(*[int(t.stride(0)) for t in outs])
         L.check(self.lib.ase_hip_rms_normalize_multi(srcs, lds, idxs, rh, rn, mp, sp, op, lo, n, D, M, _code(outs[0].dtype),
                                                      self._stream()), "rms_normalize_multi")
+
+    def rms_normalize_multi_twin(self, streams, D, M, means, stds, outs, outs32):
+        """rms_normalize_multi with an f32 twin per stream (outs32: a tensor or None each): the normalised value before rounding."""
+        n, srcs, lds, idxs, rh, rn = self._stream_arrays(streams)
+        mp = (C.c_void_p * n)(*[t.data_ptr() for t in means])
+        sp = (C.c_void_p * n)(*[t.data_ptr() for t in stds])
+        op = (C.c_void_p * n)(*[t.data_ptr() for t in outs])
+        lo = (C.c_int64 * n)(*[int(t.stride(0)) for t in outs])
+        assert all(t is None or t.dtype == torch.float32 for t in outs32)
+        op32 = (C.c_void_p * n)(*[None if t is None else t.data_ptr() for t in outs32])
+        lo32 = (C.c_int64 * n)(*[0 if t is None else int(t.stride(0)) for t in outs32])
+        L.check(self.lib.ase_hip_rms_normalize_multi_v2(srcs, lds, idxs, rh, rn, mp, sp, op, lo, op32, lo32, n, D, M,
+                                                        _code(outs[0].dtype), self._stream()), "rms_normalize_multi_v2")
 
     def rms_finalize(self, state, D, sums, count, n_streams, mean_out, std_out):
         counts = (C.c_int32 * max(n_streams, 1))(*([int(count)] * max(n_streams, 1)))

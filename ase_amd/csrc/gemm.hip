@@ -48,19 +48,40 @@ extern "C" int ase_hip_gemm_nt_kernel_id(int M, int N, int K, int dtype) {
     return nt_choice(M, N, K, ase_elem_size(dtype), ase_elem_size(dtype) == 2);
 }
 
-extern "C" int ase_hip_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
-                               const float* bias, const void* aux, int64_t ldaux, int aux_split, int aux_delta,
-                               float* colsum, int colsum_n, void* mask_out, int64_t ldmask, int M, int N, int K, int act,
-                               int aux_mode, int out_f32, float alpha, float* alpha_dev, int dtype_word, void* stream) {
+namespace {
+
+// fused duties of the f32h_t epilogue (ase_hip_gemm_nt_ex), all absent in ase_hip_gemm_nt
+struct NTFused {
+    const float* seed_w = nullptr; int seed_n = 0; float seed_scale = 0.f;
+    void* twin = nullptr; int64_t ldtwin = 0; int twin_dtype = 0;
+    double* sq_acc = nullptr; double sq_scale = 0.0; const float* sq_dyn = nullptr;
+    bool any() const { return seed_w || twin || sq_acc; }
+};
+
+int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                 const float* bias, const void* aux, int64_t ldaux, int aux_split, int aux_delta,
+                 float* colsum, int colsum_n, void* mask_out, int64_t ldmask, int M, int N, int K, int act,
+                 int aux_mode, int out_f32, float alpha, float* alpha_dev, int dtype_word, const NTFused& fu, void* stream) {
     const int dtype = dtype_word & 0xFF, ea = (dtype_word >> 8) & 0xFF, eb = (dtype_word >> 16) & 0xFF;
     const int es = ase_elem_size(dtype);
     ASE_CHECK_ARG(dtype == ASE_F32 || dtype == ASE_BF16 || dtype == ASE_F32X3 || dtype == ASE_F16 || dtype == ASE_F32H3,
                   "gemm_nt: bad dtype %d", dtype);
     ASE_CHECK_ARG(ea >= 0 && ea <= 24 && eb >= 0 && eb <= 24 && (dtype == ASE_F32H3 || (ea | eb) == 0),
                   "gemm_nt: operand scale exponents (bits 8-15 / 16-23 of dtype) are 0..24 and belong to ASE_F32H3 only");
-    ASE_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0, "gemm_nt: null/empty operand (M=%d N=%d K=%d)", M, N, K);
+    ASE_CHECK_ARG(A && B && (C || fu.twin) && M > 0 && N > 0 && K > 0, "gemm_nt: null/empty operand (M=%d N=%d K=%d)", M, N, K);
+    if (fu.any()) {
+        ASE_CHECK_ARG(dtype == ASE_F32H3 && colsum == nullptr && act <= ASE_ACT_RELU &&
+                          (aux_mode == ASE_AUX_NONE || aux_mode == ASE_AUX_RELU_BITS),
+                      "gemm_nt_ex: seed / twin / sum of squares belong to ASE_F32H3 launches without column sums, with no activation or "
+                      "ReLU and no mask operand or a bit matrix");
+        ASE_CHECK_ARG(fu.seed_w == nullptr || (fu.seed_n >= 0 && fu.seed_n <= N), "gemm_nt_ex: seed_n=%d outside [0, N]", fu.seed_n);
+        ASE_CHECK_ARG(fu.twin == nullptr || ((fu.twin_dtype == ASE_F16 || fu.twin_dtype == ASE_BF16) && fu.ldtwin >= N &&
+                                             ((uintptr_t)fu.twin % 8) == 0 && (fu.ldtwin * 2) % 8 == 0),
+                      "gemm_nt_ex: the twin is f16 / bf16, 8-byte aligned, ldtwin >= N in whole 8-byte steps");
+        ASE_CHECK_ARG(fu.sq_acc == nullptr || ((uintptr_t)fu.sq_acc % 8) == 0, "gemm_nt_ex: misaligned sq_acc");
+    }
     ASE_CHECK_ARG((K * es) % 64 == 0, "gemm_nt: K=%d is not a multiple of %d elements", K, 64 / es);
-    ASE_CHECK_ARG(lda >= K && ldb >= K && ldc >= N, "gemm_nt: leading dimension too small");
+    ASE_CHECK_ARG(lda >= K && ldb >= K && (ldc >= N || C == nullptr), "gemm_nt: leading dimension too small");
     ASE_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0 && (lda * es) % 16 == 0 && (ldb * es) % 16 == 0,
                   "gemm_nt: A/B must be 16-byte aligned with 16-byte row pitch");
     ASE_CHECK_ARG(aux_mode == ASE_AUX_NONE || aux != nullptr, "gemm_nt: aux_mode %d without aux", aux_mode);
@@ -89,6 +110,9 @@ extern "C" int ase_hip_gemm_nt(const void* A, int64_t lda, const void* B, int64_
     p.prof = nullptr;
     p.prof_clk = 0;
     p.sa = 1.f;
+    p.seed_w = fu.seed_w; p.seed_n = fu.seed_n; p.seed_scale = fu.seed_scale;
+    p.twin = (char*)fu.twin; p.ldtwin = fu.ldtwin * 2; p.twin_dtype = fu.twin_dtype;
+    p.sq_acc = fu.sq_acc; p.sq_scale = fu.sq_scale; p.sq_dyn = fu.sq_dyn;
     if (dtype == ASE_BF16) return dispatch_nt_bf16(p, (hipStream_t)stream);
     if (dtype == ASE_F16) return dispatch_nt_f16(p, (hipStream_t)stream);
     if (dtype == ASE_F32X3) return dispatch_nt_x3(p, (hipStream_t)stream);
@@ -100,3 +124,26 @@ extern "C" int ase_hip_gemm_nt(const void* A, int64_t lda, const void* B, int64_
     return dispatch_nt_f32(p, (hipStream_t)stream);
 }
 
+}  // namespace
+
+extern "C" int ase_hip_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                               const float* bias, const void* aux, int64_t ldaux, int aux_split, int aux_delta,
+                               float* colsum, int colsum_n, void* mask_out, int64_t ldmask, int M, int N, int K, int act,
+                               int aux_mode, int out_f32, float alpha, float* alpha_dev, int dtype_word, void* stream) {
+    return gemm_nt_impl(A, lda, B, ldb, C, ldc, bias, aux, ldaux, aux_split, aux_delta, colsum, colsum_n, mask_out, ldmask, M, N, K,
+                        act, aux_mode, out_f32, alpha, alpha_dev, dtype_word, NTFused{}, stream);
+}
+
+extern "C" int ase_hip_gemm_nt_ex(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                                  const float* bias, const void* aux, int64_t ldaux, int aux_split, int aux_delta,
+                                  float* colsum, int colsum_n, void* mask_out, int64_t ldmask, int M, int N, int K, int act,
+                                  int aux_mode, int out_f32, float alpha, float* alpha_dev, int dtype_word,
+                                  const float* seed_w, int seed_n, float seed_scale, void* twin, int64_t ldtwin, int twin_dtype,
+                                  double* sq_acc, double sq_scale, const float* sq_dyn, void* stream) {
+    NTFused fu;
+    fu.seed_w = seed_w; fu.seed_n = seed_n; fu.seed_scale = seed_scale;
+    fu.twin = twin; fu.ldtwin = ldtwin; fu.twin_dtype = twin_dtype;
+    fu.sq_acc = sq_acc; fu.sq_scale = sq_scale; fu.sq_dyn = sq_dyn;
+    return gemm_nt_impl(A, lda, B, ldb, C, ldc, bias, aux, ldaux, aux_split, aux_delta, colsum, colsum_n, mask_out, ldmask, M, N, K,
+                        act, aux_mode, out_f32, alpha, alpha_dev, dtype_word, fu, stream);
+}

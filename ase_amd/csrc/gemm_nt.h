@@ -48,6 +48,12 @@ struct NTParams {
     int tiles_m, tiles_n;
     unsigned long long* prof;       // debug: per-workgroup phase timestamps (ase_hip_debug_nt_profile), else null
     int prof_clk;                   // debug: stamps 1 and 2 (main loop) in shader clocks instead of the 100 MHz clock
+    // ---- fused duties of the f32h_t epilogue (ase_hip_gemm_nt_ex; the FUSE instantiations of gemm_nt_kernel read them, nobody else) ----
+    const float* seed_w; int seed_n; float seed_scale;   // nullable: C[m, n] = seed_scale * seed_w[n] * (act(z) > 0 ? 1 : 0) instead of
+                                                         // the activation (ase_hip_gp_seed's product; columns >= seed_n: 0)
+    char* twin; int64_t ldtwin; int twin_dtype;          // nullable: the stored value once more, from_f32<f16 / bf16> (ldtwin in bytes);
+                                                         // with a twin C may be null (no f32 store)
+    double* sq_acc; double sq_scale; const float* sq_dyn;   // nullable: *sq_acc += sq_scale * sq_dyn[0] * sum of the stored values' squares
 };
 
 

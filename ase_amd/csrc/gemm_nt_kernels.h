@@ -233,10 +233,14 @@ __device__ __forceinline__ void nt_aux_load(const NTParams& p, int ch, int lane,
 }
 
 // PRE: chunk 0 of the mask operand was loaded by the caller (before its main loop) into pre[]
-template <typename T, int FM, int FN, int FMC, int FNC, int AUXK, bool PRE = false>
-__device__ __forceinline__ void nt_epilogue_impl(const NTParams& p, f32x16 (&acc)[FM][FN], float* slab, int lane,
-                                                 int mrow0, int ncol0,
-                                                 AuxReg<T, AUXK> (*pre)[(FMC * 32) / (64 / (FNC * 8))] = nullptr) {
+// FUSE (f32h_t storage, ase_hip_gemm_nt_ex): the duties that were launches of their own around the gradient penalty's value path -
+// the seed s w_logit[n] [h > 0] in place of the activation (ase_hip_gp_seed), a 16-bit twin of the stored value (the conversion launch,
+// ase_hip_gather_multi) and the sum of the stored values' squares (ase_hip_sqnorm; returned per lane, the kernel reduces it) - each by
+// the helper's own expression on the 4 columns the lane holds anyway.
+template <typename T, int FM, int FN, int FMC, int FNC, int AUXK, bool PRE = false, bool FUSE = false>
+__device__ __forceinline__ double nt_epilogue_impl(const NTParams& p, f32x16 (&acc)[FM][FN], float* slab, int lane,
+                                                   int mrow0, int ncol0,
+                                                   AuxReg<T, AUXK> (*pre)[(FMC * 32) / (64 / (FNC * 8))] = nullptr) {
     constexpr int WCOLS = FNC * 32, WROWS = FMC * 32;
     const int col_in = lane & 31, row_hi = (lane >> 5) * 4;
     constexpr int ELPR = WCOLS / 4;                // lanes per row (4 columns each)
@@ -247,6 +251,7 @@ __device__ __forceinline__ void nt_epilogue_impl(const NTParams& p, f32x16 (&acc
     const int c4 = lane % ELPR, rsub = lane / ELPR;
     AuxReg<T, AUXK> areg[AHEAD ? 2 : 1][NIT];
     bool bad = false;                              // an element this lane stored overflowed (scale records, common.h)
+    double sq = 0.0;                               // FUSE: this lane's share of the sum of squares
 
     auto load_aux = [&](int ch, AuxReg<T, AUXK> (&dst)[NIT]) {
         nt_aux_load<T, FM, FN, FMC, FNC, AUXK>(p, ch, lane, mrow0, ncol0, dst);
@@ -285,6 +290,13 @@ __device__ __forceinline__ void nt_epilogue_impl(const NTParams& p, f32x16 (&acc
             }
         }
         float cs[4] = {0.f, 0.f, 0.f, 0.f};
+        f32x4 seed = {0.f, 0.f, 0.f, 0.f};             // FUSE: seed_scale * seed_w of the lane's 4 columns
+        if constexpr (FUSE) {
+            if (p.seed_w && n0 < p.N) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) seed[q] = p.seed_scale * (n0 + q < p.seed_n ? p.seed_w[n0 + q] : 0.f);
+            }
+        }
         if (n0 < p.N) {                                // N is a multiple of 4 (checked on the host)
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
@@ -324,7 +336,36 @@ __device__ __forceinline__ void nt_epilogue_impl(const NTParams& p, f32x16 (&acc
                         else v[q] = v[q] * act_grad(p.aux_mode >> 8, a);          // ASE_AUX_PREACT | (activation << 8)
                     }
                 }
-                if (p.out_f32 || sizeof(T) == 4) {
+                if constexpr (FUSE) {
+                    f32x4 sv = v;                       // the stored value; v stays the activation (mask_out below)
+                    if (p.seed_w) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) sv[q] = seed[q] * (v[q] > 0.f ? 1.f : 0.f);
+                    }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) bad |= ovf_hit1(sv[q]);
+                    if (p.C) *reinterpret_cast<f32x4*>(p.C + (int64_t)m * p.ldc + (int64_t)n0 * 4) = sv;
+                    if (p.twin) {
+                        char* t = p.twin + (int64_t)m * p.ldtwin + (int64_t)n0 * 2;
+                        if (p.twin_dtype == ASE_F16) {
+                            f16x4 o;
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) o[q] = from_f32<f16_t>(sv[q]);
+                            *reinterpret_cast<f16x4*>(t) = o;
+                        } else {
+                            bf16x4 o;
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) o[q] = from_f32<bf16_t>(sv[q]);
+                            *reinterpret_cast<bf16x4*>(t) = o;
+                        }
+                    }
+                    if (p.sq_acc) {                     // as sqnorm_kernel<float, 4>: f32 over the 4 columns (no contraction), then f64
+                        float s = 0.f;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) s = __fadd_rn(s, __fmul_rn(sv[q], sv[q]));
+                        sq += (double)s;
+                    }
+                } else if (p.out_f32 || sizeof(T) == 4) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) bad |= ovf_hit1(v[q]);
                     *reinterpret_cast<f32x4*>(p.C + (int64_t)m * p.ldc + (int64_t)n0 * 4) = v;
@@ -366,14 +407,16 @@ __device__ __forceinline__ void nt_epilogue_impl(const NTParams& p, f32x16 (&acc
         }
     }
     ovf_report(p.alpha_dev, bad);
+    return sq;
 }
 
-template <typename T, int FM, int FN, int FMC, int FNC>
-__device__ __forceinline__ void nt_epilogue(const NTParams& p, f32x16 (&acc)[FM][FN], float* slab, int lane, int mrow0,
-                                            int ncol0) {
-    if (p.aux_mode == ASE_AUX_NONE) nt_epilogue_impl<T, FM, FN, FMC, FNC, 0>(p, acc, slab, lane, mrow0, ncol0);
-    else if (p.aux_mode == ASE_AUX_RELU_BITS) nt_epilogue_impl<T, FM, FN, FMC, FNC, 2>(p, acc, slab, lane, mrow0, ncol0);
-    else nt_epilogue_impl<T, FM, FN, FMC, FNC, 1>(p, acc, slab, lane, mrow0, ncol0);
+template <typename T, int FM, int FN, int FMC, int FNC, bool FUSE = false>
+__device__ __forceinline__ double nt_epilogue(const NTParams& p, f32x16 (&acc)[FM][FN], float* slab, int lane, int mrow0,
+                                              int ncol0) {
+    if (p.aux_mode == ASE_AUX_NONE) return nt_epilogue_impl<T, FM, FN, FMC, FNC, 0, false, FUSE>(p, acc, slab, lane, mrow0, ncol0);
+    if (p.aux_mode == ASE_AUX_RELU_BITS) return nt_epilogue_impl<T, FM, FN, FMC, FNC, 2, false, FUSE>(p, acc, slab, lane, mrow0, ncol0);
+    if constexpr (FUSE) return 0.0;                // (the host admits no other mask operand beside the fused duties)
+    else return nt_epilogue_impl<T, FM, FN, FMC, FNC, 1>(p, acc, slab, lane, mrow0, ncol0);
 }
 
 // ---- row-per-lane epilogue of the lock-step kernels (bf16, swapped MFMA operands): the general FM x FN form of
@@ -428,7 +471,8 @@ __device__ __forceinline__ void nt_epilogue_rows(const NTParams& p, f32x16 (&acc
 
 // WPE = minimum waves per SIMD the register allocation must leave room for (k workgroups of T threads per CU <=> k T / 256)
 // SW (bf16): swapped MFMA operands + row-per-lane epilogue (16-byte stores from registers, no LDS slab)
-template <typename T, int WGM, int WGN, int FM, int FN, int RB, int S, int WPE = 1, bool SW = false>
+// FUSE: the epilogue's fused duties (nt_epilogue_impl), an instantiation of its own so that every other launch keeps its registers
+template <typename T, int WGM, int WGN, int FM, int FN, int RB, int S, int WPE = 1, bool SW = false, bool FUSE = false>
 __global__ __launch_bounds__(WGM * WGN * 64, WPE) void gemm_nt_kernel(NTParams p) {
     constexpr int BM = WGM * FM * 32, BN = WGN * FN * 32;
     constexpr int BK = RB / (int)sizeof(T);
@@ -534,10 +578,26 @@ __global__ __launch_bounds__(WGM * WGN * 64, WPE) void gemm_nt_kernel(NTParams p
 
     constexpr int FNC = (FN > 2) ? 2 : FN;
     float* slab = reinterpret_cast<float*>(smem) + wid * (FM * 32 * FNC * 32);
-    nt_epilogue<T, FM, FN, FM, FNC>(p, acc, slab, lane, bm0 + wm * FM * 32, bn0 + wn * FN * 32);
+    const double sq = nt_epilogue<T, FM, FN, FM, FNC, FUSE>(p, acc, slab, lane, bm0 + wm * FM * 32, bn0 + wn * FN * 32);
+    if constexpr (FUSE) {
+        if (p.sq_acc) {                                // one f64 atomic per workgroup, as ase_hip_sqnorm (block_sum)
+            const double w = wave_sum(sq);
+            __syncthreads();                           // every wave is done with its slab
+            double* red = reinterpret_cast<double*>(smem);
+            if (lane == 0) red[wid] = w;
+            __syncthreads();
+            if (tid == 0) {
+                double t = 0.0;
+                for (int i = 0; i < WGM * WGN; ++i) t += red[i];
+                double scale = p.sq_scale;
+                if (p.sq_dyn) scale *= (double)*p.sq_dyn;
+                atomic_add_f64(p.sq_acc, t * scale);
+            }
+        }
+    }
 }
 
-template <typename T, int WGM, int WGN, int FM, int FN, int RB, int S, int WPE = 1, bool SW = false>
+template <typename T, int WGM, int WGN, int FM, int FN, int RB, int S, int WPE = 1, bool SW = false, bool FUSE = false>
 int launch_nt(const NTParams& p0, hipStream_t stream) {
     constexpr int BM = WGM * FM * 32, BN = WGN * FN * 32;
     constexpr int ring = S * (BM + BN) * RB;
@@ -545,7 +605,7 @@ int launch_nt(const NTParams& p0, hipStream_t stream) {
     constexpr int lds = ring > slab ? ring : slab;
     static_assert(lds <= 160 * 1024, "LDS budget");
     static bool attr_done = false;
-    auto kern = gemm_nt_kernel<T, WGM, WGN, FM, FN, RB, S, WPE, SW>;
+    auto kern = gemm_nt_kernel<T, WGM, WGN, FM, FN, RB, S, WPE, SW, FUSE>;
     if (!attr_done) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -891,6 +951,22 @@ template <typename T> int dispatch_nt(const NTParams& p, hipStream_t s) {
     const bool fits32 = (int64_t)p.M * p.lda < (int64_t)0x7FFFFFFF && (int64_t)p.N * p.ldb < (int64_t)0x7FFFFFFF;
     int choice = nt_choice(p.M, p.N, p.K, (int)sizeof(T), sizeof(T) == 2);
     if ((choice == 2 || choice == 6) && !fits32) choice = 3;
+    if constexpr (std::is_same<T, f32h_t>::value) {
+        if (p.seed_w || p.twin || p.sq_acc) {        // the fused epilogue duties: the same tiles, their own instantiations
+            switch (choice) {
+                case 0: return launch_nt<T, 2, 2, 1, 1, 64, 4, 1, false, true>(p, s);
+                case 2: case 3: case 6:
+                    if (k128) return launch_nt<T, 4, 2, 2, 4, 128, 2, 1, false, true>(p, s);
+                    return launch_nt<T, 4, 2, 2, 4, 64, 4, 1, false, true>(p, s);
+                case 4: return launch_nt<T, 2, 2, 1, 2, 128, 2, 2, false, true>(p, s);
+                case 5: return launch_nt<T, 2, 2, 1, 1, 128, 4, 2, false, true>(p, s);
+                default:
+                    // (two workgroups per CU asked for: the plain instantiation gets there by itself, 252 registers)
+                    if (k128) return launch_nt<T, 2, 2, 2, 2, 128, 2, 2, false, true>(p, s);
+                    return launch_nt<T, 2, 2, 2, 2, 64, 4, 2, false, true>(p, s);
+            }
+        }
+    }
     switch (choice) {
         case 0: return launch_nt<T, 2, 2, 1, 1, 64, 4>(p, s);
         case 6:

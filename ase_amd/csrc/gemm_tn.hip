@@ -796,16 +796,7 @@ __global__ void refresh_shadow_kernel(const float* __restrict__ W, int n_real, i
 // f32h_t shadows (ASE_F32H3): W * 2^e split into half hi / lo parts, packed [8 hi | 8 lo] per group of 8 consecutive elements of
 // the contracted (contiguous) dimension - k for W_s, n for W_s^T; 4 bytes per element, leading dimensions in 4-byte units like the
 // f32 shadows they replace.  (See Mma<f32h_t> in gemm_nt_kernels.h.)
-__device__ __forceinline__ void store_split(char* row, int col, float v, float scale) {
-    // (saturating, like every other conversion into half storage: a weight beyond +-32 at the scale 2^11 must not become inf and
-    //  then NaN in every product - advisor, round 5; once per weight and step, free.  The A operand's split stays a plain cast in
-    //  the kernel's loop: its inputs are bounded by construction - observations clamped to +-5 at 2^12, see _gp_value)
-    const float s = __builtin_amdgcn_fmed3f(v * scale, -65504.f, 65504.f);
-    const f16_t hi = (f16_t)s, lo = (f16_t)(s - (float)hi);
-    char* g = row + (col >> 3) * 32 + (col & 7) * 2;
-    *reinterpret_cast<f16_t*>(g) = hi;
-    *reinterpret_cast<f16_t*>(g + 16) = lo;
-}
+// (store_split / split_half: common.h - ase_hip_apply_multi_v2 writes the same shadows from its own tiles)
 __global__ void refresh_shadow_split_kernel(const float* __restrict__ W, int n_real, int k_real, char* __restrict__ Ws, int64_t ldws,
                                             char* __restrict__ Wts, int64_t ldwts, int split_src, int gap, float scale) {
     __shared__ float tile[32][33];

@@ -1,5 +1,6 @@
 // Optimizer step (torch.optim.Adam semantics) and the weight-only gradient terms.
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -82,12 +83,18 @@ template <> __device__ __forceinline__ void store_shadow4<float>(float* p, const
     *reinterpret_cast<f32x4*>(p) = f32x4{w[0], w[1], w[2], w[3]};
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void apply_multi_kernel(const int64_t* __restrict__ desc, const double* __restrict__ st,
-                                                          double* __restrict__ acc) {
+// (8 waves per SIMD = 64 registers: the small kernels run in what the matrix kernels leave free; 62 without the second shadow pair)
+// SPLIT: the instantiation that may write the second shadow pair (desc2); the plain one is the kernel it always was
+template <typename T, bool SPLIT>
+__global__ __launch_bounds__(256, SPLIT ? 8 : 1) void apply_multi_kernel(const int64_t* __restrict__ desc, const double* __restrict__ st,
+                                                          double* __restrict__ acc, const int64_t* __restrict__ desc2) {
     __shared__ float tile[32][129];          // scalar path: [32][33] of it
     __shared__ double red[16];
     const int64_t* d = desc + 24 * blockIdx.y;
+    // second shadow pair of the layer (desc2, nullable; a row of zeros: none): the packed half-split shadows of W * 2^eb
+    // (ASE_F32H3, as ase_hip_refresh_shadow writes them) from the same tile - pitches in BYTES from here on
+    // (its fields are read where they are used, behind the optimizer arithmetic: held across it they cost 5 registers of 64)
+    const int64_t* e3 = (SPLIT && desc2) ? desc2 + 8 * blockIdx.y : nullptr;
     float* W = reinterpret_cast<float*>(d[0]);
     const int n_real = (int)d[1], k_real = (int)d[2];
     T* Ws = reinterpret_cast<T*>(d[3]);
@@ -187,6 +194,53 @@ __global__ __launch_bounds__(256) void apply_multi_kernel(const int64_t* __restr
                 } else {
                     for (int q = 0; q < 16 && nb + q < n_real; ++q) dst[q] = from_f32<T>(tile[16 * half + q][kk]);
                 }
+                if (SPLIT && e3 && e3[2]) {
+                    const float sc3 = ldexpf(1.f, (int)e3[4]);
+                    char* row = reinterpret_cast<char*>(e3[2]) + (int64_t)((k < split_src) ? k : k + gap) * (e3[3] * 4);
+                    if (nb + 16 <= n_real) {             // 4 x (4 hi halves, 4 lo halves): half a group of 8 each
+#pragma unroll
+                        for (int q = 0; q < 16; q += 4) {
+                            f16x4 h, l;
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) {
+                                f16_t hh, ll;
+                                split_half(tile[16 * half + q + c][kk], sc3, hh, ll);
+                                h[c] = hh; l[c] = ll;
+                            }
+                            char* g = row + ((nb + q) >> 3) * 32 + ((nb + q) & 7) * 2;
+                            *reinterpret_cast<f16x4*>(g) = h;
+                            *reinterpret_cast<f16x4*>(g + 16) = l;
+                        }
+                    } else {
+                        for (int q = 0; q < 16 && nb + q < n_real; ++q) store_split(row, nb + q, tile[16 * half + q][kk], sc3);
+                    }
+                }
+            }
+            if (SPLIT && e3 && e3[0]) {       // W_s's second shadow from the tile too (not beside the optimizer's registers): 16 k of one row per thread
+                const float sc3 = ldexpf(1.f, (int)e3[4]);
+                char* Ws3 = reinterpret_cast<char*>(e3[0]);
+                const int64_t ld3 = e3[1] * 4;
+                const int rr = threadIdx.x >> 3, kc = (threadIdx.x & 7) * 16;
+                const int n = n0 + rr;
+                if (n < n_real) {
+#pragma unroll
+                    for (int u = 0; u < 16; u += 4) {
+                        const int k4 = k0 + kc + u;
+                        if (k4 < k_real) {               // (k_real % 4 == 0; kd % 4 == 0: half a group of 8)
+                            const int kd = (k4 < split_src) ? k4 : k4 + gap;
+                            f16x4 h, l;
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) {
+                                f16_t hh, ll;
+                                split_half(tile[rr][kc + u + c], sc3, hh, ll);
+                                h[c] = hh; l[c] = ll;
+                            }
+                            char* g = Ws3 + (int64_t)n * ld3 + (kd >> 3) * 32 + (kd & 7) * 2;
+                            *reinterpret_cast<f16x4*>(g) = h;
+                            *reinterpret_cast<f16x4*>(g + 16) = l;
+                        }
+                    }
+                }
             }
         }
     } else
@@ -212,6 +266,8 @@ __global__ __launch_bounds__(256) void apply_multi_kernel(const int64_t* __restr
                     W[o] = w; mW[o] = mi; vW[o] = vi;
                 }
                 Ws[(int64_t)n * ldws + ((k < split_src) ? k : k + gap)] = from_f32<T>(w);
+                if (SPLIT && e3 && e3[0])
+                    store_split(reinterpret_cast<char*>(e3[0]) + (int64_t)n * (e3[1] * 4), (k < split_src) ? k : k + gap, w, ldexpf(1.f, (int)e3[4]));
             }
             tile[ty + 8 * i][tx] = w;
         }
@@ -219,8 +275,12 @@ __global__ __launch_bounds__(256) void apply_multi_kernel(const int64_t* __restr
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int k = k0 + ty + 8 * i, n = n0 + tx;
-            if (k < k_real && n < n_real)
+            if (k < k_real && n < n_real) {
                 Wts[(int64_t)((k < split_src) ? k : k + gap) * ldwts + n] = from_f32<T>(tile[tx][ty + 8 * i]);
+                if (SPLIT && e3 && e3[2])
+                    store_split(reinterpret_cast<char*>(e3[2]) + (int64_t)((k < split_src) ? k : k + gap) * (e3[3] * 4), n, tile[tx][ty + 8 * i],
+                                ldexpf(1.f, (int)e3[4]));
+            }
         }
     }
     if (adam && slot_a >= 0) {
@@ -280,17 +340,37 @@ extern "C" int ase_hip_axpy(float* g, const float* w, int64_t n, float c, void* 
     return ASE_OK;
 }
 
-extern "C" int ase_hip_apply_multi(const int64_t* desc, int n_layers, const double* opt_state, double* acc, int dtype,
-                                   void* stream) {
+namespace {
+int apply_multi_impl(const int64_t* desc, int n_layers, const int64_t* desc2, const double* opt_state, double* acc, int dtype,
+                     void* stream) {
     ASE_CHECK_ARG(desc && n_layers > 0, "apply_multi: null/empty operand");
     ASE_CHECK_ARG(opt_state == nullptr || acc != nullptr, "apply_multi: optimizer step without the accumulator array");
+    // (f16 storage only: the bf16 instantiation needs 2 registers more than the 64 the small kernels are held to, and would spill)
+    ASE_CHECK_ARG(desc2 == nullptr || dtype == ASE_F16, "apply_multi_v2: the half-split shadow pair is built for ASE_F16 storage (dtype %d)",
+                  dtype);
     const dim3 grid(256, n_layers);
     const int rc = ase_dispatch_storage(dtype, [&](auto tag) {
         typedef typename decltype(tag)::type T;
-        ASE_LAUNCH(apply_multi_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, desc, opt_state, acc);
+        if constexpr (std::is_same<T, f16_t>::value) if (desc2) {
+            ASE_LAUNCH((apply_multi_kernel<T, true>), grid, dim3(256), 0, (hipStream_t)stream, desc, opt_state, acc, desc2);
+            return ASE_OK;
+        }
+        ASE_LAUNCH((apply_multi_kernel<T, false>), grid, dim3(256), 0, (hipStream_t)stream, desc, opt_state, acc, desc2);
         return ASE_OK;
     });
     ASE_CHECK_ARG(rc == ASE_OK, "apply_multi: bad dtype %d", dtype);
     ASE_CHECK_LAUNCH("apply_multi");
     return ASE_OK;
+}
+}  // namespace
+
+extern "C" int ase_hip_apply_multi(const int64_t* desc, int n_layers, const double* opt_state, double* acc, int dtype,
+                                   void* stream) {
+    return apply_multi_impl(desc, n_layers, nullptr, opt_state, acc, dtype, stream);
+}
+
+extern "C" int ase_hip_apply_multi_v2(const int64_t* desc, int n_layers, const int64_t* desc2, const double* opt_state, double* acc,
+                                      int dtype, void* stream) {
+    ASE_CHECK_ARG(desc2 != nullptr, "apply_multi_v2: null table of the second shadow pairs");
+    return apply_multi_impl(desc, n_layers, desc2, opt_state, acc, dtype, stream);
 }

@@ -73,6 +73,7 @@ struct RmsStreams {
     const float* src[4]; int64_t ld[4]; const int32_t* idx[4]; int rh[4], rn[4];
     double* sums[4];                       // moments
     const float* mean[4]; const float* stdv[4]; void* out[4]; int64_t ld_out[4];   // normalize
+    float* out32[4]; int64_t ld_out32[4];  // normalize: nullable f32 twin of a stream's output (the value before rounding)
 };
 
 __global__ __launch_bounds__(256) void rms_moments_multi_kernel(RmsStreams S, int D, int M, const double* __restrict__ state) {
@@ -129,6 +130,7 @@ __global__ __launch_bounds__(256) void rms_normalize_multi_kernel(RmsStreams S, 
     f32x4 y;
 #pragma unroll
     for (int c = 0; c < 4; ++c) y[c] = fminf(fmaxf((x[c] - mu[c]) / sd[c], -5.f), 5.f);
+    if (S.out32[s]) *reinterpret_cast<f32x4*>(S.out32[s] + (int64_t)r * S.ld_out32[s] + j) = y;
     if constexpr (sizeof(T) == 2) {
         typename V16<T>::x4 v;
 #pragma unroll
@@ -370,13 +372,16 @@ extern "C" int ase_hip_rms_moments_multi(const float* const* srcs, const int64_t
     return ASE_OK;
 }
 
-extern "C" int ase_hip_rms_normalize_multi(const float* const* srcs, const int64_t* ld_srcs, const int32_t* const* idxs,
-                                           const int* remap_h, const int* remap_n, const float* const* means,
-                                           const float* const* stds, void* const* outs, const int64_t* ld_outs, int n_streams,
-                                           int D, int M, int dtype, void* stream) {
+namespace {
+
+int rms_normalize_multi_impl(const float* const* srcs, const int64_t* ld_srcs, const int32_t* const* idxs,
+                             const int* remap_h, const int* remap_n, const float* const* means,
+                             const float* const* stds, void* const* outs, const int64_t* ld_outs, float* const* outs32,
+                             const int64_t* ld_outs32, int n_streams, int D, int M, int dtype, void* stream) {
     ASE_CHECK_ARG(srcs && ld_srcs && idxs && remap_h && remap_n && means && stds && outs && ld_outs && n_streams >= 1 &&
                       n_streams <= 4 && D > 0 && M > 0, "rms_normalize_multi: null/empty operand (1..4 streams)");
     ASE_CHECK_ARG(dtype == ASE_BF16 || dtype == ASE_F32 || dtype == ASE_F16, "rms_normalize_multi: bad dtype %d", dtype);
+    ASE_CHECK_ARG(outs32 == nullptr || ld_outs32 != nullptr, "rms_normalize_multi: f32 twins without their pitches");
     const int es = ase_elem_size(dtype);
     RmsStreams S = {};
     for (int s = 0; s < n_streams; ++s) {
@@ -386,6 +391,11 @@ extern "C" int ase_hip_rms_normalize_multi(const float* const* srcs, const int64
                       "rms_normalize_multi: stream %d needs 16-byte rows (D %% 4 == 0, aligned pointers / pitches)", s);
         S.src[s] = srcs[s]; S.ld[s] = ld_srcs[s]; S.idx[s] = idxs[s]; S.rh[s] = remap_h[s]; S.rn[s] = remap_n[s];
         S.mean[s] = means[s]; S.stdv[s] = stds[s]; S.out[s] = outs[s]; S.ld_out[s] = ld_outs[s];
+        if (outs32 && outs32[s]) {
+            ASE_CHECK_ARG(ld_outs32[s] >= D && ld_outs32[s] % 4 == 0 && ((uintptr_t)outs32[s] % 16) == 0,
+                          "rms_normalize_multi: stream %d: the f32 twin needs 16-byte rows of at least D elements", s);
+            S.out32[s] = outs32[s]; S.ld_out32[s] = ld_outs32[s];
+        }
     }
     const dim3 grid((D / 4 + 63) / 64, (M + 3) / 4, n_streams);
     ase_dispatch_storage(dtype, [&](auto tag) {
@@ -395,6 +405,25 @@ extern "C" int ase_hip_rms_normalize_multi(const float* const* srcs, const int64
     });
     ASE_CHECK_LAUNCH("rms_normalize_multi");
     return ASE_OK;
+}
+
+}  // namespace
+
+extern "C" int ase_hip_rms_normalize_multi(const float* const* srcs, const int64_t* ld_srcs, const int32_t* const* idxs,
+                                           const int* remap_h, const int* remap_n, const float* const* means,
+                                           const float* const* stds, void* const* outs, const int64_t* ld_outs, int n_streams,
+                                           int D, int M, int dtype, void* stream) {
+    return rms_normalize_multi_impl(srcs, ld_srcs, idxs, remap_h, remap_n, means, stds, outs, ld_outs, nullptr, nullptr, n_streams, D, M,
+                                    dtype, stream);
+}
+
+extern "C" int ase_hip_rms_normalize_multi_v2(const float* const* srcs, const int64_t* ld_srcs, const int32_t* const* idxs,
+                                              const int* remap_h, const int* remap_n, const float* const* means,
+                                              const float* const* stds, void* const* outs, const int64_t* ld_outs,
+                                              float* const* outs32, const int64_t* ld_outs32, int n_streams, int D, int M, int dtype,
+                                              void* stream) {
+    return rms_normalize_multi_impl(srcs, ld_srcs, idxs, remap_h, remap_n, means, stds, outs, ld_outs, outs32, ld_outs32, n_streams, D, M,
+                                    dtype, stream);
 }
 
 extern "C" int ase_hip_rms_finalize(double* state, int D, const double* sums, const int32_t* counts, int n_streams,

@@ -21,6 +21,7 @@ Data layout in HBM
     the epoch permutation (env-major flat index -> physical row) inside the gather/normalise
     kernels, so neither swap_and_flatten01 nor the dataset gather materialise anything.
 """
+import contextlib
 import math
 
 import torch
@@ -191,6 +192,18 @@ class UpdateEngine:
         #                   Measured SLOWER: 76.28 vs 75.61 ms (four interleaved repetitions, profiles/r06_schedule_options_ab.txt): off
         #   stream_offset   (measurement aid) throw-away streams taken from the pool in front of the branch streams: streams land on the
         #                   hardware queues in creation order, this shifts the engine's places
+        #   gp_fuse         gp_f32 = 'x3' with the f16 split: the helper launches around the value path's matrix launches ride in those
+        #                   launches' epilogues (backend capability nt_fused_epilogue, ase_hip_gemm_nt_ex) - the seed s w_logit [h > 0]
+        #                   out of the last forward launch (gp_seed: gone, g.H[-1] never stored), the 16-bit copies of the chain out of
+        #                   the launches that produce it (the conversion launch: gone, S s g_0 never stored in f32) and sum (S s g_0)^2
+        #                   out of the last chain launch (sqnorm: gone); the demo rows' f32 input comes out of the branch's
+        #                   normalise launch (rms_normalize_multi_twin: the value path's own normalise launch is gone, its fork moves
+        #                   behind that launch); the trunk's half-split shadows come out of the optimizer launch (apply_multi_split, f16
+        #                   storage: the three refresh launches per step are gone - refresh_shadows, in which every other route that
+        #                   changes the masters ends, writes them too).  The last chain launch moves from the value path into _gp_f32: it adds into the
+        #                   step's accumulators, which the un-chained head of the cross-step schedule must not touch.
+        #                   'auto' (default) = on where the backend has the capability; True / False force it (False, or a backend
+        #                   without the capability: the launch sequence of round 6, the A/B leg)
         #   gp_stream       gp_f32 modes: the penalty's value path (f32 / bf16x3 forward of the demo rows + chain: independent of
         #                   the loss rows until the conversion launch) on its own stream beside the discriminator branch.  Round 4's
         #                   A/B had it faster (with the bf16-split kernels of that round); on round 6's kernels it is SLOWER: f16gpx3
@@ -204,7 +217,7 @@ class UpdateEngine:
         o = dict(tn_grouped=True, tn_wg_side=64, tn_early=False, disc_early=True, short_prologue=True, style_early=False,
                  relu_bits=True, fused_apply=True, apply_wide=True, side_streams=2, gp_scale_split=True, xstep=True,
                  gp_stream='auto', style_side=0, style_wg=0, side_priority=None, prefetch=True, disc_after_style=False, gp_split='f16',
-                 stream_offset=0, gp_value_late=False)
+                 stream_offset=0, gp_value_late=False, gp_fuse='auto')
         unknown = set(cfg.get('engine_opts', {}) or {}) - set(o)
         assert not unknown, f"unknown engine_opts {sorted(unknown)}"
         o.update(cfg.get('engine_opts', {}) or {})
@@ -229,6 +242,14 @@ class UpdateEngine:
         self._xstep = bool(o['xstep']) and cfg.get('graph_capture') != 'hipgraph'
         gp_side = (self.dyn_scale or self.M < 8192) if o['gp_stream'] == 'auto' else bool(o['gp_stream'])      # (self.M: THIS rank's rows)
         self._gp_side = gp_side and cfg.get('graph_capture') != 'hipgraph'      # (a fork from a forked stream: same capture_end crash)
+        self._gp_fuse = bool(self.gp32 and getattr(backend, 'nt_fused_epilogue', False) and cfg.get('gp_f32') == 'x3'
+                             and getattr(backend, 'x3', None) is not None and o['gp_split'] == 'f16'
+                             and (o['gp_fuse'] == 'auto' or bool(o['gp_fuse'])))
+        # (gp_fuse: the value path's half-split shadows are kept current by the optimizer launch and refresh_shadows, see _gp_value)
+        # (it stays set where the split optimizer launch never runs - truncate_grads, the end-of-step forms of phase_apply: those end in
+        #  refresh_shadows(), which calls _gp_refresh)
+        self._gp_split = self._gp_fuse and hasattr(backend, 'apply_multi_split') and self._fused_apply and dtype == torch.float16
+        self._gp_x_done = False          # this step's normalise launch wrote the value path's f32 input (_disc_inputs)
         self._style_side = int(o['style_side'])
         self._disc_after_style = bool(o['disc_after_style'])
         self._disc_split = False
@@ -465,10 +486,13 @@ class UpdateEngine:
                 g.X = zt(AMB, self.disc[0].k_pad, f32)                                  # normalised demo rows
                 g.Ws = [zt(d.n_pad, d.k_pad, f32) for d in self.disc]                   # f32 shadows of the trunk
                 g.Wts = [zt(d.k_pad, d.n_pad, f32) for d in self.disc]
-                g.H = [zt(AMB, d.n_pad, f32) for d in self.disc]
+                # (gp_fuse: the last layer's activation is never stored - its launch writes the top of the chain - and S s g_0 exists in
+                #  16 bits only: a shape without memory for the launch's signature)
+                g.H = [None if (self._gp_fuse and d is self.disc[-1]) else zt(AMB, d.n_pad, f32) for d in self.disc]
                 g.bits = [torch.zeros(AMB, d.n_pad // 32, dtype=torch.int32, device=dev) for d in self.disc]
                 g.Gp = [zt(AMB, d.n_pad, f32) for d in self.disc]                       # s * g_l
-                g.G0 = zt(AMB, self.disc[0].k_pad, f32)                                 # S s * g_0
+                g.G0 = (torch.empty(AMB, self.disc[0].k_pad, dtype=f32, device='meta') if self._gp_fuse
+                        else zt(AMB, self.disc[0].k_pad, f32))                          # S s * g_0
                 g.cast = None                                                           # (conversion table, built on first use)
             if self.enc_chain:
                 self.He, self.dZe = chain_bufs(self.enc_chain, AMB)
@@ -558,6 +582,26 @@ class UpdateEngine:
             self._refresh_desc = torch.tensor(rows, dtype=torch.int64, device=self.dev)
             self._refresh_items = items
         self.be.refresh_shadow_multi(self._refresh_desc, self._refresh_items, self.dtype)
+        if self._gp_split:
+            self._gp_refresh()
+
+    def _gp_refresh(self):
+        """The value path's own shadows of the discriminator trunk from the f32 masters (gp_f32 = 'x3', half split: pre-split,
+        scaled by 2^11, [8 hi | 8 lo] halves per group of 8).  Without gp_fuse: every step, by the value path itself.  With it they
+        are current behind every route that changes the masters - the optimizer launch writes them (apply_multi_split) and
+        every other route ends in refresh_shadows, which calls this."""
+        g = self._gp32
+        half = self.cfg.get('gp_f32') == 'x3' and getattr(self.be, 'x3', None) is not None and self.engine_opts['gp_split'] == 'f16'
+        for l, d in enumerate(self.disc):
+            self.be.refresh_shadow(d.W[0], g.Ws[l], g.Wts[l], d.split_src, d.split_dst, **({'x3_exp': 11} if half else {}))
+
+    def _apply(self, opt_state, a=None, b=None):
+        """The fused optimizer + shadow launch over rows [a, b) of the table (all of it by default)."""
+        desc, items = self._apply_desc[a:b], self._apply_items[a:b]
+        if self._gp_split:
+            self.be.apply_multi_split(desc, items, self.dtype, opt_state, self.acc, self._apply_desc2[a:b], self._apply_items2[a:b])
+        else:
+            self.be.apply_multi(desc, items, self.dtype, opt_state, self.acc)
 
     def _build_apply_desc(self):
         """Pointer table of ase_hip_apply_multi: per weight matrix its parameter / gradient / Adam-moment slices, the
@@ -618,6 +662,17 @@ class UpdateEngine:
         assert n_cov == self.n_train, (n_cov, self.n_train)     # every trainable scalar belongs to exactly one layer part
         self._apply_desc = torch.tensor(rows, dtype=torch.int64, device=self.dev)
         self._apply_items = items
+        if self._gp_split:
+            # second shadow pair of the discriminator trunk's rows: the value path's half-split shadows (exponent 11, _gp_value)
+            g, rows2, items2 = self._gp32, [[0] * 8 for _ in rows], [None] * len(rows)
+            for l, d in enumerate(self.disc):
+                assert len(d.parts) == 1
+                i = [j for j, it in enumerate(items) if it[0].data_ptr() == d.W[0].data_ptr() and it[0].numel()]
+                assert len(i) == 1
+                rows2[i[0]] = [g.Ws[l].data_ptr(), g.Ws[l].stride(0), g.Wts[l].data_ptr(), g.Wts[l].stride(0), 11, 0, 0, 0]
+                items2[i[0]] = (g.Ws[l], g.Wts[l], 11)
+            self._apply_desc2 = torch.tensor(rows2, dtype=torch.int64, device=self.dev)
+            self._apply_items2 = items2
         # parameter buckets of the two branch groups: rows of the table + the range of the flat buffers they cover
         # (checkpoint order: actor, critic, value, mu | discriminator, logits, encoder - each group is contiguous)
 
@@ -1090,7 +1145,7 @@ class UpdateEngine:
                 if last:
                     self._dyn_apply()
             else:
-                self.be.apply_multi(self._apply_desc[a:b], self._apply_items[a:b], self.dtype, self.opt_state, self.acc)
+                self._apply(self.opt_state, a, b)
 
     def _disc_forward(self, amp_streams, ds=None):
         """Head of the discriminator (+ encoder) branch: AMP-observation moments -> running statistics -> normalised rows
@@ -1113,7 +1168,10 @@ class UpdateEngine:
             be.rms_finalize(self.amp_state, self.amp, self.amp_sums, amb_den, 3, self.amp_mean, self.amp_std)
         else:
             self._identity_stats(self.amp_mean, self.amp_std)
-        gp_fork = self._mark() if (self.gp32 and self._gp_side) else None
+        # (gp_fuse: the normalise launch below writes the value path's f32 input too - its fork is marked behind that launch)
+        x_twin = self._gp_fuse and hasattr(be, 'rms_normalize_multi_twin') and self.amp % 4 == 0 and \
+            all(src.stride(0) % 4 == 0 for src, _, _ in amp_streams)
+        gp_fork = self._mark() if (self.gp32 and self._gp_side and not x_twin) else None
         self._enc_z_ready = False
         if self.has_enc and ds is not None:
             # enc_latents = ase_latents[0:amp_minibatch] (learning/ase_agent.py:247): a row gather that needs nothing but the
@@ -1123,7 +1181,12 @@ class UpdateEngine:
             be.gather_rows(zsrc, self.z, sidx, srm, AMB, self.enc_z)
             self._enc_z_ready = True
         xd = [self.Xd[s * AMB:(s + 1) * AMB] for s in range(3)]
-        if self.amp % 4 == 0 and all(src.stride(0) % 4 == 0 for src, _, _ in amp_streams):
+        self._gp_x_done = x_twin
+        if x_twin:
+            be.rms_normalize_multi_twin(amp_streams, self.amp, AMB, [self.amp_mean[s] for s in range(3)],
+                                        [self.amp_std[s] for s in range(3)], xd, [None, None, self._gp32.X])
+            gp_fork = self._mark() if self._gp_side else None
+        elif self.amp % 4 == 0 and all(src.stride(0) % 4 == 0 for src, _, _ in amp_streams):
             be.rms_normalize_multi(amp_streams, self.amp, AMB, [self.amp_mean[s] for s in range(3)],
                                    [self.amp_std[s] for s in range(3)], xd)
         else:                          # rows that are not whole 16-byte chunks: one launch per stream
@@ -1368,7 +1431,7 @@ class UpdateEngine:
         if apply and self._fused_apply and not self.truncate and not self.dyn_scale:      # (dynamic scale + fused: step() took the inline form)
             # weight-only loss terms + their reported norms + Adam + shadow refresh of every layer: ONE launch
             self._build_apply_desc()
-            be.apply_multi(self._apply_desc, self._apply_items, self.dtype, self.opt_state, self.acc)
+            self._apply(self.opt_state)
         else:
             if self.has_disc:
                 # weight-only loss terms, added once after the gradient reduction
@@ -1473,7 +1536,7 @@ class UpdateEngine:
                 be.scaler_fold(self.scaler, self.scale_tab)       # the producers' reports -> one number, SUM over the ranks
                 self._ar(self.scaler[:1])
             be.scaler_step(self.scaler, self.opt_state, self.opt_eff, g, scale_tab=self.scale_tab)
-            be.apply_multi(self._apply_desc, self._apply_items, self.dtype, self.opt_eff, self.acc)
+            self._apply(self.opt_eff)
         self._join_branch(br)
 
     @property
@@ -1671,8 +1734,9 @@ class UpdateEngine:
         nl, S = len(self.disc), self.gs
         s = math.sqrt(gp_coef * 2.0 / self.AMBg)
         bits = L.AUX_RELU_BITS
-        src, sidx, srm = amp_streams[2]        # the demo stream once more, into the f32 input of the penalty path
-        be.rms_normalize(src, self.amp, sidx, srm, AMB, self.amp_mean[2], self.amp_std[2], [g.X])
+        if not self._gp_x_done:     # (gp_fuse: the branch's normalise launch wrote g.X as its f32 twin)
+            src, sidx, srm = amp_streams[2]        # the demo stream once more, into the f32 input of the penalty path
+            be.rms_normalize(src, self.amp, sidx, srm, AMB, self.amp_mean[2], self.amp_std[2], [g.X])
         # gp_f32 = 'x3': the six f32-storage launches multiply as three 16-bit MFMAs per product on hi / lo splits instead of the
         # exact-f32 MFMA (1/16 of the 16-bit rate): IEEE-half parts of power-of-two scaled operands (ASE_F32H3, unit roundoff
         # ~2^-22; round 4 used bf16 parts, ~2^-17, and the driver's run missed the 1e-4 bar on the penalty by 8 %).  Half's
@@ -1682,30 +1746,48 @@ class UpdateEngine:
         #   chain values s g_l       O(1e-3 .. 1e-1); saturation above 16       2^12
         #   weights                  O(1/sqrt(K)); saturation above 32          2^11
         # (engine_opts gp_split = 'bf16' keeps round 4's bf16 split - no range assumption at all - for the same-box A/B)
+        fuse = self._gp_fuse
+        with self._gp_mode() as ex:
+            # (half split: the shadows are written PRE-SPLIT - scaled, [8 hi | 8 lo] halves per group of 8 - once per step instead
+            #  of being split again by every row tile of the six launches; gp_fuse: by the optimizer launch, see _gp_refresh)
+            if not self._gp_split:
+                self._gp_refresh()
+            top = self.disc[-1]
+            x = g.X
+            for l, d in enumerate(self.disc):
+                if fuse and l == nl - 1:
+                    # gp_fuse: the last forward launch stores the seed s w_logit [h > 0] (f32 + its 16-bit copy) instead of h
+                    self._nt(x, g.Ws[l], g.Gp[-1], AMB, d.n_pad, d.k_pad, bias=d.bs, act=L.ACT_RELU, mask_out=g.bits[l],
+                             seed=(self.disc_head.W[0].view(-1), s), twin=self.Gp[-1], **ex(12 if l == 0 else 6))
+                    break
+                self._nt(x, g.Ws[l], g.H[l], AMB, d.n_pad, d.k_pad, bias=d.bs, act=L.ACT_RELU, mask_out=g.bits[l],
+                           **ex(12 if l == 0 else 6))
+                x = g.H[l]
+            if not fuse:
+                be.gp_seed(g.H[-1], self.disc_head.W[0].view(-1), g.Gp[-1], AMB, top.N, scale=s)
+            for l in range(nl - 1, 0, -1):
+                d = self.disc[l]
+                self._nt(g.Gp[l], g.Wts[l], g.Gp[l - 1], AMB, d.k_pad, d.n_pad, aux=g.bits[l - 1], aux_mode=bits,
+                         **({'twin': self.Gp[l - 1]} if fuse else {}), **ex(12))
+            if not fuse:      # (gp_fuse: _gp_f32 launches it - it adds to the step's accumulators)
+                d0 = self.disc[0]
+                self._nt(g.Gp[0], g.Wts[0], g.G0, AMB, d0.k_pad, d0.n_pad, alpha=S, alpha_dev=self._dS, **ex(12))     # S s * g_0
+
+    @contextlib.contextmanager
+    def _gp_mode(self):
+        """Multiplication mode of the value path's f32-storage launches (gp_f32 = 'x3': the backend's x3 switch for their duration);
+        yields ex(ea) -> the launch's operand exponents (half split) or nothing."""
+        be = self.be
         x3_prev = getattr(be, 'x3', None)
         mode = self.cfg.get('gp_f32')
         half = mode == 'x3' and x3_prev is not None and self.engine_opts['gp_split'] == 'f16'
         if mode == 'x3' and x3_prev is not None:
             be.x3 = 'f16' if half else True
-        ex = (lambda ea: {'x3_exps': (ea, 11)}) if half else (lambda ea: {})
-        for l, d in enumerate(self.disc):
-            # (half split: the shadows are written PRE-SPLIT - scaled, [8 hi | 8 lo] halves per group of 8 - once per step instead
-            #  of being split again by every row tile of the six launches)
-            be.refresh_shadow(d.W[0], g.Ws[l], g.Wts[l], d.split_src, d.split_dst, **({'x3_exp': 11} if half else {}))
-        x = g.X
-        for l, d in enumerate(self.disc):
-            self._nt(x, g.Ws[l], g.H[l], AMB, d.n_pad, d.k_pad, bias=d.bs, act=L.ACT_RELU, mask_out=g.bits[l],
-                       **ex(12 if l == 0 else 6))
-            x = g.H[l]
-        top = self.disc[-1]
-        be.gp_seed(g.H[-1], self.disc_head.W[0].view(-1), g.Gp[-1], AMB, top.N, scale=s)
-        for l in range(nl - 1, 0, -1):
-            d = self.disc[l]
-            self._nt(g.Gp[l], g.Wts[l], g.Gp[l - 1], AMB, d.k_pad, d.n_pad, aux=g.bits[l - 1], aux_mode=bits, **ex(12))
-        d0 = self.disc[0]
-        self._nt(g.Gp[0], g.Wts[0], g.G0, AMB, d0.k_pad, d0.n_pad, alpha=S, alpha_dev=self._dS, **ex(12))         # S s * g_0
-        if x3_prev is not None:
-            be.x3 = x3_prev
+        try:
+            yield (lambda ea: {'x3_exps': (ea, 11)}) if half else (lambda ea: {})
+        finally:
+            if x3_prev is not None:
+                be.x3 = x3_prev
 
     def _gp_f32(self, gp_coef):
         """The gradient penalty of the demo rows (learning/amp_agent.py:453-459) through an exact-f32 value path inside a
@@ -1730,6 +1812,20 @@ class UpdateEngine:
         if getattr(self, '_gp_value_pending', None) is not None:
             self._gp_value(*self._gp_value_pending)
             self._gp_value_pending = None
+        if self._gp_fuse:
+            # the chain's last launch: S s g_0 straight into the 16-bit row block (never stored in f32) + the sum of its squares;
+            # the 16-bit copies of s g_l were written by the launches that produced them (_gp_value)
+            with self._gp_mode() as ex:
+                self._nt(g.Gp[0], g.Wts[0], g.G0, AMB, d0.k_pad, d0.n_pad, alpha=S, alpha_dev=self._dS, twin=self.G0, store=False,
+                         sq=(self.acc, L.ACC_GP, 1.0 / (cg * S * S), self._dI2), **ex(12))
+        else:
+            self._gp_convert(cg)
+        self._gp_backward(s)
+
+    def _gp_convert(self, cg):
+        """|S s g_0|^2 and the conversion launch of a gp_f32 engine without gp_fuse."""
+        be, AMB, g = self.be, self.AMB, self._gp32
+        nl, S, d0 = len(self.disc), self.gs, self.disc[0]
         be.sqnorm(g.G0, AMB, d0.k_pad, self.acc, L.ACC_GP, scale=1.0 / (cg * S * S), dyn=self._dI2)
         # [dZ_l ; s g_l] and [X ; S s g_0]: the exact chain, rounded once, in the storage type
         if g.cast is None:
@@ -1738,6 +1834,13 @@ class UpdateEngine:
             rows = [[src.data_ptr(), src.stride(0), c, dst.data_ptr(), dst.stride(0), code] for src, c, dst in items]
             g.cast = (torch.tensor(rows, dtype=torch.int64, device=self.dev), items)
         be.gather_multi(g.cast[0], g.cast[1], None, (0, 0), AMB)
+
+    def _gp_backward(self, s):
+        """Second half of _gp_f32: the loss rows' data gradients and the penalty's backward through the exact masks."""
+        be, AMB, g = self.be, self.AMB, self._gp32
+        Rd, nl, S = 3 * AMB, len(self.disc), self.gs
+        bits = L.AUX_RELU_BITS
+        d0 = self.disc[0]
         # the loss rows' data-gradient chain (3 AMB rows)
         for l in range(nl - 1, 0, -1):
             self._dgrad(self.disc[l], self.dZd[l], self.dZd[l - 1], Rd, self.Hd[l - 1], self.disc[l - 1].act)

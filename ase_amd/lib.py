@@ -39,6 +39,8 @@ _p, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 # (tests/test_abi.py parses the header and checks names + arity against this table).
 SIGNATURES = {
     "ase_hip_gemm_nt": [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i, _i, _p, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f, _p, _i, _p],
+    "ase_hip_gemm_nt_ex": [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i, _i, _p, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f, _p, _i,
+                           _p, _i, _f, _p, _i64, _i, _p, _d, _p, _p],
     "ase_hip_gemm_tn": [_p, _i64, _p, _i64, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _i, _p],
     "ase_hip_refresh_shadow": [_p, _i, _i, _p, _i64, _p, _i64, _i, _i, _i, _p],
     "ase_hip_refresh_shadow_multi": [_p, _i, _i, _p],
@@ -76,6 +78,7 @@ SIGNATURES = {
     "ase_hip_sample_latents": [_p, _i, _i, _p, _i64, _i, _p, _i64, _i, _p],
     "ase_hip_rms_moments_multi": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p],
     "ase_hip_rms_normalize_multi": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "ase_hip_rms_normalize_multi_v2": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "ase_hip_normalize_rows": [_p, _i64, _p, _i64, _i, _i, _p],
     "ase_hip_sample_actions": [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     "ase_hip_debug_nt_profile": [_p],
@@ -91,6 +94,7 @@ SIGNATURES = {
     "ase_hip_clip_frames": [_p] * 6 + [_i] + [_p] * 4 + [_i, _i, _p, _p, _i] + [_p] * 7,
     "ase_hip_gemm_nt_kernel_id": [_i, _i, _i, _i],
     "ase_hip_apply_multi": [_p, _i, _p, _p, _i, _p],
+    "ase_hip_apply_multi_v2": [_p, _i, _p, _p, _p, _i, _p],
     "ase_hip_gemm_tn_grouped_plan": [_p, _i, _i, _p, _i, _p, _p, _i, _p],
     "ase_hip_prog_create": [_p],
     "ase_hip_prog_destroy": [_p],

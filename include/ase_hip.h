@@ -32,6 +32,8 @@
 extern "C" {
 #endif
 
+/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2 and ase_hip_apply_multi_v2 were added WITHOUT a new version number: a library
+ *  built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at load time) */
 #define ASE_HIP_ABI_VERSION 9
 
 enum { ASE_F32 = 0, ASE_BF16 = 1, ASE_F32X3 = 2 /* f32 storage, products as 3 bf16 MFMAs on a hi/lo split (GEMMs only) */,
@@ -99,6 +101,22 @@ int ase_hip_gemm_nt(const void* A, int64_t lda, const void* B, int64_t ldb, void
                     const float* bias, const void* aux, int64_t ldaux, int aux_split, int aux_delta,
                     float* colsum, int colsum_n, void* mask_out, int64_t ldmask, int M, int N, int K, int act,
                     int aux_mode, int out_f32, float alpha, float* alpha_dev, int dtype, void* stream);
+
+/* ase_hip_gemm_nt with three more duties in its epilogue, each nullable and each what a launch of its own did around the
+ * six launches of the gradient penalty's value path.  dtype ASE_F32H3 only; act NONE / RELU, aux_mode NONE / RELU_BITS, no colsum.
+ *   seed_w (f32[seed_n], seed_n <= N), seed_scale: C[m,n] = seed_scale * seed_w[n] * (act(z) > 0 ? 1 : 0) instead of act(z) - the
+ *     product ase_hip_gp_seed forms for ReLU, bit for bit; columns n >= seed_n store 0.  mask_out still describes act(z).
+ *   twin ([M, ldtwin] of twin_dtype = ASE_F16 / ASE_BF16, ldtwin in elements): the value stored to C once more in 16 bits, by the
+ *     conversion ase_hip_gather_multi applies (RNE; f16 saturating).  With a twin, C may be NULL: no f32 store at all.
+ *   sq_acc (f64*), sq_scale, sq_dyn (nullable scale record, only its factor is read): *sq_acc += sq_scale * factor * sum of the
+ *     squares of the values stored (f32 over 4 consecutive columns, f64 beyond, one atomic per workgroup) - ase_hip_sqnorm.
+ * An overflow report (alpha_dev) covers the f32 values; the twin's saturation is left to ase_hip_scaler_check_multi on its buffer. */
+int ase_hip_gemm_nt_ex(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                       const float* bias, const void* aux, int64_t ldaux, int aux_split, int aux_delta,
+                       float* colsum, int colsum_n, void* mask_out, int64_t ldmask, int M, int N, int K, int act,
+                       int aux_mode, int out_f32, float alpha, float* alpha_dev, int dtype,
+                       const float* seed_w, int seed_n, float seed_scale, void* twin, int64_t ldtwin, int twin_dtype,
+                       double* sq_acc, double sq_scale, const float* sq_dyn, void* stream);
 
 /* G[n, kmap(k)] += alpha * sum_m A[m,n] * B[m,k]   for n < n_real, kmap(k) valid     "TN" GEMM
  *   A [M,N] dtype (output gradients), B [M,K] dtype (layer inputs), G f32 [n_real, k_real]
@@ -173,6 +191,14 @@ int ase_hip_rms_normalize_multi(const float* const* srcs, const int64_t* ld_srcs
                                 const int* remap_h, const int* remap_n, const float* const* means,
                                 const float* const* stds, void* const* outs, const int64_t* ld_outs, int n_streams, int D,
                                 int M, int dtype, void* stream);
+/* ... with a nullable f32 twin per stream (outs32 / ld_outs32, HOST arrays like the others; a NULL entry or a NULL array: none):
+ * the normalised, clamped value BEFORE its rounding to dtype, [M, ld] f32 in 16-byte rows - the demo rows' exact input of the
+ * gradient penalty's value path out of the launch that normalises them anyway (it was an ase_hip_rms_normalize of its own). */
+int ase_hip_rms_normalize_multi_v2(const float* const* srcs, const int64_t* ld_srcs, const int32_t* const* idxs,
+                                   const int* remap_h, const int* remap_n, const float* const* means,
+                                   const float* const* stds, void* const* outs, const int64_t* ld_outs,
+                                   float* const* outs32, const int64_t* ld_outs32, int n_streams, int D, int M, int dtype,
+                                   void* stream);
 
 /* Sequentially merge n_streams batches (sums[s][2*D], counts[s] rows each; counts are the GLOBAL
  * row counts) into `state` exactly as RunningMeanStd.forward does in training mode, and after
@@ -457,6 +483,13 @@ int ase_hip_sample_latents(float* z, int rows, int dim, uint64_t* rng_state, int
  * Replaces: the weight terms of learning/amp_agent.py:449-466 + optimizer.step() (learning/ase_agent.py:287). */
 int ase_hip_apply_multi(const int64_t* desc, int n_layers, const double* opt_state, double* acc, int dtype,
                         void* stream);
+/* ... with a SECOND shadow pair per layer: desc2 = device int64 [n_layers, 8], row l = {Ws3, ldws3, Wts3, ldwts3, eb, 0, 0, 0} or all
+ * zeros (none).  The tile that sends the fresh weight to the 16-bit shadows also writes the packed half-split shadows of W * 2^eb -
+ * exactly what ase_hip_refresh_shadow(dtype = ASE_F32H3 | eb << 16) writes (same split function, same bytes; pitches in f32
+ * elements, 32-byte aligned bases) - so the gradient penalty's value path needs no refresh launches of its own.  dtype ASE_F16 only (anything else is
+ * refused with ASE_EINVAL: the bf16 instantiation would need more than the 64 registers the small kernels are held to). */
+int ase_hip_apply_multi_v2(const int64_t* desc, int n_layers, const int64_t* desc2, const double* opt_state, double* acc,
+                           int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Observation side.
