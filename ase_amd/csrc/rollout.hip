@@ -3,12 +3,15 @@
 
 namespace {
 
+// max(x, lo) as torch.maximum / clamp_min have it: a NaN x stays NaN (fmaxf would return lo)
+__device__ __forceinline__ float floor_keep_nan(float x, float lo) { return x < lo ? lo : x; }
+
 __global__ __launch_bounds__(256) void disc_reward_kernel(const float* __restrict__ logit, int64_t ld_l,
                                                           float* __restrict__ r, int64_t n, float scale) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float l = logit[i * ld_l];
         const float prob = 1.f / (1.f + expf(-l));
-        r[i] = -logf(fmaxf(1.f - prob, 0.0001f)) * scale;
+        r[i] = -logf(floor_keep_nan(1.f - prob, 0.0001f)) * scale;
     }
 }
 
@@ -28,9 +31,9 @@ __global__ __launch_bounds__(256) void enc_reward_kernel(const float* __restrict
             zv[q] = z[row * ld_z + j];
         }
     }
-    const float nrm = fmaxf(sqrtf(wave_sum(ev[0] * ev[0] + ev[1] * ev[1])), 1e-12f);
+    const float nrm = floor_keep_nan(sqrtf(wave_sum(ev[0] * ev[0] + ev[1] * ev[1])), 1e-12f);
     const float dot = wave_sum((ev[0] / nrm) * zv[0] + (ev[1] / nrm) * zv[1]);
-    if (lane == 0) r[row] = fmaxf(dot, 0.f) * scale;
+    if (lane == 0) r[row] = (!(dot <= 0.f) ? dot : 0.f) * scale;        // clamp_min(dot, 0); NaN stays NaN
 }
 
 __global__ __launch_bounds__(256) void gae_kernel(const uint8_t* __restrict__ dones, const float* __restrict__ values,
@@ -132,7 +135,8 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t offset, 
     uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
 #pragma unroll
     for (int i = 0; i < 10; ++i) philox_round(c, k);
-    return (float)c[2] * 2.3283064365386963e-10f;                    // [0, 1)
+    // 24 bits: exact in f32 and < 1.  (float)c[2] * 2^-32 rounds every word >= 0xFFFFFF80 to 1.0, and Bernoulli(1.0) then draws 0
+    return (float)(c[2] >> 8) * 5.9604644775390625e-08f;             // [0, 1)
 }
 
 // Rollout-time action head (learning/amp_models.py:29-36 eval branch + learning/amp_agent.py:160-166): one wave per row,
@@ -185,7 +189,7 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
         const int j = lane + 64 * q;
         if (j < dim) v[q] = x[(int64_t)r * ld_x + j];
     }
-    const float nrm = fmaxf(sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1])), 1e-12f);
+    const float nrm = floor_keep_nan(sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1])), 1e-12f);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int j = lane + 64 * q;
@@ -207,7 +211,7 @@ __global__ __launch_bounds__(256) void sample_latents_kernel(float* __restrict__
         const int j = lane + 64 * q;
         if (j < dim) v[q] = philox_normal(seed, off, (uint64_t)(row_offset + r) * dim + j);
     }
-    const float nrm = fmaxf(sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1])), 1e-12f);
+    const float nrm = floor_keep_nan(sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1])), 1e-12f);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int j = lane + 64 * q;
