@@ -8,8 +8,9 @@ batch (``ase_hip_amp_reset``, csrc/amp_reset.hip); there is no host fallback.
 ``recovery_counter`` with the get-up options) and takes the simulator's tensors as the same ``state`` dict plus ``dof_pos`` /
 ``dof_vel`` [N, D] - plain tensors or the two views of the simulator's interleaved [N, D, 2] dof state.  A reset is a draw
 (``draw_reset`` -> a plan of device tensors) and an apply (``apply_reset``: the launch), so that a recorded plan can be applied
-and an apply can be recorded in a launch program.  Binding a simulator (pushing the written state to the physics engine),
-the target / marker resets of the four tasks and ``_generate_fall_states`` (which needs physics) stay with the caller.
+and an apply can be recorded in a launch program.  Binding a simulator (pushing the written state to the physics engine)
+and ``_generate_fall_states`` (which needs physics) stay with the caller; the target resets of the four tasks are
+``env_tensors.HumanoidTensors.reset_task`` - for the strike task called after ``apply_reset``, as the reference does.
 """
 import numpy as np
 import torch

@@ -378,6 +378,40 @@ class HipBackend:
                                              _ptr(body_pos), 0 if body_pos is None else body_pos.shape[1], int(body_id), float(dt), n,
                                              _ptr(reward), self._stream()), "task_reward")
 
+    # ------------------------------------------------------------------ target resets of the tasks (N8)
+    def task_reset(self, kind, progress_buf=None, change_steps=None, root_states=None, tar_a=None, tar_b=None, tar_speed=None,
+                   tar_states=None, env_ids=None, u=None, steps=None, rng_state=None, advance=True, steps_low=0, steps_high=0,
+                   tar_speed_min=0.0, tar_speed_max=0.0, tar_dist_min=0.0, tar_dist_max=0.0, tar_height_min=0.0, tar_height_max=0.0,
+                   near_dist=0.0, near_prob=0.0, enable_rand_heading=True):
+        """_reset_task / _reset_target / _update_task of kind L.TASK_* in one launch (operands: see ase_hip_task_reset).
+        env_ids (int32, distinct) names the rows, None: every environment with progress_buf >= change_steps.  The draws are
+        either passed in (u f32 [n_ids, L.TASK_RESET_DRAWS[kind]], steps int64 [n_ids]) or made on the device from rng_state
+        (int64 [2] = seed | offset, advanced by one unless advance is false).  tar_a / tar_b / tar_speed / tar_states and
+        change_steps are written in place; root_states / tar_states [N, 13] may be strided views with unit column stride.
+        The strike task reads root_states when the launch runs: call it after the actor reset."""
+        self._f32c(tar_a, tar_b, tar_speed, u)
+        n = next(t for t in (progress_buf, root_states, tar_states) if t is not None).shape[0]
+        for t in (root_states, tar_states):
+            assert t is None or (t.dtype == torch.float32 and t.shape == (n, 13) and t.stride(1) == 1), "[n, 13] f32, unit column stride"
+        for t in (progress_buf, change_steps, steps):
+            assert t is None or (t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 1), "int64 vectors"
+        for t, cols in ((progress_buf, 1), (change_steps, 1), (tar_a, 3 if kind == L.TASK_REACH else 2), (tar_b, 2), (tar_speed, 1)):
+            assert t is None or t.numel() == n * cols, "task_reset: operand shape"
+        n_ids = 0
+        if env_ids is not None:
+            assert env_ids.dtype == torch.int32 and env_ids.is_contiguous() and env_ids.dim() == 1
+            n_ids = env_ids.numel()
+        assert u is None or (0 <= kind < 4 and u.shape == (n_ids, L.TASK_RESET_DRAWS[kind])), "u: [n_ids, draws of the kind]"
+        assert steps is None or steps.numel() == n_ids
+        assert rng_state is None or (rng_state.dtype == torch.int64 and rng_state.numel() == 2 and rng_state.is_contiguous())
+        L.check(self.lib.ase_hip_task_reset(int(kind), _ptr(env_ids), n_ids, _ptr(u), _ptr(steps), _ptr(rng_state), int(advance),
+                                            _ptr(progress_buf), _ptr(change_steps), int(steps_low), int(steps_high),
+                                            _ptr(root_states), _ld(root_states), _ptr(tar_a), _ptr(tar_b), _ptr(tar_speed),
+                                            _ptr(tar_states), _ld(tar_states), float(tar_speed_min), float(tar_speed_max),
+                                            float(tar_dist_min), float(tar_dist_max), float(tar_height_min), float(tar_height_max),
+                                            float(near_dist), float(near_prob), int(enable_rand_heading), n, self._stream()),
+                "task_reset")
+
     # ------------------------------------------------------------------ resets (N6)
     def amp_reset(self, clips, env_ids, kind, motion_ids, motion_times, src_rows, table, root_states, dof_pos, dof_vel, body_pos,
                   body_rot, body_vel, body_ang_vel, local_root_obs, root_height_obs, env_dt, hist,

@@ -1,5 +1,5 @@
 // Once-per-epoch rollout tail: AMP rewards, GAE, advantage normalisation, replay ring, latent RNG.
-#include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -109,36 +109,6 @@ __global__ __launch_bounds__(256) void ring_store_kernel(const float* __restrict
     for (int j = tx; j < D; j += 64) dst[q * D + j] = src[p * ld_src + j];
 }
 
-// Philox4x32-10
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
-    const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-    const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-    const uint32_t n0 = hi1 ^ c[1] ^ k[0], n1 = lo1, n2 = hi0 ^ c[3] ^ k[1], n3 = lo0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    k[0] += 0x9E3779B9u;
-    k[1] += 0xBB67AE85u;
-}
-
-__device__ __forceinline__ float philox_normal(uint64_t seed, uint64_t offset, uint64_t elem) {
-    uint32_t c[4] = {(uint32_t)elem, (uint32_t)(elem >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
-    uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-    for (int i = 0; i < 10; ++i) philox_round(c, k);
-    const float u1 = ((float)c[0] + 1.0f) * 2.3283064365386963e-10f;  // (0, 1]
-    const float u2 = (float)c[1] * 2.3283064365386963e-10f;
-    return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
-}
-
-__device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t offset, uint64_t elem) {
-    uint32_t c[4] = {(uint32_t)elem, (uint32_t)(elem >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
-    uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-#pragma unroll
-    for (int i = 0; i < 10; ++i) philox_round(c, k);
-    // 24 bits: exact in f32 and < 1.  (float)c[2] * 2^-32 rounds every word >= 0xFFFFFF80 to 1.0, and Bernoulli(1.0) then draws 0
-    return (float)(c[2] >> 8) * 5.9604644775390625e-08f;             // [0, 1)
-}
-
 // Rollout-time action head (learning/amp_models.py:29-36 eval branch + learning/amp_agent.py:160-166): one wave per row,
 //   mu (optionally tanh, learning/hrl_network_builder.py:26-29) -> a = mu + sigma * N(0, 1) -> neglogp(a) -> eps-greedy:
 //   rows whose Bernoulli(p_row) draw is 0 take the deterministic action mu (the stored neglogp stays the sampled one).
@@ -226,8 +196,6 @@ __global__ __launch_bounds__(256) void sample_latents_kernel(float* __restrict__
         }
     }
 }
-
-__global__ void rng_advance_kernel(uint64_t* rng) { rng[1] += 1; }
 
 inline int grid_for(int64_t n) {
     int64_t g = (n + 255) / 256;

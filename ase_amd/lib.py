@@ -19,6 +19,7 @@ ACT_NONE, ACT_RELU, ACT_TANH, ACT_SILU, ACT_ELU, ACT_GELU, ACT_SIGMOID, ACT_SELU
 AUX_NONE, AUX_RELU_MASK, AUX_TANH_GRAD, AUX_RELU_BITS, AUX_PREACT = 0, 1, 2, 3, 4
 TASK_HEADING, TASK_LOCATION, TASK_REACH, TASK_STRIKE = range(4)     # ASE_TASK_*
 TASK_OBS_COLS = (5, 2, 3, 15)                                       # columns ase_hip_task_obs writes per kind
+TASK_RESET_DRAWS = (3, 2, 3, 4)                                     # uniforms per row ase_hip_task_reset takes per kind
 RESET_FRAME, RESET_TABLE, RESET_MOTION = range(3)                   # ASE_RESET_*: the kinds of a row of ase_hip_amp_reset
 RESET_HAS_TABLE, RESET_HAS_MOTION = 1, 2                            # ASE_RESET_HAS_*: the host mask of kinds that may occur
 
@@ -89,6 +90,7 @@ SIGNATURES = {
     "ase_hip_humanoid_reset": [_p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _f, _i, _p, _p, _p],
     "ase_hip_task_obs": [_i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i64, _i, _p],
     "ase_hip_task_reward": [_i, _p, _p, _p, _p, _p, _f, _p, _p, _i, _i, _f, _i, _p, _p],
+    "ase_hip_task_reset": [_i, _p, _i, _p, _p, _p, _i, _p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p, _i64] + [_d] * 8 + [_i, _i, _p],
     "ase_hip_amp_reset": [_p] * 6 + [_i] + [_p] * 6 + [_i, _p, _i] + [_p] * 5 + [_i, _i, _p, _p, _p, _i, _p, _i64, _p, _p, _i64, _i,
                           _p, _p, _p, _p, _i, _i, _i, _f, _p, _i, _p],
     "ase_hip_clip_frames": [_p] * 6 + [_i] + [_p] * 4 + [_i, _i, _p, _p, _i] + [_p] * 7,

@@ -40,6 +40,11 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
                                                       compute_humanoid_reset, plain and strike form
   task_obs(kind, root_states, ...) -> obs / task_reward(kind, n_envs, ...) -> reward
                                                       the observation / reward functions of humanoid_heading / _location / _reach / _strike
+  task_reset(kind, ranges, steps_low, steps_high, enable_rand_heading, progress_buf, change_steps, root_states, tar_a, tar_b,
+             tar_speed, tar_states, env_ids, u, steps, rng_state, advance=True) -> ()
+                                                      (change_steps, tar_a, tar_b, tar_speed, tar_states, rng_state written in place)
+                                                      _reset_task / _update_task of humanoid_heading / _location / _reach and
+                                                      HumanoidStrike._reset_target: new targets and change steps in one launch
   amp_reset(root_states, dof_pos, dof_vel, hist, body_pos, body_rot, body_vel, body_ang_vel, env_ids, kind, motion_ids,
             motion_times, src_rows, clip tensors ..., tab_root_states, tab_dof_pos, tab_dof_vel, dof_body_ids, dof_offsets,
             key_body_ids, local_root_obs, root_height_obs, env_dt) -> ()      (root_states, dof_pos, dof_vel, hist written in place)
@@ -608,6 +613,30 @@ def _(kind, n_envs, root_states=None, prev_root_pos=None, tar_a=None, tar_b=None
       tar_states=None, body_pos=None, body_id=0, dt=0.0):
     some = next(t for t in (root_states, tar_a, tar_states, body_pos) if t is not None)
     return some.new_empty(n_envs, dtype=torch.float32)
+
+
+_RESET_RANGES = {'heading': ('tar_speed_min', 'tar_speed_max'), 'location': ('tar_dist_max',),
+                 'reach': ('tar_dist_max', 'tar_height_min', 'tar_height_max'),
+                 'strike': ('tar_dist_min', 'tar_dist_max', 'near_dist', 'near_prob')}
+
+
+@torch.library.custom_op('ase_hip::task_reset', mutates_args=('change_steps', 'tar_a', 'tar_b', 'tar_speed', 'tar_states', 'rng_state'),
+                         device_types='cuda')
+def task_reset(kind: str, ranges: list[float], steps_low: int, steps_high: int, enable_rand_heading: bool,
+               progress_buf: torch.Tensor | None, change_steps: torch.Tensor | None, root_states: torch.Tensor | None,
+               tar_a: torch.Tensor | None, tar_b: torch.Tensor | None, tar_speed: torch.Tensor | None,
+               tar_states: torch.Tensor | None, env_ids: torch.Tensor | None, u: torch.Tensor | None, steps: torch.Tensor | None,
+               rng_state: torch.Tensor | None, advance: bool = True) -> None:
+    """New targets and change steps of 'heading' | 'location' | 'reach' | 'strike' in one launch (operands: see
+    ase_hip_task_reset).  ranges: heading [tar_speed_min, tar_speed_max], location [tar_dist_max], reach [tar_dist_max,
+    tar_height_min, tar_height_max], strike [tar_dist_min, tar_dist_max, near_dist, near_prob].  env_ids None: every environment
+    with progress_buf >= change_steps; draws from u / steps or, on the device, from rng_state (advanced unless advance is false).
+    Every tensor is passed by position, None where the kind or the mode has none."""
+    k = _task_kind(kind)
+    names = _RESET_RANGES[kind]
+    _check(len(ranges) == len(names), f'task_reset: {kind} takes ranges = [{", ".join(names)}]')
+    _backend().task_reset(k, progress_buf, change_steps, root_states, tar_a, tar_b, tar_speed, tar_states, env_ids, u, steps, rng_state,
+                          advance, steps_low, steps_high, enable_rand_heading=enable_rand_heading, **dict(zip(names, ranges)))
 
 
 @torch.library.custom_op('ase_hip::amp_reset', mutates_args=('root_states', 'dof_pos', 'dof_vel', 'hist'), device_types='cuda')

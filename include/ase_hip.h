@@ -32,8 +32,9 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2 and ase_hip_apply_multi_v2 were added WITHOUT a new version number: a library
- *  built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at load time) */
+/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2 and ase_hip_task_reset were added WITHOUT a new version
+ *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
+ *  load time) */
 #define ASE_HIP_ABI_VERSION 9
 
 enum { ASE_F32 = 0, ASE_BF16 = 1, ASE_F32X3 = 2 /* f32 storage, products as 3 bf16 MFMAs on a hi/lo split (GEMMs only) */,
@@ -588,6 +589,51 @@ int ase_hip_task_reward(int kind, const float* root_states, const float* prev_ro
                         const float* tar_b, const float* tar_speed, float tar_speed_scalar, const float* tar_states,
                         const float* body_pos, int n_bodies, int body_id, float dt, int n_envs, float* reward,
                         void* stream);
+
+/* Target draws and resets of the four tasks (an addition to ABI 9, nothing else changed): new targets and new
+ * change steps for the selected environments, in ONE launch, one lane per row, no intermediate tensor.
+ * Which rows:
+ *   ids mode: env_ids (DEVICE int32[n_ids], DISTINCT) names them - _reset_task(env_ids) / _reset_target(env_ids); ids
+ *             outside [0, n_envs) are skipped.
+ *   due mode: env_ids NULL with n_ids = 0: every environment e with progress_buf[e] >= change_steps[e], tested inside the
+ *             kernel - _update_task without nonzero, without a host round trip, on a fixed grid.  Refused for STRIKE (it has
+ *             no change steps).
+ * Where the draws come from - exactly one of u and rng_state is non-NULL:
+ *   u         f32 [n_ids, U] uniforms in [0, 1), ids mode only, in the order of the reference's torch.rand calls: HEADING
+ *             U = 3 {theta, face theta, speed}, LOCATION 2 {x, y}, REACH 3 {x, y, height}, STRIKE 4 {near test, distance,
+ *             theta, rotation theta}; with it steps int64 [n_ids], what torch.randint(low, high) returned (NULL for STRIKE).
+ *             Row i of both belongs to env_ids[i].
+ *   rng_state u64[2] = {seed, offset} on the device, as in ase_hip_sample_latents; steps must be NULL.  The draws of
+ *             environment e depend on (seed, offset, e) only, not on its position in env_ids or on the other rows: uniform
+ *             j is (word 2 of Philox4x32-10 at element 4 e + j, same counter / key layout as above) >> 8, times 2^-24; the
+ *             change steps are steps_low + (((uint64)w * (uint64)(steps_high - steps_low)) >> 32) with w = word 0 of
+ *             element 4 e + 3 - an integer in [steps_low, steps_high), exactly.  advance != 0: the offset moves on by one
+ *             behind the launch (also when env_ids is empty: a call is one stream position).
+ * What is written, for the selected rows only, f32 operation by operation in the reference's order (2 pi and pi are the f32
+ * roundings of the f64 constants; sinf / cosf):
+ *   HEADING : theta = 2 pi u0 - pi, face = 2 pi u1 - pi (both 0 unless enable_rand_heading); tar_a [n, 2] = (cos, sin) theta,
+ *             tar_b [n, 2] = (cos, sin) face; tar_speed [n] = (float)(tar_speed_max - tar_speed_min) u2 + tar_speed_min
+ *   LOCATION: tar_a [n, 2] = root_states[e, 0:2] + tar_dist_max (2 u - 1)
+ *   REACH   : tar_a [n, 3] = {tar_dist_max (2 u0 - 1), tar_dist_max (2 u1 - 1), (float)(tar_height_max - tar_height_min) u2 +
+ *             tar_height_min}
+ *   STRIKE  : d = ((u0 < near_prob ? near_dist : tar_dist_max) - tar_dist_min) u1 + tar_dist_min; target_states[e] =
+ *             {d cos(2 pi u2) + root x, d sin(2 pi u2) + root y, 0.9, quat_from_angle_axis(2 pi u3, z) normalised, 0 x 6}.
+ *             root_states is read when the launch runs: the reference calls _reset_target after the actor reset wrote the
+ *             new root, so this call comes after ase_hip_amp_reset on the stream.
+ *   all but STRIKE: change_steps[e] = progress_buf[e] + steps (int64 [n_envs] both).
+ * Every other row and column is untouched.  root_states / target_states: row e at base + e * ld (ld_root, ld_target >= 13:
+ * views of the simulator's [n_envs, actors, 13] tensor).  An operand a kind does not use must be NULL, one it uses must not
+ * be; the range arguments a kind does not use are ignored.  steps_high - steps_low in [1, 2^32 - 1].
+ * Replaces: HumanoidHeading._update_task / _reset_task (env/tasks/humanoid_heading.py:147-174), HumanoidLocation
+ *   (env/tasks/humanoid_location.py:107-125), HumanoidReach (env/tasks/humanoid_reach.py:111-130),
+ *   HumanoidStrike._reset_target (env/tasks/humanoid_strike.py:108-128). */
+int ase_hip_task_reset(int kind, const int32_t* env_ids, int n_ids, const float* u, const int64_t* steps,
+                       uint64_t* rng_state, int advance, const int64_t* progress_buf, int64_t* change_steps,
+                       int64_t steps_low, int64_t steps_high, const float* root_states, int64_t ld_root, float* tar_a,
+                       float* tar_b, float* tar_speed, float* target_states, int64_t ld_target, double tar_speed_min,
+                       double tar_speed_max, double tar_dist_min, double tar_dist_max, double tar_height_min,
+                       double tar_height_max, double near_dist, double near_prob, int enable_rand_heading, int n_envs,
+                       void* stream);
 
 /* HumanoidAMP / HumanoidAMPGetup resets (ABI 9): for n_ids environments, state initialisation and the refill of
  * their AMP observation history hist [n_envs, n_steps, F] (F as in ase_hip_build_amp_obs), all in ONE launch.
