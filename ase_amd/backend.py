@@ -412,6 +412,40 @@ class HipBackend:
                                             float(near_dist), float(near_prob), int(enable_rand_heading), n, self._stream()),
                 "task_reset")
 
+    # ------------------------------------------------------------------ renewals of the ASE latents (N9)
+    def latent_renew(self, latents, env_ids=None, eps=None, steps=None, rng_state=None, advance=True, progress_buf=None,
+                     reset_steps=None, steps_add=False, steps_low=0, steps_high=1, z2=None):
+        """_reset_latents / _reset_latent_step_count / _update_latents in one launch (operands: see ase_hip_latent_renew).
+        env_ids (int32, distinct) names the rows, None: every environment with reset_steps <= progress_buf (int32 or int64).
+        The draws are either passed in (eps f32 [n_ids, >= dim], steps int32 [n_ids] when reset_steps is given) or made on
+        the device from rng_state (int64 [2] = seed | offset, advanced by one unless advance is false).  latents
+        [n_envs, dim] f32 and reset_steps int32 [n_envs] are written in place; z2 (due mode: every environment's latent after
+        the decision, f32 / f16 / bf16) too.  latents, eps and z2 may be strided views with unit column stride."""
+        assert latents.dtype == torch.float32 and latents.dim() == 2 and latents.stride(1) == 1, "latents: f32 [n_envs, dim], unit column stride"
+        n, dim = latents.shape
+        n_ids = 0
+        if env_ids is not None:
+            assert env_ids.dtype == torch.int32 and env_ids.is_contiguous() and env_ids.dim() == 1, "env_ids: contiguous int32 vector"
+            n_ids = env_ids.numel()
+            if n_ids == 0 and (rng_state is None or not advance):
+                return                                   # nothing to renew and no stream position to move
+        assert eps is None or (eps.dtype == torch.float32 and eps.dim() == 2 and eps.shape[0] == n_ids and eps.shape[1] >= dim and
+                               eps.stride(1) == 1), "eps: f32 [n_ids, >= dim], unit column stride"
+        assert steps is None or (steps.dtype == torch.int32 and steps.is_contiguous() and steps.shape == (n_ids,)), "steps: int32 [n_ids]"
+        assert reset_steps is None or (reset_steps.dtype == torch.int32 and reset_steps.is_contiguous() and
+                                       reset_steps.shape == (n,)), "reset_steps: int32 [n_envs]"
+        assert progress_buf is None or (progress_buf.dtype in (torch.int32, torch.int64) and progress_buf.is_contiguous() and
+                                        progress_buf.shape == (n,)), "progress_buf: int32 or int64 [n_envs]"
+        assert rng_state is None or (rng_state.dtype == torch.int64 and rng_state.numel() == 2 and rng_state.is_contiguous())
+        assert z2 is None or (z2.dim() == 2 and z2.shape == (n, dim) and z2.stride(1) == 1), "z2: [n_envs, dim], unit column stride"
+        # an empty tensor has no storage: an empty id list is still ids mode, so it gets a pointer (that is never read)
+        ids_ptr = _ptr(latents) if env_ids is not None and n_ids == 0 else _ptr(env_ids)
+        L.check(self.lib.ase_hip_latent_renew(ids_ptr, n_ids, _ptr(eps), _ld(eps), _ptr(steps), _ptr(rng_state), int(advance),
+                                              _ptr(progress_buf), int(progress_buf is not None and progress_buf.dtype == torch.int64),
+                                              _ptr(reset_steps), int(bool(steps_add)), int(steps_low), int(steps_high),
+                                              _ptr(latents), _ld(latents), _ptr(z2), _ld(z2), 0 if z2 is None else _code(z2.dtype),
+                                              n, dim, self._stream()), "latent_renew")
+
     # ------------------------------------------------------------------ resets (N6)
     def amp_reset(self, clips, env_ids, kind, motion_ids, motion_times, src_rows, table, root_states, dof_pos, dof_vel, body_pos,
                   body_rot, body_vel, body_ang_vel, local_root_obs, root_height_obs, env_dt, hist,

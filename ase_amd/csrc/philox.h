@@ -1,4 +1,4 @@
-// The library's random stream (rollout.hip, task_reset.hip): counter-based Philox4x32-10 on the counter {elem lo, elem hi,
+// The library's random stream (rollout.hip, task_reset.hip, latent_renew.hip): counter-based Philox4x32-10 on the counter {elem lo, elem hi,
 // offset lo, offset hi} with the key {seed lo, seed hi}; rng_state is u64[2] = {seed, offset} on the device, read by the
 // drawing kernel and advanced behind it by rng_advance_kernel.  tests/ref_rollout.py states the stream word for word.
 #pragma once
@@ -36,14 +36,16 @@ __device__ __forceinline__ float philox_uniform(uint64_t seed, uint64_t offset, 
     return (float)(c[2] >> 8) * 5.9604644775390625e-08f;             // [0, 1)
 }
 
-// word 0 of an element, for integer draws
-__device__ __forceinline__ uint32_t philox_word0(uint64_t seed, uint64_t offset, uint64_t elem) {
+// output word W of an element, for integer draws.  The normal of an element uses words 0 and 1, its keep-uniform word 2: word 3
+// of an element is independent of every float the element gives.
+template <int W> __device__ __forceinline__ uint32_t philox_word(uint64_t seed, uint64_t offset, uint64_t elem) {
     uint32_t c[4] = {(uint32_t)elem, (uint32_t)(elem >> 32), (uint32_t)offset, (uint32_t)(offset >> 32)};
     uint32_t k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
 #pragma unroll
     for (int i = 0; i < 10; ++i) philox_round(c, k);
-    return c[0];
+    return c[W];
 }
+__device__ __forceinline__ uint32_t philox_word0(uint64_t seed, uint64_t offset, uint64_t elem) { return philox_word<0>(seed, offset, elem); }
 
 __global__ void rng_advance_kernel(uint64_t* rng) { rng[1] += 1; }
 

@@ -1,10 +1,7 @@
 // Once-per-epoch rollout tail: AMP rewards, GAE, advantage normalisation, replay ring, latent RNG.
-#include "philox.h"
+#include "latent_row.h"
 
 namespace {
-
-// max(x, lo) as torch.maximum / clamp_min have it: a NaN x stays NaN (fmaxf would return lo)
-__device__ __forceinline__ float floor_keep_nan(float x, float lo) { return x < lo ? lo : x; }
 
 __global__ __launch_bounds__(256) void disc_reward_kernel(const float* __restrict__ logit, int64_t ld_l,
                                                           float* __restrict__ r, int64_t n, float scale) {
@@ -174,25 +171,15 @@ __global__ __launch_bounds__(256) void sample_latents_kernel(float* __restrict__
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
-    const uint64_t seed = rng[0], off = rng[1];
-    float v[2] = {0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int j = lane + 64 * q;
-        if (j < dim) v[q] = philox_normal(seed, off, (uint64_t)(row_offset + r) * dim + j);
-    }
-    const float nrm = floor_keep_nan(sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1])), 1e-12f);
+    float v[2];
+    latent_row_normals(rng[0], rng[1], (uint64_t)(row_offset + r) * dim, dim, lane, v);
+    latent_row_normalize(v);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int j = lane + 64 * q;
         if (j < dim) {
-            const float o = v[q] / nrm;
-            z[(int64_t)r * dim + j] = o;
-            if (z2) {
-                if (z2_dtype == ASE_BF16) reinterpret_cast<bf16_t*>(z2)[(int64_t)r * ld_z2 + j] = (bf16_t)o;
-                else if (z2_dtype == ASE_F16) reinterpret_cast<f16_t*>(z2)[(int64_t)r * ld_z2 + j] = from_f32<f16_t>(o);
-                else reinterpret_cast<float*>(z2)[(int64_t)r * ld_z2 + j] = o;
-            }
+            z[(int64_t)r * dim + j] = v[q];
+            if (z2) latent_store_as(z2, z2_dtype, (int64_t)r * ld_z2 + j, v[q]);
         }
     }
 }

@@ -523,6 +523,7 @@ class CommonAgent:
         for n in range(self.horizon_length):
             self.obs = self.env_reset(done_indices)
             E['obses'][n].copy_(self.obs['obs'])
+            self._rollout_step = n                    # the experience slot of this step, for a _before_act that writes into it
             self._before_act()
             res = self._act()
             for k in ('actions', 'neglogpacs', 'values', 'mus', 'sigmas'):
@@ -1142,6 +1143,8 @@ class ASEAgent(AMPAgent):
         self._enc_reward_scale = config['enc_reward_scale']
         self._enc_grad_penalty = config['enc_grad_penalty']
         self._enc_reward_w = config['enc_reward_w']
+        # opt-in: latent renewals as launches of backend.latent_renew (csrc/latent_renew.hip) instead of the host path below
+        self._device_latents = bool(config.get('device_latents', False))
 
     def _build_net_config(self):
         c = super()._build_net_config()
@@ -1155,6 +1158,11 @@ class ASEAgent(AMPAgent):
         self.tensor_list += ['ase_latents']
         self._ase_latents = torch.zeros(N, self._latent_dim, dtype=torch.float32, device=dev)      # learning/ase_agent.py:24-27
         self._latent_reset_steps = torch.zeros(N, dtype=torch.int32, device=dev)
+        self._rollout_step, self._latents_slot = 0, -1       # device_latents: the slot _update_latents writes / has written
+        if self._device_latents:
+            assert hasattr(self.backend, 'latent_renew'), "device_latents needs a backend with latent_renew"
+            assert np.isfinite(self._latent_steps_min) and np.isfinite(self._latent_steps_max) and \
+                int(self._latent_steps_min) < int(self._latent_steps_max), "device_latents: finite latent_steps_min < latent_steps_max"
 
     # ---- per-environment latents (learning/ase_agent.py:310-379)
     def _progress_buf(self):
@@ -1167,6 +1175,13 @@ class ASEAgent(AMPAgent):
             env_ids = torch.arange(self.num_actors * self.num_agents, dtype=torch.long, device=self.ppo_device)
         if len(env_ids) > 0:
             env_ids = torch.as_tensor(env_ids, dtype=torch.long, device=self.ppo_device)
+            if self._device_latents:
+                # one launch on the stream sample_latents(n) reads: environment e gets row e of sample_latents(N), so a full
+                # reset gives the host path's latents
+                self.backend.latent_renew(self._ase_latents, env_ids=env_ids.to(torch.int32).contiguous().view(-1),
+                                          rng_state=self.engine.rng_state, reset_steps=self._latent_reset_steps, steps_add=False,
+                                          steps_low=int(self._latent_steps_min), steps_high=int(self._latent_steps_max))
+                return obs
             self._reset_latents(env_ids)
             self._reset_latent_step_count(env_ids)
         return obs
@@ -1185,6 +1200,14 @@ class ASEAgent(AMPAgent):
         self._ase_latents[env_ids] = self._sample_latents(len(env_ids))
 
     def _update_latents(self):
+        if self._device_latents:
+            # the due test runs inside the launch, which also writes every latent into this step's experience slot
+            n = self._rollout_step
+            self.backend.latent_renew(self._ase_latents, rng_state=self.engine.rng_state, progress_buf=self._progress_buf().contiguous(),
+                                      reset_steps=self._latent_reset_steps, steps_add=True, steps_low=int(self._latent_steps_min),
+                                      steps_high=int(self._latent_steps_max), z2=self.experience['ase_latents'][n])
+            self._latents_slot = n
+            return
         new_latent_envs = self._latent_reset_steps <= self._progress_buf()
         if bool(torch.any(new_latent_envs)):
             ids = new_latent_envs.nonzero(as_tuple=False).flatten()
@@ -1202,6 +1225,9 @@ class ASEAgent(AMPAgent):
 
     def _rollout_extras(self, n, res_dict, infos):
         super()._rollout_extras(n, res_dict, infos)
+        if self._latents_slot == n:                   # _update_latents' launch wrote the slot
+            self._latents_slot = -1
+            return
         self.experience['ase_latents'][n].copy_(self._ase_latents)
 
     def _record_train_batch_info(self, batch_dict, train_info):

@@ -268,7 +268,9 @@ class ASEPlayer(AMPPlayerContinuous):
         self._latent_steps_min = config.get('latent_steps_min', np.inf)
         self._latent_steps_max = config.get('latent_steps_max', np.inf)
         self._enc_reward_scale = config['enc_reward_scale']
+        self._device_latents = bool(config.get('device_latents', False))     # opt-in: _reset_latents as one backend.latent_renew launch
         super().__init__(config)
+        assert not self._device_latents or hasattr(self.backend, 'latent_renew'), "device_latents needs a backend with latent_renew"
         if self.env is not None and hasattr(self.env, 'task'):
             batch_size = self.env.task.num_envs
         else:
@@ -303,7 +305,11 @@ class ASEPlayer(AMPPlayerContinuous):
         done_env_ids = torch.as_tensor(done_env_ids, dtype=torch.long, device=self.device)
         if len(done_env_ids) == 0:
             return
-        self._ase_latents[done_env_ids] = self.model.a2c_network.sample_latents(len(done_env_ids))
+        if self._device_latents:
+            self.backend.latent_renew(self._ase_latents, env_ids=done_env_ids.to(torch.int32).contiguous().view(-1),
+                                      rng_state=self.engine.rng_state)
+        else:
+            self._ase_latents[done_env_ids] = self.model.a2c_network.sample_latents(len(done_env_ids))
         self._change_char_color(done_env_ids)
 
     def _update_latents(self):

@@ -91,6 +91,7 @@ SIGNATURES = {
     "ase_hip_task_obs": [_i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i64, _i, _p],
     "ase_hip_task_reward": [_i, _p, _p, _p, _p, _p, _f, _p, _p, _i, _i, _f, _i, _p, _p],
     "ase_hip_task_reset": [_i, _p, _i, _p, _p, _p, _i, _p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p, _i64] + [_d] * 8 + [_i, _i, _p],
+    "ase_hip_latent_renew": [_p, _i, _p, _i64, _p, _p, _i, _p, _i, _p, _i, _i64, _i64, _p, _i64, _p, _i64, _i, _i, _i, _p],
     "ase_hip_amp_reset": [_p] * 6 + [_i] + [_p] * 6 + [_i, _p, _i] + [_p] * 5 + [_i, _i, _p, _p, _p, _i, _p, _i64, _p, _p, _i64, _i,
                           _p, _p, _p, _p, _i, _i, _i, _f, _p, _i, _p],
     "ase_hip_clip_frames": [_p] * 6 + [_i] + [_p] * 4 + [_i, _i, _p, _p, _i] + [_p] * 7,

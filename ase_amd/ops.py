@@ -45,6 +45,10 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
                                                       (change_steps, tar_a, tar_b, tar_speed, tar_states, rng_state written in place)
                                                       _reset_task / _update_task of humanoid_heading / _location / _reach and
                                                       HumanoidStrike._reset_target: new targets and change steps in one launch
+  latent_renew(latents, env_ids, eps, steps, rng_state, advance, progress_buf, reset_steps, steps_add, steps_low, steps_high, z2) -> ()
+                                                      (latents, reset_steps, rng_state, z2 written in place)
+                                                      ASEAgent._reset_latents + _reset_latent_step_count / _update_latents and
+                                                      the step's ase_latents copy (learning/ase_agent.py:310-379) in one launch
   amp_reset(root_states, dof_pos, dof_vel, hist, body_pos, body_rot, body_vel, body_ang_vel, env_ids, kind, motion_ids,
             motion_times, src_rows, clip tensors ..., tab_root_states, tab_dof_pos, tab_dof_vel, dof_body_ids, dof_offsets,
             key_body_ids, local_root_obs, root_height_obs, env_dt) -> ()      (root_states, dof_pos, dof_vel, hist written in place)
@@ -637,6 +641,27 @@ def task_reset(kind: str, ranges: list[float], steps_low: int, steps_high: int, 
     _check(len(ranges) == len(names), f'task_reset: {kind} takes ranges = [{", ".join(names)}]')
     _backend().task_reset(k, progress_buf, change_steps, root_states, tar_a, tar_b, tar_speed, tar_states, env_ids, u, steps, rng_state,
                           advance, steps_low, steps_high, enable_rand_heading=enable_rand_heading, **dict(zip(names, ranges)))
+
+
+@torch.library.custom_op('ase_hip::latent_renew', mutates_args=('latents', 'reset_steps', 'rng_state', 'z2'), device_types='cuda')
+def latent_renew(latents: torch.Tensor, env_ids: torch.Tensor | None, eps: torch.Tensor | None, steps: torch.Tensor | None,
+                 rng_state: torch.Tensor | None, advance: bool, progress_buf: torch.Tensor | None, reset_steps: torch.Tensor | None,
+                 steps_add: bool, steps_low: int, steps_high: int, z2: torch.Tensor | None) -> None:
+    """New unit latents (and step counts, when reset_steps is given) of the ASE agent's environments in one launch (operands: see
+    ase_hip_latent_renew).  env_ids None: every environment with reset_steps <= progress_buf, and z2 [n_envs, dim] receives every
+    environment's latent after the decision; draws from eps / steps or, on the device, from rng_state (advanced unless advance is
+    false).  Every tensor is passed by position, None where the mode has none."""
+    _check(latents.dim() == 2 and latents.dtype == torch.float32 and latents.stride(1) == 1, 'latent_renew: latents f32 [n_envs, dim]')
+    for name, t, dts in (('env_ids', env_ids, (torch.int32,)), ('eps', eps, (torch.float32,)), ('steps', steps, (torch.int32,)),
+                         ('rng_state', rng_state, (torch.int64,)), ('progress_buf', progress_buf, (torch.int32, torch.int64)),
+                         ('reset_steps', reset_steps, (torch.int32,)), ('z2', z2, (torch.float32, torch.float16, torch.bfloat16))):
+        _check(t is None or t.dtype in dts, f'latent_renew: {name} must be {" or ".join(str(d) for d in dts)}')
+    _backend().latent_renew(latents, env_ids, eps, steps, rng_state, advance, progress_buf, reset_steps, steps_add, steps_low, steps_high, z2)
+
+
+@latent_renew.register_fake
+def _(latents, env_ids, eps, steps, rng_state, advance, progress_buf, reset_steps, steps_add, steps_low, steps_high, z2):
+    return None
 
 
 @torch.library.custom_op('ase_hip::amp_reset', mutates_args=('root_states', 'dof_pos', 'dof_vel', 'hist'), device_types='cuda')

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2 and ase_hip_task_reset were added WITHOUT a new version
+/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset and ase_hip_latent_renew were added WITHOUT a new version
  *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
  *  load time) */
 #define ASE_HIP_ABI_VERSION 9
@@ -634,6 +634,43 @@ int ase_hip_task_reset(int kind, const int32_t* env_ids, int n_ids, const float*
                        double tar_speed_max, double tar_dist_min, double tar_dist_max, double tar_height_min,
                        double tar_height_max, double near_dist, double near_prob, int enable_rand_heading, int n_envs,
                        void* stream);
+
+/* Renewals of the ASE agent's per-environment latents (an addition to ABI 9, nothing else changed): new unit
+ * latents and new step counts for the selected environments, in ONE launch, one wave per row (lanes j and j + 64 hold the
+ * row's elements, dim 1 .. 128), no intermediate tensor.
+ * Which rows:
+ *   ids mode: env_ids (DEVICE int32[n_ids], DISTINCT) names them - _reset_latents(env_ids) of env_reset and of the player;
+ *             ids outside [0, n_envs) are skipped and never dereferenced.
+ *   due mode: env_ids NULL with n_ids = 0: every environment e with reset_steps[e] <= progress_buf[e], tested inside the
+ *             kernel - _update_latents without any / nonzero, without a host round trip, on a fixed grid.  progress_buf is
+ *             int64 [n_envs] when progress_i64 is set, else int32 [n_envs]; it is NULL in ids mode.
+ * A renewed row: latents[e, 0:dim] = v / max(|v|, 1e-12) with v the row's dim normals (torch.nn.functional.normalize; a NaN
+ * in v makes the row NaN, an all-zero v gives zeros), row e at latents + e * ld_z (ld_z >= dim).  Rows that are not
+ * renewed are not written.
+ * The step counts, only if reset_steps (int32 [n_envs]) is given: steps_add = 0: reset_steps[e] = s
+ * (_reset_latent_step_count); steps_add != 0: reset_steps[e] += s (_update_latents; required in due mode, which also
+ * requires reset_steps).  Without reset_steps (the player's resets) no step is drawn and steps must be NULL.
+ * Where the draws come from - exactly one of eps and rng_state is non-NULL:
+ *   eps       f32 [n_ids, >= dim] normals with row stride ld_eps, ids mode only, and with it steps int32 [n_ids] (what
+ *             torch.randint_like returned) whenever reset_steps is given.  Row i of both belongs to env_ids[i].
+ *   rng_state u64[2] = {seed, offset} on the device, as in ase_hip_sample_latents; steps must be NULL.  Normal j of
+ *             environment e is the normal of element e * dim + j: a renewed row e is row e of
+ *             ase_hip_sample_latents(rows = n_envs, dim) at the same stream position, whichever other rows are renewed.  The
+ *             step count is steps_low + (((uint64)w * (uint64)(steps_high - steps_low)) >> 32) with w = output word 3 of
+ *             element e * dim (words 0 and 1 make that element's normal, word 2 its keep-uniform) - an integer in
+ *             [steps_low, steps_high), exactly; steps_high - steps_low in [1, 2^32 - 1] and the range within int32.
+ *             advance != 0: the offset moves on by one behind the launch (also when env_ids is empty: a call is one stream
+ *             position).
+ * z2 (nullable, due mode only): a second output [n_envs, ld_z2 >= dim] in z2_dtype (ASE_F32 / ASE_F16 / ASE_BF16, converted
+ * as in ase_hip_sample_latents): row e receives the latent of EVERY environment after the decision, renewed or kept - the
+ * copy of all latents into the step's experience slot, folded into the launch.
+ * Replaces: ASEAgent.env_reset's latent part, _reset_latent_step_count, _reset_latents, _update_latents
+ *   (learning/ase_agent.py:310-379), ASEPlayer._reset_latents (learning/ase_players.py), and the ase_latents copy of
+ *   play_steps (learning/ase_agent.py:36-115). */
+int ase_hip_latent_renew(const int32_t* env_ids, int n_ids, const float* eps, int64_t ld_eps, const int32_t* steps,
+                         uint64_t* rng_state, int advance, const void* progress_buf, int progress_i64, int32_t* reset_steps,
+                         int steps_add, int64_t steps_low, int64_t steps_high, float* latents, int64_t ld_z, void* z2,
+                         int64_t ld_z2, int z2_dtype, int n_envs, int dim, void* stream);
 
 /* HumanoidAMP / HumanoidAMPGetup resets (ABI 9): for n_ids environments, state initialisation and the refill of
  * their AMP observation history hist [n_envs, n_steps, F] (F as in ase_hip_build_amp_obs), all in ONE launch.
