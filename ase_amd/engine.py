@@ -160,39 +160,21 @@ class UpdateEngine:
         # Scheduling options (cfg['engine_opts'], a dict; every default is the measured best of its A/B on MI355X):
         #   tn_grouped      weight gradients of a branch queued and launched as ONE grouped grid (else one launch per layer)
         #   tn_wg_side      workgroups the planner sizes a SIDE branch's grouped launch for (it runs beside other branches)
-        #   tn_early        policy weight gradients as soon as the actor's data-gradient chain is through, beside the style-MLP
-        #                   tail (else ONE policy launch as the last kernel of the step; 70.4 ms either way)
         #   disc_early      head of the discriminator branch submitted at the top of the step, into the ~80 us of prologue kernels
         #   short_prologue  only the observation chain in front of the actor chain; latent copies / gathers on side streams
-        #   style_early     style MLP beside the observation chain (69.3 vs 68.9 ms: the window is not idle)
         #   relu_bits       bit-mask twins of ReLU activations for the data-gradient epilogues
         #   fused_apply     weight-only loss terms + Adam + shadow refresh in one launch per branch (apply_wide: its 16-byte path)
-        #   side_streams    2 = critic and discriminator on their own streams, 1 = they share one
-        #   gp_scale_split  f16 mode: the gradient scale split between the two factors of the penalty chain's products (_gp_scales)
         #   xstep           the head of the discriminator branch (zero its gradient bucket, AMP moments -> normalise -> forward) is
         #                   NOT chained behind the main stream: it follows the branch's own optimizer step of the PREVIOUS
         #                   optimisation step on its stream and runs under that step's policy tail (grouped weight gradients ->
         #                   reduce -> optimizer, ~290 us with one queue busy) and this step's prologue of tiny kernels
-        #   style_side      the style MLP's backward + its three weight gradients (style_wg > 0: own small grouped launch sized for
-        #                   that many workgroups; 0: direct launches of the split-M kernel) beside the policy's wide
-        #                   weight-gradient launch instead of in front of it.  Measured SLOWER (f16gpx3 73.9 -> 76.7 / 79.0 ms with
-        #                   64 / 32 workgroups: three narrow problems over 32768 rows on a few CUs outlast the wide launch): off
         #   prefetch        (with xstep) the step's weight-independent prologue - observation moments -> running statistics ->
         #                   normalised [obs | latent] inputs, latent copies, diversity draw, loss-head fields - is submitted at the top
         #                   of the step on the critic's stream WITHOUT waiting for the main stream: it runs under the previous step's
         #                   policy tail, the inputs it writes are double-buffered by step parity (Xa / Xc / Zs)
-        #   disc_after_style  (with xstep) the discriminator head's matrix launches wait until the main stream has launched the style
-        #                   MLP's forward (its statistics / normalisation half stays un-chained).  Measured SLOWER (bf16 62.9 ->
-        #                   65.2 ms): the update is bound by total matrix-pipe time, CUs left idle for the critical path are lost
         #   side_priority   HIP priority of the branch streams, one number or [critic, discriminator, penalty value path] (0 = default,
         #                   -1 = high; the main stream's priority is the caller's)
-        #   gp_split        gp_f32 = 'x3': 'f16' = three f16 MFMAs per product on hi / lo splits of scaled operands (ASE_F32H3, ~2^-22),
-        #                   'bf16' = round 4's bf16 split (ASE_F32X3, ~2^-17; penalty 1.08e-4 off in the driver's round-4 run)
-        #   gp_value_late   (gp_stream off) the penalty's value path behind the loss rows' forward and heads instead of in front of them.
-        #                   Measured SLOWER: 76.28 vs 75.61 ms (four interleaved repetitions, profiles/r06_schedule_options_ab.txt): off
-        #   stream_offset   (measurement aid) throw-away streams taken from the pool in front of the branch streams: streams land on the
-        #                   hardware queues in creation order, this shifts the engine's places
-        #   gp_fuse         gp_f32 = 'x3' with the f16 split: the helper launches around the value path's matrix launches ride in those
+        #   gp_fuse         gp_f32 = 'x3' (the half split): the helper launches around the value path's matrix launches ride in those
         #                   launches' epilogues (backend capability nt_fused_epilogue, ase_hip_gemm_nt_ex) - the seed s w_logit [h > 0]
         #                   out of the last forward launch (gp_seed: gone, g.H[-1] never stored), the 16-bit copies of the chain out of
         #                   the launches that produce it (the conversion launch: gone, S s g_0 never stored in f32) and sum (S s g_0)^2
@@ -214,10 +196,8 @@ class UpdateEngine:
         #                   step (4096 rows: 796 vs 1038 us, 2048 rows: 622 vs 919; 8192 rows: 1089 vs 1044 - off again) and under the
         #                   dynamic loss scale (95.3 vs 115.2 ms).  'auto' (default) = on for minibatches below 8192 rows and under the
         #                   dynamic loss scale, off otherwise; True / False force it
-        o = dict(tn_grouped=True, tn_wg_side=64, tn_early=False, disc_early=True, short_prologue=True, style_early=False,
-                 relu_bits=True, fused_apply=True, apply_wide=True, side_streams=2, gp_scale_split=True, xstep=True,
-                 gp_stream='auto', style_side=0, style_wg=0, side_priority=None, prefetch=True, disc_after_style=False, gp_split='f16',
-                 stream_offset=0, gp_value_late=False, gp_fuse='auto')
+        o = dict(tn_grouped=True, tn_wg_side=64, disc_early=True, short_prologue=True, relu_bits=True, fused_apply=True,
+                 apply_wide=True, xstep=True, gp_stream='auto', side_priority=None, prefetch=True, gp_fuse='auto')
         unknown = set(cfg.get('engine_opts', {}) or {}) - set(o)
         assert not unknown, f"unknown engine_opts {sorted(unknown)}"
         o.update(cfg.get('engine_opts', {}) or {})
@@ -225,7 +205,6 @@ class UpdateEngine:
         self._tn_defer = bool(getattr(backend, 'grouped_tn_ok', None)) and bool(o['tn_grouped'])
         self._tn_queue, self._tn_plans = [], {}          # weight gradients queued by the CURRENT branch (see _flush_tn)
         self._tn_wg_side = int(o['tn_wg_side'])
-        self._tn_early = bool(o['tn_early'])
         self._disc_early = bool(o['disc_early'])
         self._early_fork = None
         # (captured hipGraphs keep the serial prologue: at config-2 size torch's capture_end segfaults on the graph of a step whose
@@ -233,8 +212,6 @@ class UpdateEngine:
         #  the default replay form and 2x faster than the captured graph anyway, are not affected)
         self._short_prologue = bool(o['short_prologue']) and cfg.get('graph_capture') != 'hipgraph'
         self._prep = self._lat_ready = self._fill_done = None
-        self._style_early = bool(o['style_early'])
-        self._n_side = max(1, min(int(o['side_streams']), 2))
         self._apply_groups = None
         self._use_bits = bool(o['relu_bits'])
         self._fused_apply = hasattr(backend, 'apply_multi') and bool(o['fused_apply'])
@@ -243,21 +220,16 @@ class UpdateEngine:
         gp_side = (self.dyn_scale or self.M < 8192) if o['gp_stream'] == 'auto' else bool(o['gp_stream'])      # (self.M: THIS rank's rows)
         self._gp_side = gp_side and cfg.get('graph_capture') != 'hipgraph'      # (a fork from a forked stream: same capture_end crash)
         self._gp_fuse = bool(self.gp32 and getattr(backend, 'nt_fused_epilogue', False) and cfg.get('gp_f32') == 'x3'
-                             and getattr(backend, 'x3', None) is not None and o['gp_split'] == 'f16'
-                             and (o['gp_fuse'] == 'auto' or bool(o['gp_fuse'])))
+                             and getattr(backend, 'x3', None) is not None and (o['gp_fuse'] == 'auto' or bool(o['gp_fuse'])))
         # (gp_fuse: the value path's half-split shadows are kept current by the optimizer launch and refresh_shadows, see _gp_value)
         # (it stays set where the split optimizer launch never runs - truncate_grads, the end-of-step forms of phase_apply: those end in
         #  refresh_shadows(), which calls _gp_refresh)
         self._gp_split = self._gp_fuse and hasattr(backend, 'apply_multi_split') and self._fused_apply and dtype == torch.float16
         self._gp_x_done = False          # this step's normalise launch wrote the value path's f32 input (_disc_inputs)
-        self._style_side = int(o['style_side'])
-        self._disc_after_style = bool(o['disc_after_style'])
-        self._disc_split = False
         self._enc_z_ready = False
         self._prefetch = bool(o['prefetch'])
         self._par, self._par_set, self._last_par, self._fenced = 0, False, None, False
         self._stats_exchanged = False    # this step's partial statistics were exchanged inside the un-chained heads (phase_stats)
-        self._style_wg = int(o['style_wg'])
         sp = o['side_priority']
         if sp is None:
             # measured on MI355X, config 2, with the main stream high (agents: main_stream_priority): the policy's second stream
@@ -591,7 +563,7 @@ class UpdateEngine:
         are current behind every route that changes the masters - the optimizer launch writes them (apply_multi_split) and
         every other route ends in refresh_shadows, which calls this."""
         g = self._gp32
-        half = self.cfg.get('gp_f32') == 'x3' and getattr(self.be, 'x3', None) is not None and self.engine_opts['gp_split'] == 'f16'
+        half = self.cfg.get('gp_f32') == 'x3' and getattr(self.be, 'x3', None) is not None
         for l, d in enumerate(self.disc):
             self.be.refresh_shadow(d.W[0], g.Ws[l], g.Wts[l], d.split_src, d.split_dst, **({'x3_exp': 11} if half else {}))
 
@@ -914,19 +886,11 @@ class UpdateEngine:
             # the optimizer state; the loss heads further down wait for begin_step.
             self._build_apply_desc()
             lo, hi = self._apply_groups['disc'][2:]
-            # disc_after_style: only the HBM-bound half of the head is submitted here; its matrix launches are held back until the
-            # main stream has launched the style MLP's forward (phase_main) - three narrow launches that open the step's critical
-            # path and took 105 us instead of ~35 when they had to queue for CUs behind the 120-us tiles of this branch
-            self._disc_split = bool(self._disc_after_style and self.style)
             with self._Branch(self, self._side(1), nowait=True):
                 be.zero_(self.grads[lo:hi])
                 if not merged:                   # (merged: the prologue's begin_step zeroed the whole statistics buffer)
                     be.zero_(self.amp_sums)
-                if self._disc_split:
-                    self._disc_inputs(amp_streams, ds)
-                    self._disc_fwd_out = 'split'
-                else:
-                    self._disc_fwd_out = self._disc_forward(amp_streams, ds)
+                self._disc_fwd_out = self._disc_forward(amp_streams, ds)
         pre = None
         if pf:
             # The weight-independent prologue, un-chained like the discriminator's head: on the critic's stream it follows that
@@ -988,9 +952,8 @@ class UpdateEngine:
         if self._short_prologue and self._amp_stats_in_branch():
             # Short prologue (single GPU, streams): the actor chain - the critical path - keeps only the observation chain
             # (moments -> finalise -> normalise) in front of it on the main stream.  The latent copies and the diversity draw
-            # (engine_opts style_early: the style MLP's three small matrix kernels too) run beside it on the critic's stream,
-            # followed by the gather of the loss-head fields and the mask sum (first needed ~300 us later); zeroing the
-            # gradients goes to the discriminator's stream (that branch is their first user).
+            # run beside it on the critic's stream, followed by the gather of the loss-head fields and the mask sum (first
+            # needed ~300 us later); zeroing the gradients goes to the discriminator's stream (that branch is their first user).
             m0 = self._mark()
             with self._Branch(self, self._side(1), m0):
                 be.zero_(self.grads[:self.n_train])
@@ -1000,10 +963,6 @@ class UpdateEngine:
                 self.gather_minibatch(ds, idx, remap, part=2)
                 if self.div_on:
                     self._draw_new_latents(new_z)
-                if self.style and self._style_early:
-                    sd = self.actor[0].split_dst
-                    h = self._fwd_chain(self.style[:-1], self.Zs, self.Hs, self.Ra)
-                    self._fwd(self.style[-1], h, self.Xa[:, sd:], self.Ra)
                 self._lat_ready = self._mark()
                 self.gather_minibatch(ds, idx, remap, part=1)
                 if self.masked:
@@ -1056,9 +1015,7 @@ class UpdateEngine:
         if not self.multi_stream:
             return None
         if self._side_streams is None:
-            self._pad_streams = [torch.cuda.Stream(device=self.dev, priority=p) for _ in range(int(self.engine_opts['stream_offset']))
-                                 for p in (0, -1)]
-            self._side_streams = [torch.cuda.Stream(device=self.dev, priority=self._side_prio[k % 3]) for k in range(self._n_side)]
+            self._side_streams = [torch.cuda.Stream(device=self.dev, priority=self._side_prio[k]) for k in range(2)]
             if self.gp32 and not self._gp_side and self._gp_stream_obj is None:
                 # A gp_f32 engine takes its value-path stream from the pool even when it does not use it (gp_stream off): streams
                 # land on the hardware queues in creation order, and an engine that takes THREE streams shifts every later engine of
@@ -1066,7 +1023,7 @@ class UpdateEngine:
                 # with two of their branch streams on one hardware queue: 82-85 ms instead of 62, 371-374 instead of 296-303
                 # (profiles/r06_bench_n1.json's history: calls AC / AE against I / M)
                 self._gp_stream_obj = torch.cuda.Stream(device=self.dev, priority=self._side_prio[2])
-        return self._side_streams[k % len(self._side_streams)]
+        return self._side_streams[k]
 
     def fence_side_streams(self):
         """Everything the main stream holds so far happens before whatever the branch streams are given next.  Inside a step
@@ -1201,8 +1158,6 @@ class UpdateEngine:
                 with self._Branch(self, self._gp_stream(), gp_fork) as br:
                     self._gp_value(amp_streams, gp_coef)
                 self._gp_value_done = br
-            elif self.engine_opts['gp_value_late']:
-                self._gp_value_pending = (amp_streams, gp_coef)         # launched by _gp_f32, behind the loss rows' forward and heads
             else:
                 self._gp_value(amp_streams, gp_coef)
 
@@ -1240,9 +1195,7 @@ class UpdateEngine:
         amb_den = self.AMBg if self.shard else self.AMB
         Rd = 3 * AMB
 
-        if self._disc_fwd_out == 'split':            # (its matrix half follows the style forward below)
-            hd = he = None
-        elif self._disc_fwd_out is not None:         # cross-step schedule: submitted at the top of phase_stats
+        if self._disc_fwd_out is not None:           # cross-step schedule: submitted at the top of phase_stats
             hd, he = self._disc_fwd_out
         elif disc_early:
             with self._Branch(self, self._side(1), fork0):
@@ -1265,13 +1218,10 @@ class UpdateEngine:
 
         # The actor chain (2 M rows with the diversity pass) is the longest: it is launched FIRST on the main stream, the
         # critic and the discriminator branches follow on their streams, forked from the events above.
-        # (style_early ran the style MLP with the short prologue on the critic's stream; the un-chained prologue of `prefetch`
-        #  cannot - it precedes the optimizer step that writes the style weights - so the option is ignored there)
-        if self.style and not (self._prep is not None and self._style_early and self._pre_done is None):
+        if self.style:
             sd = self.actor[0].split_dst
             h = self._fwd_chain(self.style[:-1], self.Zs, self.Hs, Ra)
             self._fwd(self.style[-1], h, self.Xa[:, sd:], Ra)
-        style_launched = self._mark() if self._disc_fwd_out == 'split' else None
         ha = self._fwd_chain(self.actor, self.Xa, self.Ha, Ra)
         self._fwd(self.mu_head, ha, self.MU, Ra)
 
@@ -1284,10 +1234,7 @@ class UpdateEngine:
         if self.has_disc:
             tnq, self._tn_queue = self._tn_queue, []          # the branch queues (and flushes) its own weight gradients
             with self._Branch(self, self._side(1), fork0) as br_disc:
-                if self._disc_fwd_out == 'split':
-                    be.wait(style_launched)
-                    hd, he = self._disc_matrices()
-                elif not disc_early:
+                if not disc_early:
                     hd, he = self._disc_forward(amp_streams)
                 be.disc_head(self.HD, self.dHD, self.disc_head.gb[0], self.acc, AMB, amb_den, c['disc_coef'],
                              grad_scale=self.gs, dyn=self._dS)
@@ -1339,29 +1286,21 @@ class UpdateEngine:
                     **ls_kw)
         fork2 = self._mark()
 
-        # -- actor backward on the main stream, critic backward beside it.  The wide layers' weight gradients of BOTH
-        # (one parameter bucket) go out as one grouped launch on the critic's stream as soon as the actor's data-gradient
-        # chain is through, next to the small kernels of the style-MLP backward that end the main stream's chain.
+        # -- actor backward on the main stream, critic backward beside it.  The weight gradients of both and of the style MLP
+        # (one parameter bucket) are queued in that order and go out as ONE grouped launch, the last matrix kernel of the step.
         self._wgrad(self.mu_head, self.dMU, ha, Ra)
         last = self.actor[-1]
         self._dgrad(self.mu_head, self.dMU, self.dZa[-1], Ra, self.Ha[-1], last.act)
         self._bwd_chain(self.actor, self.Xa, self.Ha, self.dZa, Ra)
         tn_actor, self._tn_queue = self._tn_queue, []
-        actor_done = self._mark()
         with self._Branch(self, self._side(0), fork2) as br_cb:
             self._wgrad(self.value_head, self.dV, hc, M)
             last = self.critic[-1]
             self._dgrad(self.value_head, self.dV, self.dZc[-1], M, self.Hc[-1], last.act)
             self._bwd_chain(self.critic, self.Xc, self.Hc, self.dZc, M)
-            if self._tn_early:
-                if actor_done is not None:
-                    be.wait(actor_done)
-                self._tn_queue = tn_actor + self._tn_queue
-                self._flush_tn(0)
-            else:
-                tn_actor = tn_actor + self._tn_queue
-                self._tn_queue = []
-        def style_backward():
+            tn_actor = tn_actor + self._tn_queue
+            self._tn_queue = []
+        if self.style:
             a0, sdn = self.actor[0], self.style[-1]
             sd = a0.split_dst
             self._dgrad(a0, self.dZa[0], self.dStyle, Ra, self.Xa[:, sd:], sdn.act, wts=a0.Wts[sd:], n_out=P(self.z))
@@ -1371,44 +1310,8 @@ class UpdateEngine:
                 p = self.style[-2]
                 self._dgrad(sdn, self.dStyle, self.dZs[-1], Ra, self.Hs[-1], p.act)
                 self._bwd_chain(self.style[:-1], self.Zs, self.Hs, self.dZs, Ra)
-
-        if self.style and self._style_side == 2 and self.multi_stream and self._tn_defer and not self._tn_early:
-            # variant: only the style MLP's three data-gradient launches leave the critical path (critic's stream, beside the
-            # wide weight-gradient launch); its weight gradients follow the wide launch on the main stream as a second grouped
-            # launch over the whole chip
-            self._join_branch(br_cb)
-            wide, self._tn_queue = tn_actor, []
-            with self._Branch(self, self._side(0), actor_done) as br_style:
-                style_backward()
-            narrow, self._tn_queue = self._tn_queue, wide
-            self._flush_tn(0)
-            self._join_branch(br_style)
-            self._tn_queue = narrow
-        elif self.style and self._style_side and self.multi_stream and self._tn_defer and not self._tn_early:
-            # The style MLP's backward (three narrow data-gradient launches, ~75 us back to back) used to sit between the actor's
-            # data-gradient chain and the policy's grouped weight-gradient launch - on the step's critical path.  The wide
-            # launch needs nothing of it: it goes out as soon as the actor's and the critic's chains are through, and the style
-            # backward runs beside it on the critic's stream (idle by then) with its OWN small grouped launch for the three
-            # style weight gradients (sized for the CUs the wide launch leaves free); the optimizer step waits for both.
-            self._join_branch(br_cb)
-            wide, self._tn_queue = tn_actor, []
-            with self._Branch(self, self._side(0), actor_done) as br_style:
-                if self._style_wg <= 0:          # style weight gradients as direct launches of the 128 x 128 split-M kernel
-                    defer, self._tn_defer = self._tn_defer, False
-                    style_backward()
-                    self._tn_defer = defer
-                else:
-                    style_backward()
-                    self._flush_tn(self._style_wg)
-            self._tn_queue = wide
-            self._flush_tn(0)
-            self._join_branch(br_style)
-        else:
-            if self.style:
-                style_backward()
-            self._join_branch(br_cb)
-            if not self._tn_early:
-                self._tn_queue = tn_actor + self._tn_queue
+        self._join_branch(br_cb)
+        self._tn_queue = tn_actor + self._tn_queue
         self._finish_branch('policy', inline_apply, last=True)        # (flushes what is still queued)
         if br_disc is not None:
             self._join_branch(br_disc)
@@ -1656,12 +1559,8 @@ class UpdateEngine:
         """(Sc, Sr): the gradient scale S (a power of two) split between the two factors of the penalty chain's products, as evenly
         as powers of two allow.  Dynamic scale: Sc stays put (2^6, the static mode's value at S = 4096) and Sr = S / Sc moves with the
         scale - returned here is its HOST factor 1 / Sc, the launches multiply the device's S (_dS), 1 / S (_dI), 1 / S^2 (_dI2) in."""
-        split = self.engine_opts.get('gp_scale_split', True)
         if self.dyn_scale:
-            sc = 64.0 if split else 1.0
-            return sc, 1.0 / sc
-        if not split:
-            return 1.0, self.gs
+            return 64.0, 1.0 / 64.0
         e = int(round(math.log2(self.gs)))
         sc = 2.0 ** ((e + 1) // 2)
         return sc, self.gs / sc
@@ -1739,13 +1638,12 @@ class UpdateEngine:
             be.rms_normalize(src, self.amp, sidx, srm, AMB, self.amp_mean[2], self.amp_std[2], [g.X])
         # gp_f32 = 'x3': the six f32-storage launches multiply as three 16-bit MFMAs per product on hi / lo splits instead of the
         # exact-f32 MFMA (1/16 of the 16-bit rate): IEEE-half parts of power-of-two scaled operands (ASE_F32H3, unit roundoff
-        # ~2^-22; round 4 used bf16 parts, ~2^-17, and the driver's run missed the 1e-4 bar on the penalty by 8 %).  Half's
+        # ~2^-22; bf16 parts, ~2^-17, missed the 1e-4 bar on the penalty by 8 %: profiles/r05_gp_split_ab.txt).  Half's
         # narrow exponent range needs the operands near [2^-2, 2^15] after scaling - and the ranges here are known:
         #   normalised observations  |x| <= 5 (the normaliser's clamp)          2^12
         #   hidden activations       O(1); saturation above 1023                2^6
         #   chain values s g_l       O(1e-3 .. 1e-1); saturation above 16       2^12
         #   weights                  O(1/sqrt(K)); saturation above 32          2^11
-        # (engine_opts gp_split = 'bf16' keeps round 4's bf16 split - no range assumption at all - for the same-box A/B)
         fuse = self._gp_fuse
         with self._gp_mode() as ex:
             # (half split: the shadows are written PRE-SPLIT - scaled, [8 hi | 8 lo] halves per group of 8 - once per step instead
@@ -1780,9 +1678,9 @@ class UpdateEngine:
         be = self.be
         x3_prev = getattr(be, 'x3', None)
         mode = self.cfg.get('gp_f32')
-        half = mode == 'x3' and x3_prev is not None and self.engine_opts['gp_split'] == 'f16'
-        if mode == 'x3' and x3_prev is not None:
-            be.x3 = 'f16' if half else True
+        half = mode == 'x3' and x3_prev is not None
+        if half:
+            be.x3 = 'f16'
         try:
             yield (lambda ea: {'x3_exps': (ea, 11)}) if half else (lambda ea: {})
         finally:
@@ -1809,9 +1707,6 @@ class UpdateEngine:
         if self._gp_value_done is not None:
             self._join_branch(self._gp_value_done)
             self._gp_value_done = None
-        if getattr(self, '_gp_value_pending', None) is not None:
-            self._gp_value(*self._gp_value_pending)
-            self._gp_value_pending = None
         if self._gp_fuse:
             # the chain's last launch: S s g_0 straight into the 16-bit row block (never stored in f32) + the sum of its squares;
             # the 16-bit copies of s g_l were written by the launches that produced them (_gp_value)

@@ -103,18 +103,16 @@ def test_first_step_f16_emulated(name, golden_dir):
         assert rel < 0.06, ('grad ' + k, rel)
 
 
-@pytest.mark.parametrize('early', [False, True])
 @pytest.mark.parametrize('name', CASES)
-def test_deferred_weight_gradients(name, early, golden_dir):
+def test_deferred_weight_gradients(name, golden_dir):
     """The grouped weight-gradient launches (all layers of a branch queued during its backward, ONE launch per branch
     group - discriminator | policy - at the end of the branch) read nothing the data-gradient chain overwrites: same
     golden result with every layer deferred."""
     G = torch.load(os.path.join(golden_dir, name + '.pt'), weights_only=False)
     be = EmuBackend(group_all=True)
-    net, eng = first_step(G, be, torch.float32, engine_opts={'tn_early': early})
-    # discriminator branch | actor + critic + style MLP as the last launch of the step; with engine_opts tn_early the actor +
-    # critic layers go beside the style-MLP backward and what the style MLP queued after that is a third launch
-    assert be.grouped_launches == {'ppo': 1, 'amp': 2, 'ase': 3 if early else 2}[G['kind']] and not eng._tn_queue
+    net, eng = first_step(G, be, torch.float32)
+    # discriminator branch | actor + critic + style MLP as the last launch of the step
+    assert be.grouped_launches == {'ppo': 1, 'amp': 2, 'ase': 2}[G['kind']] and not eng._tn_queue
     lr = G['cfg']['learning_rate']
     check_first_step(G, net, eng, rtol=2e-5, gtol=2e-4, wtol=lr * 0.05)
 
@@ -201,3 +199,16 @@ def test_hipgraph_mode_runs_the_plain_schedule(golden_dir):
         Gm['cfg'].update(graph_capture=mode, engine_opts={'xstep': True, 'short_prologue': True, 'gp_stream': True})
         _, eng = first_step(Gm, EmuBackend(), torch.float32)
         assert (eng._xstep, eng._short_prologue, eng._gp_side) == ((False, False, False) if plain else (True, True, True)), mode
+
+
+RETIRED_OPTS = {'style_side': 0, 'style_wg': 0, 'disc_after_style': False, 'style_early': False, 'stream_offset': 0,
+                'side_streams': 2, 'tn_early': False, 'gp_value_late': False, 'gp_split': 'f16', 'gp_scale_split': True}
+
+
+@pytest.mark.parametrize('name', sorted(RETIRED_OPTS))
+def test_retired_engine_opts_are_unknown(name, golden_dir):
+    """The schedule options that lost their A/B are gone with the paths they selected: passing one, even with
+    its old default, is refused like any other unknown key."""
+    G = torch.load(os.path.join(golden_dir, 'ase_tiny.pt'), weights_only=False)
+    with pytest.raises(AssertionError, match='unknown engine_opts'):
+        first_step(G, EmuBackend(), torch.float32, engine_opts={name: RETIRED_OPTS[name]})

@@ -168,11 +168,3 @@ def test_gp_fuse_shadows_follow_every_route_that_changes_the_weights(G, route):
     assert_same_step(res[True][1], res[False][1], route)
     assert not torch.equal(res[True][1]['res']['disc_grad_penalty'], res[True][0]['res']['disc_grad_penalty'])
 
-
-def test_gp_fuse_with_the_value_path_issued_late(G, unfused):
-    """engine_opts gp_value_late (the value path behind the loss rows' forward and heads) in both settings of gp_fuse: the same
-    launches in another place of the sequence - the same numbers as the default order."""
-    for fuse in (True, False):
-        _, eng, out = run_steps(G, FusedEmuBackend(), engine_opts={'gp_fuse': fuse, 'gp_value_late': True})
-        assert eng._gp_fuse == fuse
-        assert_same_step(out[0], unfused[0][0], 'gp_value_late, gp_fuse %s' % fuse)
