@@ -180,9 +180,6 @@ class HipBackend:
         waste most of a 256 x 256 tile's MFMAs, but a work item costs its HBM traffic either way: measured (scripts/lab,
         LAB_TNG_N) the six narrow problems of a step add 67 us to the grouped launch against 156 us as seven launches of the
         128 x 128 kernel."""
-        # (every problem: narrow outputs - heads, style MLP, N or K <= 64 - waste most of a 256 x 256 tile's MFMAs, but a work
-        #  item costs its HBM traffic either way; measured: the six narrow problems of a step add 67 us to the grouped launch
-        #  against 156 us as seven launches of the 128 x 128 kernel)
         return dtype in (torch.bfloat16, torch.float16) and M % 64 == 0 and bias_rows % 64 == 0
 
     def make_tn_plan(self, problems, target_wg=0, alpha_dev=None):

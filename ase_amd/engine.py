@@ -64,6 +64,37 @@ class Dense:
         return self.parts[0][0]
 
 
+class _StepState:
+    """What the phases of ONE optimisation step hand each other.  phase_stats opens every step with a fresh one; it stays alive
+    until the next step replaces it (the replays of the three-graph hipGraph path call _allreduce_stats / _allreduce_grads, which
+    read stats_exchanged and prep).  Whatever outlives a step - _xs, the parity fields, the plan and descriptor caches - is an
+    attribute of the engine.  field: written by -> read by
+      disc_fwd_out     phase_stats, cross-step schedule: (hd, he) of the discriminator head submitted there -> phase_main
+      merged_stats     phase_stats: [amp sums | obs sums | mask sum] travel as ONE collective -> _exchange_amp_sums
+      stats_mark_a     phase_stats (merged): the policy prologue's sums are formed -> _exchange_amp_sums
+      stats_mark_b     _exchange_amp_sums (merged): the collective is through -> phase_stats' prefetch prologue
+      stats_exchanged  phase_stats: the un-chained heads exchanged the partial statistics -> _allreduce_stats
+      pre_done         phase_stats: the prefetch prologue's branch (statistics + normalised inputs came with it) -> phase_main
+      prep             phase_stats: the critic-stream branch of the short / prefetch prologue -> phase_main, _allreduce_stats
+      lat_ready        phase_stats: mark behind the latent copies + diversity draw (only where prep is set) -> phase_main
+      fill_done        phase_stats, short prologue: the gradients are zeroed (only where prep is set) -> phase_main
+      early_fork       phase_stats: fork point of the discriminator branch -> phase_main
+      enc_z_ready      _disc_inputs: the encoder latents were gathered with the branch's head -> _gather_enc_z
+      gp_x_done        _disc_inputs: the normalise launch wrote the value path's f32 input -> _gp_value
+      gp_value_done    _disc_inputs: the value path's branch on its own stream -> _gp_f32 (joins and clears it)
+      disc_acc_mark    phase_main: every loss partial sum of the discriminator branch is launched -> _finish_branch
+      acc_in_bucket    _finish_branch: the loss partial sums travelled inside the policy bucket's exchange -> phase_finish
+      lr_live          step(): the step runs the optimizer, so the adaptive schedule may move the learning rate -> _finalize"""
+    __slots__ = ('disc_fwd_out', 'merged_stats', 'stats_mark_a', 'stats_mark_b', 'stats_exchanged', 'pre_done', 'prep',
+                 'lat_ready', 'fill_done', 'early_fork', 'enc_z_ready', 'gp_x_done', 'gp_value_done', 'disc_acc_mark',
+                 'acc_in_bucket', 'lr_live')
+
+    def __init__(self):
+        self.disc_fwd_out = self.stats_mark_a = self.stats_mark_b = self.pre_done = self.prep = self.lat_ready = None
+        self.fill_done = self.early_fork = self.gp_value_done = self.disc_acc_mark = None
+        self.merged_stats = self.stats_exchanged = self.enc_z_ready = self.gp_x_done = self.acc_in_bucket = self.lr_live = False
+
+
 class UpdateEngine:
     """kind: 'ase' | 'amp' | 'ppo'.  sizes: rows handled by THIS rank (M, AMB) and global counts."""
 
@@ -206,12 +237,10 @@ class UpdateEngine:
         self._tn_queue, self._tn_plans = [], {}          # weight gradients queued by the CURRENT branch (see _flush_tn)
         self._tn_wg_side = int(o['tn_wg_side'])
         self._disc_early = bool(o['disc_early'])
-        self._early_fork = None
         # (captured hipGraphs keep the serial prologue: at config-2 size torch's capture_end segfaults on the graph of a step whose
         #  prologue is forked onto the side streams - every precision, ROCm 7.2; `profiles/r06_hipgraph_triage.txt`.  Launch programs,
         #  the default replay form and 2x faster than the captured graph anyway, are not affected)
         self._short_prologue = bool(o['short_prologue']) and cfg.get('graph_capture') != 'hipgraph'
-        self._prep = self._lat_ready = self._fill_done = None
         self._apply_groups = None
         self._use_bits = bool(o['relu_bits'])
         self._fused_apply = hasattr(backend, 'apply_multi') and bool(o['fused_apply'])
@@ -225,11 +254,8 @@ class UpdateEngine:
         # (it stays set where the split optimizer launch never runs - truncate_grads, the end-of-step forms of phase_apply: those end in
         #  refresh_shadows(), which calls _gp_refresh)
         self._gp_split = self._gp_fuse and hasattr(backend, 'apply_multi_split') and self._fused_apply and dtype == torch.float16
-        self._gp_x_done = False          # this step's normalise launch wrote the value path's f32 input (_disc_inputs)
-        self._enc_z_ready = False
         self._prefetch = bool(o['prefetch'])
         self._par, self._par_set, self._last_par, self._fenced = 0, False, None, False
-        self._stats_exchanged = False    # this step's partial statistics were exchanged inside the un-chained heads (phase_stats)
         sp = o['side_priority']
         if sp is None:
             # measured on MI355X, config 2, with the main stream high (agents: main_stream_priority): the policy's second stream
@@ -241,7 +267,7 @@ class UpdateEngine:
         self._side_prio = [int(x) for x in sp] if isinstance(sp, (list, tuple)) else [int(sp)] * 3      # critic, disc, gp streams
         self._gp_stream_obj = None
         self._xs = False                 # this step runs the cross-step schedule (decided per step in step())
-        self._disc_fwd_out = self._gp_value_done = self._pre_done = None
+        self._st = _StepState()          # everything else the phases of a step hand each other
         self._apply_wide = bool(o['apply_wide'])
         self._apply_desc = self._apply_items = None
         self.force_dist = bool(cfg.get('force_dist', False))   # exercise the collectives with a 1-rank group
@@ -252,9 +278,6 @@ class UpdateEngine:
         self.dp_grad_dtype = cfg.get('dp_grad_dtype', 'f32')
         assert self.dp_grad_dtype in ('f32', 'bf16'), self.dp_grad_dtype
         self._xbuf = {}
-        self._disc_acc_mark = None
-        self._merged_stats = False       # this step exchanges [amp sums | obs sums | mask sum] as ONE collective (phase_stats)
-        self._acc_in_bucket = False      # ... and the loss partial sums inside the policy bucket's exchange (_finish_branch)
         self._refresh_desc = None
         self._mb_desc = None
         self._mb_desc_key = None
@@ -752,6 +775,12 @@ class UpdateEngine:
                 p = chain[l - 1]
                 self._dgrad(d, dZ[l], dZ[l - 1], rows, H[l - 1], p.act)
 
+    def _head_backward(self, head, d_out, h_top, chain, X0, H, dZ, rows):
+        """Backward of a head and the chain under it: d_out holds d loss / d (head output), h_top the chain's last activation."""
+        self._wgrad(head, d_out, h_top, rows)
+        self._dgrad(head, d_out, dZ[-1], rows, H[-1], chain[-1].act)
+        self._bwd_chain(chain, X0, H, dZ, rows)
+
     # ------------------------------------------------------------------ one optimisation step
     def gather_minibatch(self, ds, idx, remap, part=0):
         """All small per-row fields of the minibatch (learning/amp_datasets.py:21-22) in one launch - including the two
@@ -832,7 +861,7 @@ class UpdateEngine:
             self._par_set, self._fenced = False, False
         self.phase_stats(ds, idx, remap, amp_streams, advance=apply, new_z=new_z)
         self._allreduce_stats()
-        self._lr_live = apply          # (calc_gradients-style calls without the optimizer step leave the learning rate alone)
+        self._st.lr_live = apply       # (calc_gradients-style calls without the optimizer step leave the learning rate alone)
         self.phase_main(ds, idx, remap, amp_streams, new_z, inline_apply=inline)
         if inline:
             self.phase_finish()
@@ -856,17 +885,15 @@ class UpdateEngine:
                               z2=self.Zs[M:])
 
     def phase_stats(self, ds, idx, remap, amp_streams=None, advance=True, new_z=None):
-        be, c, M, AMB = self.be, self.cfg, self.M, self.AMB
-        self._disc_fwd_out = None
-        self._stats_exchanged = False
+        st = self._st = _StepState()
+        be, c, M = self.be, self.cfg, self.M
         pf = self._xs and self._prefetch and len(self._Xa2) == 2
         # Sharded data parallel under the cross-step schedule: ONE statistics collective per step.  The policy prologue (critic's
         # stream) forms the observation sums and the mask sum, the discriminator's head (its own stream) the amp sums; the head waits
         # for the prologue's mark, exchanges the whole buffer [amp sums x3 | obs sums | mask sum] and the prologue waits for that -
         # every running statistic stays on the stream that owns it (round 5: three small collectives from three streams, which the
         # process group's single stream serialised anyway).
-        merged = self._merged_stats = bool(pf and self._dist_shard() and self.has_disc and self.masked)
-        pre_a = None
+        merged = st.merged_stats = bool(pf and self._dist_shard() and self.has_disc and self.masked)
         if merged:
             self._build_apply_desc()
             with self._Branch(self, self._side(0), nowait=True):
@@ -875,8 +902,7 @@ class UpdateEngine:
                 be.reduce_sum(self.mb['rand_action_mask'], M, False, self.stats_flat, self.stats_flat.numel() - 1)
                 if c.get('normalize_input', True):
                     be.rms_moments(ds['obs'], self.obs, idx, remap, M, self.obs_state, self.obs_sums)
-                pre_a = self._mark()
-        self._stats_mark_a, self._stats_mark_b = pre_a, None
+                st.stats_mark_a = self._mark()
         if self._xs:
             # Cross-step schedule: the head of the discriminator branch goes FIRST into the step's launch sequence and waits
             # for nothing on the main stream.  On its own stream it follows the branch's optimizer step of the previous
@@ -890,48 +916,37 @@ class UpdateEngine:
                 be.zero_(self.grads[lo:hi])
                 if not merged:                   # (merged: the prologue's begin_step zeroed the whole statistics buffer)
                     be.zero_(self.amp_sums)
-                self._disc_fwd_out = self._disc_forward(amp_streams, ds)
-        pre = None
+                st.disc_fwd_out = self._disc_forward(amp_streams, ds)
         if pf:
             # The weight-independent prologue, un-chained like the discriminator's head: on the critic's stream it follows that
             # branch's backward of the previous step (whose loss head was the last reader of the minibatch fields) and runs
             # under the previous step's policy tail.  It zeroes its own partial sums and advances the diversity stream itself
             # (one begin_step launch without optimizer state); the accumulators are not touched before the step's real
             # begin_step below (the mask sum follows it).
-            with self._Branch(self, self._side(0), nowait=True) as pre:
+            with self._Branch(self, self._side(0), nowait=True) as st.pre_done:
                 if merged:
-                    be.wait(self._stats_mark_b)          # the one statistics collective of the step (discriminator's head) is through
+                    be.wait(st.stats_mark_b)             # the one statistics collective of the step (discriminator's head) is through
                 else:
                     be.begin_step(None, None, zero2=self.obs_sums, rng_bump=self.div_rng if self.div_on else None)
-                if c.get('normalize_input', True):
-                    if not merged:
-                        be.rms_moments(ds['obs'], self.obs, idx, remap, M, self.obs_state, self.obs_sums)
-                        if self._dist_shard():
-                            self._ar(self.obs_sums)          # (sharded data parallel: the ranks' partial sums, on this stream)
-                    be.rms_finalize(self.obs_state, self.obs, self.obs_sums, self.Mg if self.shard else self.M, 1, self.obs_mean,
-                                    self.obs_std)
-                else:
-                    self._identity_stats(self.obs_mean, self.obs_std)
-                outs = [self.Xa[:M], self.Xc]
-                if self.div_on:
-                    outs.append(self.Xa[M:])
-                be.rms_normalize(ds['obs'], self.obs, idx, remap, M, self.obs_mean[0], self.obs_std[0], outs)
+                if c.get('normalize_input', True) and not merged:
+                    be.rms_moments(ds['obs'], self.obs, idx, remap, M, self.obs_state, self.obs_sums)
+                    if self._dist_shard():
+                        self._ar(self.obs_sums)              # (sharded data parallel: the ranks' partial sums, on this stream)
+                self._obs_inputs(ds, idx, remap)
                 self.gather_minibatch(ds, idx, remap, part=2)
                 if self.div_on:
                     self._draw_new_latents(new_z)
-                self._lat_ready = self._mark()        # everything the style MLP / the first actor layer read is in place
+                st.lat_ready = self._mark()           # everything the style MLP / the first actor layer read is in place
                 if not merged:
                     self.gather_minibatch(ds, idx, remap, part=1)
-        self._pre_done = pre
-        if pf:
             # begin_step leaves the main stream: nothing in front of the loss heads reads the accumulators or the optimizer
             # state, so the launch (after the previous step's last kernel: mark on the main stream) and what follows it - zeroing
             # the policy's gradient bucket, the mask sum - go to the critic's stream; the main stream opens with the style MLP
             tail = self._mark()
             plo, phi = self._apply_groups['policy'][2:]
-            with self._Branch(self, self._side(0), tail) as prep:           # (same stream as the prologue above: after it)
+            with self._Branch(self, self._side(0), tail) as st.prep:         # (same stream as the prologue above: after it)
                 be.begin_step(self.opt_state if advance else None, self.acc, zero2=None, rng_bump=None)
-                self._early_fork = self._mark()
+                st.early_fork = self._mark()
                 be.zero_(self.grads[plo:phi])
                 if merged:                               # (the global mask sum came with the statistics collective)
                     be.copy_(self.acc[L.ACC_MASK_SUM:L.ACC_MASK_SUM + 1], self.stats_flat[-1:])
@@ -939,16 +954,12 @@ class UpdateEngine:
                     be.reduce_sum(self.mb['rand_action_mask'], M, False, self.acc, L.ACC_MASK_SUM)
                     if self._dist_shard():
                         self._ar(self.acc[L.ACC_MASK_SUM:L.ACC_MASK_SUM + 1])
-            self._fill_done = None
-            self._prep = prep
-            self._stats_exchanged = True
+            st.stats_exchanged = True
             return
         # one launch: Adam step counter / bias corrections (advance=False - calc_gradients-style calls - leaves them),
         # loss accumulators and per-step partial statistics zeroed, position of the diversity-latent stream advanced
         be.begin_step(self.opt_state if advance else None, self.acc,
-                      zero2=None if pf else (self.obs_sums if self._xs else self.stats_flat),
-                      rng_bump=self.div_rng if (self.div_on and not pf) else None)
-        self._prep = None
+                      zero2=self.obs_sums if self._xs else self.stats_flat, rng_bump=self.div_rng if self.div_on else None)
         if self._short_prologue and self._amp_stats_in_branch():
             # Short prologue (single GPU, streams): the actor chain - the critical path - keeps only the observation chain
             # (moments -> finalise -> normalise) in front of it on the main stream.  The latent copies and the diversity draw
@@ -957,24 +968,23 @@ class UpdateEngine:
             m0 = self._mark()
             with self._Branch(self, self._side(1), m0):
                 be.zero_(self.grads[:self.n_train])
-                self._fill_done = self._mark()
-            self._early_fork = self._fill_done if self.has_disc else None
-            with self._Branch(self, self._side(0), m0) as prep:
+                st.fill_done = self._mark()
+            st.early_fork = st.fill_done if self.has_disc else None
+            with self._Branch(self, self._side(0), m0) as st.prep:
                 self.gather_minibatch(ds, idx, remap, part=2)
                 if self.div_on:
                     self._draw_new_latents(new_z)
-                self._lat_ready = self._mark()
+                st.lat_ready = self._mark()
                 self.gather_minibatch(ds, idx, remap, part=1)
                 if self.masked:
                     be.reduce_sum(self.mb['rand_action_mask'], M, False, self.acc, L.ACC_MASK_SUM)
-            self._prep = prep
             if c.get('normalize_input', True):
                 be.rms_moments(ds['obs'], self.obs, idx, remap, M, self.obs_state, self.obs_sums)
             return
         be.zero_(self.grads[:self.n_train])
         # the discriminator branch needs nothing of what follows here (minibatch fields, observation moments): with its own
         # stream and no exchange between the phases it may start as soon as the accumulators and gradients are zeroed
-        self._early_fork = self._mark() if (self.has_disc and self._amp_stats_in_branch() and self._disc_early) else None
+        st.early_fork = self._mark() if (self.has_disc and self._amp_stats_in_branch() and self._disc_early) else None
         self.gather_minibatch(ds, idx, remap)
         if self.masked:
             be.reduce_sum(self.mb['rand_action_mask'], M, False, self.acc, L.ACC_MASK_SUM)
@@ -994,13 +1004,43 @@ class UpdateEngine:
     def _dist_shard(self):
         return self._dist_on() and self.shard
 
+    @property
+    def _m_den(self):
+        """Denominator of the minibatch means: the GLOBAL row count of a sharded step, this rank's own otherwise."""
+        return self.Mg if self.shard else self.M
+
+    @property
+    def _amb_den(self):
+        return self.AMBg if self.shard else self.AMB
+
+    def _obs_inputs(self, ds, idx, remap):
+        """Observation sums -> running statistics -> the normalised inputs of the first actor / critic layers."""
+        be, M = self.be, self.M
+        if self.cfg.get('normalize_input', True):
+            be.rms_finalize(self.obs_state, self.obs, self.obs_sums, self._m_den, 1, self.obs_mean, self.obs_std)
+        else:
+            self._identity_stats(self.obs_mean, self.obs_std)
+        outs = [self.Xa[:M], self.Xc]
+        if self.div_on:
+            outs.append(self.Xa[M:])
+        be.rms_normalize(ds['obs'], self.obs, idx, remap, M, self.obs_mean[0], self.obs_std[0], outs)
+
+    def _gather_enc_z(self, ds, amp_streams):
+        """enc_latents = ase_latents[0:amp_minibatch] (learning/ase_agent.py:247): a row gather that needs nothing but the step's
+        indices - once per step, with the branch's head where that has the dataset, else in front of the encoder's loss head."""
+        if not self._st.enc_z_ready:
+            _, sidx, srm = amp_streams[0]
+            zsrc = ds['ase_latents'].view(ds['ase_latents'].shape[0], -1)
+            self.be.gather_rows(zsrc, self.z, sidx, srm, self.AMB, self.enc_z)
+            self._st.enc_z_ready = True
+
     def _exchange_amp_sums(self):
-        if self._merged_stats:
+        if self._st.merged_stats:
             # the step's ONE statistics collective: behind the policy prologue's sums (mark A), in front of everything that reads a
             # global statistic on either stream (mark B)
-            self.be.wait(self._stats_mark_a)
+            self.be.wait(self._st.stats_mark_a)
             self._ar(self.stats_flat)
-            self._stats_mark_b = self._mark()
+            self._st.stats_mark_b = self._mark()
         elif self._dist_shard():
             self._ar(self.amp_sums_flat)
 
@@ -1086,12 +1126,12 @@ class UpdateEngine:
             if self._dist_on():
                 # the LAST bucket of a sharded step (the policy's, on the main stream) carries the loss partial sums of the whole step
                 # with it: one collective less (round 5: a 100-byte all-reduce of its own in phase_finish).  The discriminator branch's
-                # contributions to them are complete at its mark (_disc_acc_mark), long before this point.
+                # contributions to them are complete at its mark (disc_acc_mark), long before this point.
                 with_acc = bool(last and self.shard and self.dp_grad_dtype == 'f32')
-                if with_acc and self._disc_acc_mark is not None:
-                    self.be.wait(self._disc_acc_mark)
+                if with_acc and self._st.disc_acc_mark is not None:
+                    self.be.wait(self._st.disc_acc_mark)
                 self._exchange_bucket(group, lo, hi, with_acc)
-                self._acc_in_bucket = with_acc
+                self._st.acc_in_bucket = with_acc
                 if not self.shard:
                     self._host(lambda: self.grads[lo:hi].mul_(1.0 / self.R))
             if self.dyn_scale:
@@ -1114,31 +1154,22 @@ class UpdateEngine:
     def _disc_inputs(self, amp_streams, ds=None):
         """First half of the branch's head: statistics and normalised inputs (HBM-bound streams) + the fork of the penalty's
         value path (gp_f32 modes)."""
-        be, c, AMB = self.be, self.cfg, self.AMB
-        Rd = 3 * AMB
-        norm_amp = self.has_disc and c.get('normalize_amp_input', True)
-        amb_den = self.AMBg if self.shard else self.AMB
+        be, c, AMB, st = self.be, self.cfg, self.AMB, self._st
         if self._amp_stats_in_branch():
             self._amp_moments(amp_streams)
             self._exchange_amp_sums()
-        if norm_amp:
-            be.rms_finalize(self.amp_state, self.amp, self.amp_sums, amb_den, 3, self.amp_mean, self.amp_std)
+        if self.has_disc and c.get('normalize_amp_input', True):
+            be.rms_finalize(self.amp_state, self.amp, self.amp_sums, self._amb_den, 3, self.amp_mean, self.amp_std)
         else:
             self._identity_stats(self.amp_mean, self.amp_std)
         # (gp_fuse: the normalise launch below writes the value path's f32 input too - its fork is marked behind that launch)
         x_twin = self._gp_fuse and hasattr(be, 'rms_normalize_multi_twin') and self.amp % 4 == 0 and \
             all(src.stride(0) % 4 == 0 for src, _, _ in amp_streams)
         gp_fork = self._mark() if (self.gp32 and self._gp_side and not x_twin) else None
-        self._enc_z_ready = False
-        if self.has_enc and ds is not None:
-            # enc_latents = ase_latents[0:amp_minibatch] (learning/ase_agent.py:247): a row gather that needs nothing but the
-            # step's indices - with the un-chained head instead of between the discriminator's loss heads
-            src, sidx, srm = amp_streams[0]
-            zsrc = ds['ase_latents'].view(ds['ase_latents'].shape[0], -1)
-            be.gather_rows(zsrc, self.z, sidx, srm, AMB, self.enc_z)
-            self._enc_z_ready = True
+        if self.has_enc and ds is not None:      # (with the un-chained head instead of between the discriminator's loss heads)
+            self._gather_enc_z(ds, amp_streams)
         xd = [self.Xd[s * AMB:(s + 1) * AMB] for s in range(3)]
-        self._gp_x_done = x_twin
+        st.gp_x_done = x_twin
         if x_twin:
             be.rms_normalize_multi_twin(amp_streams, self.amp, AMB, [self.amp_mean[s] for s in range(3)],
                                         [self.amp_std[s] for s in range(3)], xd, [None, None, self._gp32.X])
@@ -1149,15 +1180,13 @@ class UpdateEngine:
         else:                          # rows that are not whole 16-byte chunks: one launch per stream
             for s, (src, sidx, srm) in enumerate(amp_streams):
                 be.rms_normalize(src, self.amp, sidx, srm, AMB, self.amp_mean[s], self.amp_std[s], [xd[s]])
-        self._gp_value_done = None
         if self.gp32:
             gp_coef = c['disc_coef'] * c['disc_grad_penalty']
             if gp_fork is not None:
                 # the penalty's value path beside the loss rows' forward, on its own stream: it follows the statistics above
                 # (and, through them, the branch's previous optimizer step) and is joined before the conversion launch
-                with self._Branch(self, self._gp_stream(), gp_fork) as br:
+                with self._Branch(self, self._gp_stream(), gp_fork) as st.gp_value_done:
                     self._gp_value(amp_streams, gp_coef)
-                self._gp_value_done = br
             else:
                 self._gp_value(amp_streams, gp_coef)
 
@@ -1184,35 +1213,23 @@ class UpdateEngine:
 
     # ---- phase B: normalise, forward, loss heads, backward -----------------------------------------
     def phase_main(self, ds, idx, remap, amp_streams=None, new_z=None, inline_apply=False):
-        be, c, M, AMB = self.be, self.cfg, self.M, self.AMB
-        norm_in = c.get('normalize_input', True)
-        norm_amp = self.has_disc and c.get('normalize_amp_input', True)
-        Ra = self.Ra
+        be, c, M, AMB, st = self.be, self.cfg, self.M, self.AMB, self._st
+        Ra, Rd = self.Ra, 3 * AMB
         if inline_apply:
             self._build_apply_desc()
-        fork0 = self._early_fork if self._early_fork is not None else self._mark()   # (nothing of the observation prologue)
-        disc_early = self.has_disc and self._early_fork is not None and self._disc_early
-        amb_den = self.AMBg if self.shard else self.AMB
-        Rd = 3 * AMB
+        fork0 = st.early_fork if st.early_fork is not None else self._mark()   # (nothing of the observation prologue)
+        disc_early = self.has_disc and st.early_fork is not None and self._disc_early
 
-        if self._disc_fwd_out is not None:           # cross-step schedule: submitted at the top of phase_stats
-            hd, he = self._disc_fwd_out
+        if st.disc_fwd_out is not None:              # cross-step schedule: submitted at the top of phase_stats
+            hd, he = st.disc_fwd_out
         elif disc_early:
             with self._Branch(self, self._side(1), fork0):
                 hd, he = self._disc_forward(amp_streams)
-        if self._pre_done is None:            # (prefetch: statistics + normalised inputs came with the un-chained prologue)
-            if norm_in:
-                be.rms_finalize(self.obs_state, self.obs, self.obs_sums, self.Mg if self.shard else self.M, 1, self.obs_mean,
-                                self.obs_std)
-            else:
-                self._identity_stats(self.obs_mean, self.obs_std)
-            outs = [self.Xa[:M], self.Xc]
-            if self.div_on:
-                outs.append(self.Xa[M:])
-            be.rms_normalize(ds['obs'], self.obs, idx, remap, M, self.obs_mean[0], self.obs_std[0], outs)
+        if st.pre_done is None:               # (prefetch: statistics + normalised inputs came with the un-chained prologue)
+            self._obs_inputs(ds, idx, remap)
         fork1 = self._mark()                 # critic: observations normalised, latents in place (gather_minibatch)
-        if self._prep is not None:
-            be.wait(self._lat_ready)         # latent copies + diversity draw of the short prologue (critic's stream)
+        if st.prep is not None:
+            be.wait(st.lat_ready)            # latent copies + diversity draw of the short prologue (critic's stream)
         elif self.div_on:
             self._draw_new_latents(new_z)
 
@@ -1236,20 +1253,17 @@ class UpdateEngine:
             with self._Branch(self, self._side(1), fork0) as br_disc:
                 if not disc_early:
                     hd, he = self._disc_forward(amp_streams)
-                be.disc_head(self.HD, self.dHD, self.disc_head.gb[0], self.acc, AMB, amb_den, c['disc_coef'],
+                be.disc_head(self.HD, self.dHD, self.disc_head.gb[0], self.acc, AMB, self._amb_den, c['disc_coef'],
                              grad_scale=self.gs, dyn=self._dS)
                 if self.has_enc:
-                    src, sidx, srm = amp_streams[0]   # enc_latents = ase_latents[0:amp_minibatch] (learning/ase_agent.py:247)
-                    zsrc = ds['ase_latents'].view(ds['ase_latents'].shape[0], -1)
-                    if not self._enc_z_ready:
-                        be.gather_rows(zsrc, self.z, sidx, srm, AMB, self.enc_z)
+                    self._gather_enc_z(ds, amp_streams)
                     if self.enc_sep:
-                        be.enc_head(self.E, self.enc_z, self.dE, self.enc_head.gb[0], None, self.acc, AMB, amb_den,
+                        be.enc_head(self.E, self.enc_z, self.dE, self.enc_head.gb[0], None, self.acc, AMB, self._amb_den,
                                     self.z, c['enc_coef'], grad_scale=self.gs, dyn=self._dS)
                     else:
                         off = self.disc_head.parts[1][2]
                         be.enc_head(self.HD[:AMB, off:], self.enc_z, self.dHD[:AMB, off:], self.disc_head.gb[1], None,
-                                    self.acc, AMB, amb_den, self.z, c['enc_coef'], grad_scale=self.gs, dyn=self._dS)
+                                    self.acc, AMB, self._amb_den, self.z, c['enc_coef'], grad_scale=self.gs, dyn=self._dS)
                 if self.enc_gp:
                     self._enc_grad_penalty(he if self.enc_chain else hd[:AMB])
                 self._wgrad(self.disc_head, self.dHD, hd, Rd)
@@ -1257,19 +1271,16 @@ class UpdateEngine:
                 self._dgrad(self.disc_head, self.dHD, self.dZd[-1], Rd, self.Hd[-1], last.act)
                 self._disc_backward()
                 if self.enc_chain:
-                    self._wgrad(self.enc_head, self.dE, he, AMB)
-                    last = self.enc_chain[-1]
-                    self._dgrad(self.enc_head, self.dE, self.dZe[-1], AMB, self.He[-1], last.act)
-                    self._bwd_chain(self.enc_chain, self.Xd[:AMB], self.He, self.dZe, AMB)
+                    self._head_backward(self.enc_head, self.dE, he, self.enc_chain, self.Xd[:AMB], self.He, self.dZe, AMB)
                 # (every contribution of this branch to the loss partial sums - logit losses, penalties, encoder loss - is launched)
-                self._disc_acc_mark = self._mark()
+                st.disc_acc_mark = self._mark()
                 self._finish_branch('disc', inline_apply)
             self._tn_queue = tnq
         self._join_branch(br_critic)
-        if self._prep is not None:
-            self._join_branch(self._prep)      # (same stream as the critic branch: already implied; kept explicit)
-            if self._fill_done is not None:
-                be.wait(self._fill_done)       # gradients zeroed (discriminator's stream) before the loss head adds to them
+        if st.prep is not None:
+            self._join_branch(st.prep)         # (same stream as the critic branch: already implied; kept explicit)
+            if st.fill_done is not None:
+                be.wait(st.fill_done)          # gradients zeroed (discriminator's stream) before the loss head adds to them
 
         # -- PPO loss head (value + gradient w.r.t. mu / value + head bias gradients)
         ls_kw = {}
@@ -1280,7 +1291,7 @@ class UpdateEngine:
         elif self.sigma_mode == 'vector':
             ls_kw = dict(ls_mode=L.LS_VECTOR, db_logstd=self.glogstd, entropy_coef=c.get('entropy_coef', 0.0))
         be.ppo_head(self.MU, self.V, self.mb, self.new_z if self.div_on else None, self._logstd_of(self.MU), self.dMU, self.dV,
-                    self.mu_head.gb[0], self.value_head.gb[0], self.acc, M, self.Mg if self.shard else self.M, self.act, self.z,
+                    self.mu_head.gb[0], self.value_head.gb[0], self.acc, M, self._m_den, self.act, self.z,
                     self.masked, self.div_on, self.mu_tanh, c['clip_value'], c['e_clip'], c['critic_coef'],
                     self.bounds_coef, c.get('amp_diversity_bonus', 0.0), c.get('amp_diversity_tar', 0.0), grad_scale=self.gs, dyn=self._dS,
                     **ls_kw)
@@ -1288,16 +1299,10 @@ class UpdateEngine:
 
         # -- actor backward on the main stream, critic backward beside it.  The weight gradients of both and of the style MLP
         # (one parameter bucket) are queued in that order and go out as ONE grouped launch, the last matrix kernel of the step.
-        self._wgrad(self.mu_head, self.dMU, ha, Ra)
-        last = self.actor[-1]
-        self._dgrad(self.mu_head, self.dMU, self.dZa[-1], Ra, self.Ha[-1], last.act)
-        self._bwd_chain(self.actor, self.Xa, self.Ha, self.dZa, Ra)
+        self._head_backward(self.mu_head, self.dMU, ha, self.actor, self.Xa, self.Ha, self.dZa, Ra)
         tn_actor, self._tn_queue = self._tn_queue, []
         with self._Branch(self, self._side(0), fork2) as br_cb:
-            self._wgrad(self.value_head, self.dV, hc, M)
-            last = self.critic[-1]
-            self._dgrad(self.value_head, self.dV, self.dZc[-1], M, self.Hc[-1], last.act)
-            self._bwd_chain(self.critic, self.Xc, self.Hc, self.dZc, M)
+            self._head_backward(self.value_head, self.dV, hc, self.critic, self.Xc, self.Hc, self.dZc, M)
             tn_actor = tn_actor + self._tn_queue
             self._tn_queue = []
         if self.style:
@@ -1319,14 +1324,16 @@ class UpdateEngine:
     def phase_finish(self):
         """After the inline per-branch optimizer steps: loss partial sums over the ranks (weight-norm slots are local),
         reported scalars."""
-        c = self.cfg
-        if self._dist_on() and self.shard and not self._acc_in_bucket:
+        if self._dist_shard() and not self._st.acc_in_bucket:
             self._ar(self.acc[1:L.ACC_LOGIT_W2])
-        self._acc_in_bucket = False
+        self._finalize(self._st.lr_live)
+
+    def _finalize(self, apply):
+        """The step's reported scalars (+ apply: the adaptive schedule's learning rate for the next step) in one launch."""
         self._average_kl()
-        self.be.finalize_scalars(self.acc, self.res, self.Mg if self.shard else self.M, self.AMBg if self.shard else self.AMB,
-                                 self.masked, self.has_disc, self.has_enc, self.div_on, c,
-                                 opt_state=self.opt_state if (self.adaptive_lr and self._lr_live) else None, kl_threshold=self.kl_threshold)
+        self.be.finalize_scalars(self.acc, self.res, self._m_den, self._amb_den, self.masked, self.has_disc, self.has_enc,
+                                 self.div_on, self.cfg, opt_state=self.opt_state if (self.adaptive_lr and apply) else None,
+                                 kl_threshold=self.kl_threshold)
 
     # ---- phase C (end-of-step form): weight-only loss terms, optimizer, shadows, reported scalars ------
     def phase_apply(self, apply=True):
@@ -1355,12 +1362,8 @@ class UpdateEngine:
                 # GradScaler (learning/ase_agent.py:271-288): found_inf over the scaled backward (every half buffer a launch of the
                 # step wrote + the f32 gradient), one flag for all ranks, then the decision - a found overflow zeroes the gradient
                 # and the optimizer launch below runs the identity step (weights, moments, step counter stay what they are)
-                g = self.grads[:self.n_train]
                 self._dyn_check('all', 0, self.n_train)
-                if self._dist_on():
-                    be.scaler_fold(self.scaler, self.scale_tab)
-                    self._ar(self.scaler[:1])
-                be.scaler_step(self.scaler, self.opt_state, self.opt_eff, g, scale_tab=self.scale_tab)
+                self._scaler_step()
             elif self.dyn_scale:
                 # a step without the optimizer (calc_gradients-style calls): GradScaler sees nothing of it - what its launches
                 # reported is dropped
@@ -1373,10 +1376,7 @@ class UpdateEngine:
                 be.adam(self.params[:self.n_train], self.grads[:self.n_train], self.adam_m[:self.n_train],
                         self.adam_v[:self.n_train], self.opt_eff if self.dyn_scale else self.opt_state)
                 self.refresh_shadows()
-        self._average_kl()
-        be.finalize_scalars(self.acc, self.res, self.Mg if self.shard else self.M, self.AMBg if self.shard else self.AMB,
-                            self.masked, self.has_disc, self.has_enc, self.div_on, c,
-                            opt_state=self.opt_state if (self.adaptive_lr and apply) else None, kl_threshold=self.kl_threshold)
+        self._finalize(apply)
 
     # ---- dynamic loss scale (cfg loss_scale = 'dynamic') ---------------------------------------------------------------
     def _scaler_bufs(self):
@@ -1431,16 +1431,19 @@ class UpdateEngine:
         submitted on the discriminator branch's stream - behind that branch's tail, waiting for the main stream's position - so
         that the head of the NEXT step's discriminator branch (cross-step schedule: un-chained, same stream) follows the
         optimizer step by stream order; the main stream joins it."""
-        be = self.be
-        g = self.grads[:self.n_train]
         side = self._side(1) if (self.multi_stream and self.has_disc) else None
         with self._Branch(self, side) as br:
-            if self._dist_on():
-                be.scaler_fold(self.scaler, self.scale_tab)       # the producers' reports -> one number, SUM over the ranks
-                self._ar(self.scaler[:1])
-            be.scaler_step(self.scaler, self.opt_state, self.opt_eff, g, scale_tab=self.scale_tab)
+            self._scaler_step()
             self._apply(self.opt_eff)
         self._join_branch(br)
+
+    def _scaler_step(self):
+        """GradScaler.step + update behind the step's checks: ONE found_inf for all ranks, then the decision (into opt_eff)."""
+        be = self.be
+        if self._dist_on():
+            be.scaler_fold(self.scaler, self.scale_tab)           # the producers' reports -> one number, SUM over the ranks
+            self._ar(self.scaler[:1])
+        be.scaler_step(self.scaler, self.opt_state, self.opt_eff, self.grads[:self.n_train], scale_tab=self.scale_tab)
 
     @property
     def _dS(self):
@@ -1515,7 +1518,6 @@ class UpdateEngine:
         chain = self.enc_chain if sep else self.disc
         head = self.enc_head if sep else self.disc_head
         H = self.He if sep else [h[:AMB] for h in self.Hd]
-        X0 = self.Xd[:AMB]
         for d in chain:
             assert d.act == L.ACT_RELU, "analytic gradient penalty needs ReLU encoder layers"
         if sep:
@@ -1523,7 +1525,7 @@ class UpdateEngine:
         else:
             off = self.disc_head.parts[1][2]
             e, d_e, db = self.HD[:AMB, off:], self.dHD[:AMB, off:], self.disc_head.gb[1]
-        cg = c['enc_coef'] * c['enc_grad_penalty'] * 2.0 / (self.AMBg if self.shard else self.AMB)
+        cg = c['enc_coef'] * c['enc_grad_penalty'] * 2.0 / self._amb_den
         s = math.sqrt(cg)
         nl = len(chain)
         be.enc_gp_seed(e, self.enc_z, self.Ue[:, off:], AMB, self.z, scale=s)
@@ -1607,22 +1609,34 @@ class UpdateEngine:
         self._nt(self.Gp[0], d0.Wts, self.G0, AMB, d0.k_pad, d0.n_pad, alpha=Sr / Sc, alpha_dev=self._dS)        # Sr s * g_0
         be.sqnorm(self.G0, AMB, d0.k_pad, self.acc, L.ACC_GP, scale=1.0 / (cg * Sr * Sr), dyn=self._dI2)
         # backward of the chain (values scaled by s; see the docstring): dJ/dU_l, masked by the demo rows' ReLU masks
-        aux, mode = self._aux(self.Hd[0][2 * AMB:], L.AUX_RELU_MASK)
+        self._gp_chain_backward(lambda l: self._aux(self.Hd[l][2 * AMB:], L.AUX_RELU_MASK), s / Sr)
+        for l in range(nl):
+            self._wgrad_stacked(l)
+
+    def _gp_chain_backward(self, mask, top_scale):
+        """Backward of the penalty chain, shared by the 16-bit and the gp_f32 form: dJ/dU_0 = m_0 * (s g_0 @ W_1^T), dJ/dU_l =
+        m_l * (dJ/dU_{l-1} @ W_{l+1}^T) into the 4th row block of Hd4.  mask(l) -> (aux, aux mode): the demo rows' ReLU mask of
+        layer l.  The top launch is kept in f32 at true scale (top_scale = s / the scale its operand carries): only its column sums
+        are used, the penalty's gradient w.r.t. the logit weights."""
+        AMB, nl, d0 = self.AMB, len(self.disc), self.disc[0]
+        aux, mode = mask(0)
         self._nt(self.G0, d0.Ws, self.dGp[0], AMB, d0.n_pad, d0.k_pad, aux=aux, aux_mode=mode)
         for l in range(1, nl):
             d = self.disc[l]
             last = l == nl - 1
-            aux, mode = self._aux(self.Hd[l][2 * AMB:], L.AUX_RELU_MASK)
+            aux, mode = mask(l)
             self._nt(self.dGp[l - 1], d.Ws, self.GpTop if last else self.dGp[l], AMB, d.n_pad, d.k_pad, aux=aux,
-                       aux_mode=mode, alpha=s / Sr if last else 1.0, alpha_dev=self._dI if last else None)
-            if last:      # the penalty's gradient w.r.t. the logit weights: column sums of the top launch (f32, true scale)
-                be.colsum(self.GpTop, AMB, d.N, self.disc_head.gW[0].view(-1))
-        # weight (+ bias) gradients: one launch per layer over the stacked rows
-        for l in range(nl):
-            d = self.disc[l]
-            X = self.Xd4 if l == 0 else self.Hd4[l - 1]
-            self._tn(self.dZd4[l], X, d.gW[0], 4 * AMB, d.n_pad, d.k_pad, d.N, d.K, d.split_src, d.split_dst,
-                     gbias=d.gb[0], bias_rows=Rd)
+                     aux_mode=mode, alpha=top_scale if last else 1.0, alpha_dev=self._dI if last else None)
+            if last:
+                self.be.colsum(self.GpTop, AMB, d.N, self.disc_head.gW[0].view(-1))
+
+    def _wgrad_stacked(self, l):
+        """Weight (+ bias) gradient of discriminator layer l over the stacked rows, ONE launch:
+        gW_l += [dZ_l ; s g_l]^T [H_{l-1} ; dJ/dU_{l-1}], the bias gradient from the 3 AMB loss rows alone."""
+        d, AMB = self.disc[l], self.AMB
+        X = self.Xd4 if l == 0 else self.Hd4[l - 1]
+        self._tn(self.dZd4[l], X, d.gW[0], 4 * AMB, d.n_pad, d.k_pad, d.N, d.K, d.split_src, d.split_dst,
+                 gbias=d.gb[0], bias_rows=3 * AMB)
 
     def _gp_value(self, amp_streams, gp_coef):
         """VALUE path of the gradient penalty in a gp_f32 engine (see _gp_f32): the demo rows normalised into an f32 input,
@@ -1633,7 +1647,7 @@ class UpdateEngine:
         nl, S = len(self.disc), self.gs
         s = math.sqrt(gp_coef * 2.0 / self.AMBg)
         bits = L.AUX_RELU_BITS
-        if not self._gp_x_done:     # (gp_fuse: the branch's normalise launch wrote g.X as its f32 twin)
+        if not self._st.gp_x_done:  # (gp_fuse: the branch's normalise launch wrote g.X as its f32 twin)
             src, sidx, srm = amp_streams[2]        # the demo stream once more, into the f32 input of the penalty path
             be.rms_normalize(src, self.amp, sidx, srm, AMB, self.amp_mean[2], self.amp_std[2], [g.X])
         # gp_f32 = 'x3': the six f32-storage launches multiply as three 16-bit MFMAs per product on hi / lo splits instead of the
@@ -1698,15 +1712,12 @@ class UpdateEngine:
         conversion launch writes s g_l and S s g_0 into the 4th row block of the discriminator's buffers - and the penalty's
         BACKWARD (dJ/dU_l through the exact masks, the logit-weight term, the stacked weight-gradient problems) runs as in
         _disc_backward; the loss rows' data-gradient launches shrink to 3 AMB rows."""
-        be, AMB, g = self.be, self.AMB, self._gp32
-        Rd, nl, S = 3 * AMB, len(self.disc), self.gs
+        AMB, g, S, d0 = self.AMB, self._gp32, self.gs, self.disc[0]
         cg = gp_coef * 2.0 / self.AMBg
         s = math.sqrt(cg)
-        bits = L.AUX_RELU_BITS
-        d0 = self.disc[0]
-        if self._gp_value_done is not None:
-            self._join_branch(self._gp_value_done)
-            self._gp_value_done = None
+        if self._st.gp_value_done is not None:
+            self._join_branch(self._st.gp_value_done)
+            self._st.gp_value_done = None
         if self._gp_fuse:
             # the chain's last launch: S s g_0 straight into the 16-bit row block (never stored in f32) + the sum of its squares;
             # the 16-bit copies of s g_l were written by the launches that produced them (_gp_value)
@@ -1732,27 +1743,14 @@ class UpdateEngine:
 
     def _gp_backward(self, s):
         """Second half of _gp_f32: the loss rows' data gradients and the penalty's backward through the exact masks."""
-        be, AMB, g = self.be, self.AMB, self._gp32
-        Rd, nl, S = 3 * AMB, len(self.disc), self.gs
-        bits = L.AUX_RELU_BITS
-        d0 = self.disc[0]
+        g, nl = self._gp32, len(self.disc)
         # the loss rows' data-gradient chain (3 AMB rows)
         for l in range(nl - 1, 0, -1):
-            self._dgrad(self.disc[l], self.dZd[l], self.dZd[l - 1], Rd, self.Hd[l - 1], self.disc[l - 1].act)
+            self._dgrad(self.disc[l], self.dZd[l], self.dZd[l - 1], 3 * self.AMB, self.Hd[l - 1], self.disc[l - 1].act)
         # backward of the penalty chain (values carry s and the gradient scale S), through the EXACT masks
-        self._nt(self.G0, d0.Ws, self.dGp[0], AMB, d0.n_pad, d0.k_pad, aux=g.bits[0], aux_mode=bits)
-        for l in range(1, nl):
-            d = self.disc[l]
-            last = l == nl - 1
-            self._nt(self.dGp[l - 1], d.Ws, self.GpTop if last else self.dGp[l], AMB, d.n_pad, d.k_pad, aux=g.bits[l],
-                       aux_mode=bits, alpha=s / S if last else 1.0, alpha_dev=self._dI if last else None)
-            if last:
-                be.colsum(self.GpTop, AMB, d.N, self.disc_head.gW[0].view(-1))
+        self._gp_chain_backward(lambda l: (g.bits[l], L.AUX_RELU_BITS), s / self.gs)
         for l in range(nl):
-            d = self.disc[l]
-            X = self.Xd4 if l == 0 else self.Hd4[l - 1]
-            self._tn(self.dZd4[l], X, d.gW[0], 4 * AMB, d.n_pad, d.k_pad, d.N, d.K, d.split_src, d.split_dst,
-                     gbias=d.gb[0], bias_rows=Rd)
+            self._wgrad_stacked(l)
 
     def _disc_backward_curved(self, gp_coef):
         """Discriminator backward with the gradient penalty for activations with curvature (anything but ReLU; SURVEY 8 row
@@ -1766,8 +1764,8 @@ class UpdateEngine:
         (dZ_l) BEFORE that layer's data- and weight-gradient launches, so the penalty chain (which needs nothing of the loss
         backward) runs first here instead of riding on the discriminator's data-gradient launches.  Scales as in
         _disc_backward: chain values carry s = sqrt(2 c / AMB) and Sc, the r side s and Sr (Sc Sr = the gradient scale S)."""
-        be, c, AMB = self.be, self.cfg, self.AMB
-        Rd, nl, S = 3 * AMB, len(self.disc), self.gs
+        be, AMB = self.be, self.AMB
+        Rd, nl = 3 * AMB, len(self.disc)
         cg = gp_coef * 2.0 / self.AMBg
         s = math.sqrt(cg)
         demo = slice(2 * AMB, 3 * AMB)
@@ -1800,9 +1798,7 @@ class UpdateEngine:
         for l in range(nl - 1, -1, -1):
             d = self.disc[l]
             be.gp_second(self._twin(self.Hd[l][demo], d), self.Gp[l], self.dGp[l], self.dZd[l][demo], AMB, d.N, d.act)
-            X = self.Xd4 if l == 0 else self.Hd4[l - 1]
-            self._tn(self.dZd4[l], X, d.gW[0], 4 * AMB, d.n_pad, d.k_pad, d.N, d.K, d.split_src, d.split_dst,
-                     gbias=d.gb[0], bias_rows=Rd)
+            self._wgrad_stacked(l)
             if l > 0:
                 pl = self.disc[l - 1]
                 self._dgrad(d, self.dZd[l], self.dZd[l - 1], Rd, self.Hd[l - 1], pl.act)
@@ -1878,12 +1874,12 @@ class UpdateEngine:
         return self.R > 1 or self.force_dist
 
     def _allreduce_stats(self):
-        """Exchange of the step's partial statistics when it is NOT done inside the un-chained heads (_stats_exchanged): the
+        """Exchange of the step's partial statistics when it is NOT done inside the un-chained heads (stats_exchanged): the
         observation sums and the mask sum here; the amp block too unless the discriminator's head - which computes it on its own
         stream whenever streams exist - has exchanged it (_exchange_amp_sums)."""
-        if self._dist_shard() and not self._stats_exchanged:
-            if self._prep is not None:
-                self._join_branch(self._prep)          # (short prologue: the mask sum was formed on the critic's stream)
+        if self._dist_shard() and not self._st.stats_exchanged:
+            if self._st.prep is not None:
+                self._join_branch(self._st.prep)         # (short prologue: the mask sum was formed on the critic's stream)
             if self.masked:
                 self.be.copy_(self.stats_flat[-1:], self.acc[L.ACC_MASK_SUM:L.ACC_MASK_SUM + 1])
             n_amp = self.amp_sums_flat.numel() if (self.has_disc and self._amp_stats_in_branch()) else 0

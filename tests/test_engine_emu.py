@@ -9,7 +9,7 @@ import os
 import pytest
 import torch
 
-from ase_amd.engine import UpdateEngine
+from ase_amd.engine import UpdateEngine, _StepState
 from tests.emu_backend import EmuBackend
 from tests.helpers import build_net, close, get_rms, set_rms
 
@@ -17,7 +17,8 @@ CASES = ['ase_tiny', 'amp_tiny', 'ppo_tiny', 'ase_sep_tiny', 'ase_gp_tiny', 'ase
          'ase_swish_tiny']       # swish (SiLU) in the policy MLPs, the discriminator and the encoder: the curved gradient penalty
 
 
-def first_step(G, be, dtype, device='cpu', grad_scale=None, engine_opts=None, gp_f32=False):
+def build_engine(G, be, dtype, device='cpu', grad_scale=None, engine_opts=None, gp_f32=False):
+    """(net, engine, arguments of engine.step for the golden's first minibatch)."""
     kind, cfg, E = G['kind'], dict(G['cfg']), G['epochs'][0]
     if engine_opts:
         cfg['engine_opts'] = engine_opts
@@ -36,7 +37,12 @@ def first_step(G, be, dtype, device='cpu', grad_scale=None, engine_opts=None, gp
     if kind != 'ppo':
         streams = [(mb['amp_obs'], idx, (0, 0)), (mb['amp_obs_replay'], idx, (0, 0)), (mb['amp_obs_demo'], idx, (0, 0))]
     z = E['new_zs'][0].to(device) if E['new_zs'] else None
-    eng.step(mb, idx, (0, 0), streams, new_z=z)
+    return net, eng, ((mb, idx, (0, 0), streams), dict(new_z=z))
+
+
+def first_step(G, be, dtype, **kw):
+    net, eng, (args, kwargs) = build_engine(G, be, dtype, **kw)
+    eng.step(*args, **kwargs)
     return net, eng
 
 
@@ -212,3 +218,41 @@ def test_retired_engine_opts_are_unknown(name, golden_dir):
     G = torch.load(os.path.join(golden_dir, 'ase_tiny.pt'), weights_only=False)
     with pytest.raises(AssertionError, match='unknown engine_opts'):
         first_step(G, EmuBackend(), torch.float32, engine_opts={name: RETIRED_OPTS[name]})
+
+
+# the fields of engine._StepState; each was an engine attribute of the same name behind an underscore
+STEP_STATE_FIELDS = ['disc_fwd_out', 'stats_exchanged', 'merged_stats', 'stats_mark_a', 'stats_mark_b', 'pre_done', 'prep', 'lat_ready',
+                     'fill_done', 'early_fork', 'enc_z_ready', 'gp_x_done', 'gp_value_done', 'disc_acc_mark', 'acc_in_bucket', 'lr_live']
+
+
+def test_step_state_is_replaced_every_step(golden_dir):
+    """What the phases of a step hand each other lives in ONE object (engine._StepState), which phase_stats replaces at the top of
+    every step; none of the sixteen loose attributes it replaced is left on the engine."""
+    G = torch.load(os.path.join(golden_dir, 'ase_tiny.pt'), weights_only=False)
+    net, eng, (args, kwargs) = build_engine(G, EmuBackend(), torch.float32)
+    seen = [eng._st]
+    for _ in range(2):
+        eng.step(*args, **kwargs)
+        seen.append(eng._st)
+    assert all(type(st) is _StepState for st in seen)
+    assert seen[2] is not seen[1] and seen[1] is not seen[0]
+    assert sorted(_StepState.__slots__) == sorted(STEP_STATE_FIELDS) and len(STEP_STATE_FIELDS) == 16
+    for name in STEP_STATE_FIELDS:
+        assert not hasattr(eng, '_' + name), name
+
+
+def test_step_state_refuses_unknown_fields(golden_dir):
+    """__slots__: a misspelled field raises instead of creating an attribute nobody reads."""
+    G = torch.load(os.path.join(golden_dir, 'ppo_tiny.pt'), weights_only=False)
+    _, eng = first_step(G, EmuBackend(), torch.float32)
+    with pytest.raises(AttributeError):
+        eng._st.lat_redy = None
+    with pytest.raises(AttributeError):
+        _StepState().disc_acc_mrak = None
+
+
+def test_step_state_disc_acc_mark_stays_none_without_discriminator(golden_dir):
+    """Kind 'ppo' has no discriminator branch: nothing sets its mark, and a fresh state per step means no earlier one survives."""
+    G = torch.load(os.path.join(golden_dir, 'ppo_tiny.pt'), weights_only=False)
+    _, eng = first_step(G, EmuBackend(), torch.float32)
+    assert eng._st.disc_acc_mark is None

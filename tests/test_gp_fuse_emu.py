@@ -105,7 +105,7 @@ def test_gp_fuse_matches_the_separate_launches(G, unfused):
     assert be.fused_launches == 2 * (nl + 1)                     # seed launch, nl - 1 inner chain launches, the last chain launch
     assert off_helpers[0] - be.helper_launches == 2 * 3          # gp_seed, sqnorm and the conversion launch: gone
     if eng.amp % 4 == 0:                                         # ... and the value path's own normalise launch (16-byte rows)
-        assert eng._gp_x_done and off_helpers[1] - be.normalize_launches == 2
+        assert eng._st.gp_x_done and off_helpers[1] - be.normalize_launches == 2
     assert eng._gp_split and be.split_shadow_writes == 2 * nl       # the trunk's half-split shadows: by the optimizer launch
     assert float(on[0]['res']['disc_grad_penalty']) > 0
     assert_same_step(on[0], off[0], 'step 0')
