@@ -140,7 +140,7 @@ __device__ __forceinline__ uint32_t rows_frag(const f32x16& c, const f32x4 (&bia
             }
             const i16x2 o = __builtin_elementwise_max(__builtin_bit_cast(i16x2, cvt_pk16<T>(v)), relu_lo);
             pk[g][pr] = __builtin_bit_cast(uint32_t, o);
-            if constexpr (MASK) {
+            if constexpr (MASK) {       // assumes ReLU (o >= 0, so min(o, 1) is 0 or 1): rows_epi() sends every other mask_out launch to the slab
                 const i16x2 one = {1, 1};
                 const u16x2 t = __builtin_bit_cast(u16x2, __builtin_elementwise_min(o, one));      // 1 where the stored value is > 0
                 const u16x2 sh = {(unsigned short)((g & 1) * 8 + 2 * pr), (unsigned short)((g & 1) * 8 + 2 * pr + 1)};

@@ -939,9 +939,11 @@ template <typename T, bool SW = false, int BM = 256> int launch_nt8(const NTPara
 namespace {
 
 // row-per-lane epilogue (swapped MFMA operands): 16-bit output in whole wave-tile column blocks, no column sums, no tanh,
-// mask operand absent or a bit matrix
+// mask operand absent or a bit matrix; a mask_out twin only behind ReLU (rows_frag forms its bit from the clamped 16-bit pattern -
+// any other activation takes the LDS-slab epilogue, which compares the stored value with 0)
 inline bool rows_epi(const NTParams& p, int wave_cols) {
     return !p.out_f32 && p.N % wave_cols == 0 && p.colsum == nullptr && p.act <= ASE_ACT_RELU &&
+           (p.mask_out == nullptr || p.act == ASE_ACT_RELU) &&
            (p.aux_mode == ASE_AUX_NONE || p.aux_mode == ASE_AUX_RELU_BITS);
 }
 
