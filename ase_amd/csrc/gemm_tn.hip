@@ -433,7 +433,7 @@ __device__ __forceinline__ void tn8_body(const TNParams& p, char* smem, int bn0,
                 const int row0 = (kind >> 1) * 32 + 2 * (g * 8 + wid), row = row0 + lrow;
                 int chunk = slot ^ ((row & 3) << 2);
                 const int col0 = isA ? bn0 : bk0, width = isA ? p.N : p.K;
-                if (col0 + chunk * 8 >= width) chunk = 0;            // columns past the operand: products only reach unstored outputs
+                if (col0 + chunk * 8 >= width) chunk = 0;            // columns past the operand: products only reach unstored outputs (k_real + gap <= K)
                 const int64_t ld = isA ? p.lda : p.ldb;
                 L.voff[kind][g] = (uint32_t)((int64_t)(m_begin + row) * ld + (int64_t)col0 * 2 + chunk * 16);
                 L.dst[kind][g] = (uint32_t)(uintptr_t)smem + (isA ? 0 : 32768) + row0 * 512;
@@ -880,6 +880,23 @@ extern "C" int ase_hip_refresh_shadow_multi(const int64_t* desc, int n_layers, i
     return ASE_OK;
 }
 
+// The single-problem launch's kernel choice (ase_hip_gemm_tn and ase_hip_gemm_tn_kernel_id: written once).  The phased 256 x 256
+// kernel takes a 16-bit problem only when few M-splits fill the chip (its split reduction costs 256 KB of memory-side atomics
+// per workgroup; see the grouped launch): whole 64-row K-tiles, whole bias tiles, >= 32 K-tiles per split - and operands it can
+// reach through 32-bit byte offsets (< 2 GiB each).  bias_rows <= 0: all rows.
+static bool tn_takes_phased(int M, int N, int K, int n_real, int bias_rows, int64_t lda, int64_t ldb, int dtype) {
+    (void)N;
+    if (dtype != ASE_BF16 && dtype != ASE_F16) return false;
+    const int br = bias_rows > 0 ? bias_rows : M;
+    const int t256 = ((n_real + 255) / 256) * ((K + 255) / 256);
+    const bool fits32 = (int64_t)M * lda * 2 < (int64_t)0x7FFFFFFF && (int64_t)M * ldb * 2 < (int64_t)0x7FFFFFFF;
+    return M % 64 == 0 && br % 64 == 0 && n_real >= 128 && K >= 128 && (int64_t)M * t256 >= 256 * 2048 && fits32;
+}
+
+extern "C" int ase_hip_gemm_tn_kernel_id(int M, int N, int K, int n_real, int bias_rows, int64_t lda, int64_t ldb, int dtype) {
+    return tn_takes_phased(M, N, K, n_real, bias_rows, lda, ldb, dtype) ? 1 : 0;
+}
+
 extern "C" int ase_hip_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* G, float* gbias,
                                int bias_rows, int M, int N, int K, int n_real, int k_real, int split_src, int split_dst, float alpha,
                                const float* alpha_dev, int dtype, void* stream) {
@@ -892,18 +909,16 @@ extern "C" int ase_hip_gemm_tn(const void* A, int64_t lda, const void* B, int64_
                   "gemm_tn: A/B must be 16-byte aligned with 16-byte row pitch");
     ASE_CHECK_ARG(n_real > 0 && n_real <= N && k_real > 0 && split_src <= split_dst && split_src <= k_real,
                   "gemm_tn: bad real dims / split");
+    // (every column of G needs its column of B: the phased kernel substitutes chunk 0 for the chunks past K, which is harmless
+    //  only while no stored output reads them)
+    ASE_CHECK_ARG((int64_t)k_real + (split_dst - split_src) <= K, "gemm_tn: k_real=%d + concat gap %d exceeds K=%d", k_real,
+                  split_dst - split_src, K);
     TNParams p;
     p.A = (const char*)A; p.lda = lda * es; p.B = (const char*)B; p.ldb = ldb * es; p.G = G; p.gbias = gbias; p.bias_rows = bias_rows > 0 ? bias_rows : M;
     p.M = M; p.N = N; p.K = K; p.n_real = n_real; p.k_real = k_real; p.split_src = split_src; p.split_dst = split_dst;
     p.alpha = alpha; p.alpha_dev = alpha_dev; p.tiles_n = p.tiles_k = p.m_chunk = 0; p.prof = nullptr;
     if (es == 2) {
-        // Single-problem launches take the phased 256 x 256 kernel only when few M-splits fill the chip (its split
-        // reduction costs 256 KB of memory-side atomics per workgroup; see the grouped launch): whole 64-row K-tiles,
-        // whole bias tiles, >= 32 K-tiles per split.
-        const int t256 = ((n_real + 255) / 256) * ((K + 255) / 256);
-        // (the phased kernel reaches its operands through 32-bit byte offsets: < 2 GiB each)
-        const bool fits32 = (int64_t)M * p.lda < (int64_t)0x7FFFFFFF && (int64_t)M * p.ldb < (int64_t)0x7FFFFFFF;
-        const bool phased = M % 64 == 0 && p.bias_rows % 64 == 0 && n_real >= 128 && K >= 128 && (int64_t)M * t256 >= 256 * 2048 && fits32;
+        const bool phased = tn_takes_phased(M, N, K, n_real, bias_rows, lda, ldb, dtype);
         if (dtype == ASE_BF16) return phased ? launch_tn8<bf16_t>(p, (hipStream_t)stream) : launch_tn<bf16_t>(p, (hipStream_t)stream);
         return phased ? launch_tn8<f16_t>(p, (hipStream_t)stream) : launch_tn<f16_t>(p, (hipStream_t)stream);
     }
@@ -923,6 +938,8 @@ static int tn_problem_check(const int64_t* d, int i) {
                   "gemm_tn_grouped: problem %d: operands must be 16-byte aligned with whole 16-byte chunks per row", i);
     ASE_CHECK_ARG(n_real > 0 && n_real <= N && k_real > 0 && d[12] <= d[13] && d[12] <= k_real,
                   "gemm_tn_grouped: problem %d: bad real dims / split", i);
+    ASE_CHECK_ARG(k_real + (d[13] - d[12]) <= K, "gemm_tn_grouped: problem %d: k_real=%lld + concat gap %lld exceeds K=%lld", i,
+                  (long long)k_real, (long long)(d[13] - d[12]), (long long)K);
     ASE_CHECK_ARG(M * lda * 2 < (int64_t)0x7FFFFFFF && M * ldb * 2 < (int64_t)0x7FFFFFFF,
                   "gemm_tn_grouped: problem %d: operands beyond 2 GiB (the kernel addresses them with 32-bit byte offsets)", i);
     return ASE_OK;

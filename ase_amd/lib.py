@@ -96,6 +96,7 @@ SIGNATURES = {
                           _p, _p, _p, _p, _i, _i, _i, _f, _p, _i, _p],
     "ase_hip_clip_frames": [_p] * 6 + [_i] + [_p] * 4 + [_i, _i, _p, _p, _i] + [_p] * 7,
     "ase_hip_gemm_nt_kernel_id": [_i, _i, _i, _i],
+    "ase_hip_gemm_tn_kernel_id": [_i, _i, _i, _i, _i, _i64, _i64, _i],
     "ase_hip_apply_multi": [_p, _i, _p, _p, _i, _p],
     "ase_hip_apply_multi_v2": [_p, _i, _p, _p, _p, _i, _p],
     "ase_hip_gemm_tn_grouped_plan": [_p, _i, _i, _p, _i, _p, _p, _i, _p],

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset and ase_hip_latent_renew were added WITHOUT a new version
+/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew and ase_hip_gemm_tn_kernel_id were added WITHOUT a new version
  *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
  *  load time) */
 #define ASE_HIP_ABI_VERSION 9
@@ -127,11 +127,19 @@ int ase_hip_gemm_nt_ex(const void* A, int64_t lda, const void* B, int64_t ldb, v
  *   (layers without a concat pass split_src = split_dst = k_real).
  *   gbias (nullable, f32[n_real]) += alpha * sum_{m < bias_rows} A[m,n] (bias_rows <= 0: all rows): the bias gradient of the same layer, reduced from
  *   the A tiles the kernel stages anyway (a handful of atomics per column instead of one per row tile).
+ *   Every column of G needs its column of B: k_real + (split_dst - split_src) <= K, anything else is refused (ASE_EINVAL; the
+ *   grouped plan refuses it too).  Columns [n_real, N) of A, [split_src, split_dst) and [k_real + gap, K) of B are padding whose
+ *   CONTENT never reaches G or gbias.
  * Replaces: autograd's weight gradient of nn.Linear inside loss.backward()
  *   (learning/ase_agent.py:271). */
 int ase_hip_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, float* G, float* gbias,
                     int bias_rows, int M, int N, int K, int n_real, int k_real, int split_src, int split_dst,
                     float alpha, const float* alpha_dev, int dtype, void* stream);
+
+/* Which kernel ase_hip_gemm_tn launches for a problem (host only): 0 = 128 x 128 (register-staged, every storage mode),
+ * 1 = phased 256 x 256 (16-bit storage, M and bias_rows whole 64-row K-tiles, M * (256 x 256 tiles) >= 256 * 2048, operands
+ * below 2 GiB).  The arguments are exactly what the choice depends on; ase_hip_gemm_tn asks the same function. */
+int ase_hip_gemm_tn_kernel_id(int M, int N, int K, int n_real, int bias_rows, int64_t lda, int64_t ldb, int dtype);
 
 /* All weight gradients of one branch of an optimisation step in ONE grouped launch (16-bit storage).  They only depend on
  * buffers the data-gradient chain has already written, and one grid of ~256 long contractions pays the split-M reduction once

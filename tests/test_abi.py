@@ -135,6 +135,43 @@ def test_grouped_plan_rejects_ragged_rows():
     assert rc == -1
 
 
+def test_tn_kernel_choice_is_reported():
+    """ase_hip_gemm_tn_kernel_id(M, N, K, n_real, bias_rows, lda, ldb, dtype): 0 = 128 x 128, 1 = phased 256 x 256 - the function
+    ase_hip_gemm_tn itself asks (tests/ref_gemm_tn.py pins every exact case's id)."""
+    lib = L.load()
+    assert lib.ase_hip_gemm_tn_kernel_id(65536, 512, 1024, 512, 0, 512, 1024, L.BF16) == 1       # 8 tiles x 65536 rows = 256 x 2048
+    assert lib.ase_hip_gemm_tn_kernel_id(65536, 512, 1024, 512, 0, 512, 1024, L.F16) == 1
+    assert lib.ase_hip_gemm_tn_kernel_id(65536, 512, 1024, 512, 0, 512, 1024, L.F32) == 0        # 4-byte storage
+    assert lib.ase_hip_gemm_tn_kernel_id(65536, 512, 1024, 512, 0, 512, 1024, L.F32X3) == 0
+    assert lib.ase_hip_gemm_tn_kernel_id(65472, 512, 1024, 512, 0, 512, 1024, L.BF16) == 0      # one K-tile short
+    assert lib.ase_hip_gemm_tn_kernel_id(16384, 512, 1024, 512, 0, 512, 1024, L.BF16) == 0      # (tests/test_gpu_ops.py's largest TN shape)
+    assert lib.ase_hip_gemm_tn_kernel_id(65536, 512, 1024, 512, 12288, 512, 1024, L.BF16) == 1   # whole bias tiles
+    assert lib.ase_hip_gemm_tn_kernel_id(65536, 512, 1024, 512, 12300, 512, 1024, L.BF16) == 0   # a ragged bias limit
+    assert lib.ase_hip_gemm_tn_kernel_id(65568, 512, 1024, 512, 0, 512, 1024, L.BF16) == 0       # ragged rows
+    assert lib.ase_hip_gemm_tn_kernel_id(1 << 20, 64, 1024, 64, 0, 64, 1024, L.BF16) == 0        # narrow output
+    assert lib.ase_hip_gemm_tn_kernel_id(1 << 20, 512, 1024, 512, 0, 512, 1024, L.BF16) == 0    # B past 2 GiB (32-bit offsets)
+
+
+def test_tn_refuses_columns_of_g_without_a_column_of_b():
+    """k_real + (split_dst - split_src) > K: the 128 x 128 kernel would add zeros for the missing columns, the phased kernel
+    products of chunk 0.  Both entry points refuse it on the host (no GPU needed)."""
+    lib = L.load()
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    p = ctypes.c_void_p((p.value + 15) // 16 * 16)
+    args = lambda kr, ss, sd, K: (p, 64, p, K, p, None, 0, 64, 64, K, 64, kr, ss, sd, 1.0, None, L.BF16, None)
+    assert lib.ase_hip_gemm_tn(*args(62, 40, 48, 64)) == -1 and b'concat gap' in lib.ase_hip_last_error()
+    assert lib.ase_hip_gemm_tn(*args(65, 65, 65, 64)) == -1 and b'exceeds K' in lib.ase_hip_last_error()
+    for kr, ss, sd, K, ok in [(62, 40, 48, 64, False), (65, 65, 65, 64, False), (56, 40, 48, 64, True), (64, 64, 64, 64, True)]:
+        tab = (ctypes.c_int64 * 16)(0x1000, 64, 0x2000, K, 0x3000, 0, 0, 64, 64, K, 64, kr, ss, sd, 0x3F800000, 0)
+        work, red = (ctypes.c_int32 * (4 * 64))(), (ctypes.c_int32 * (4 * 64))()
+        nw, nr = ctypes.c_int(0), ctypes.c_int(0)
+        rc = lib.ase_hip_gemm_tn_grouped_plan(tab, 1, 0, work, 64, ctypes.byref(nw), red, 64, ctypes.byref(nr))
+        assert rc == (0 if ok else -1), (kr, ss, sd, K)
+        if not ok:
+            assert b'exceeds K' in lib.ase_hip_last_error()
+
+
 def test_nt_kernel_choice_is_reported():
     lib = L.load()
     assert lib.ase_hip_gemm_nt_kernel_id(16384, 1024, 1024, L.BF16) == 2      # phased 256 x 256
