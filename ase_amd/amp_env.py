@@ -11,6 +11,19 @@ batch (``ase_hip_amp_reset``, csrc/amp_reset.hip); there is no host fallback.
 and an apply can be recorded in a launch program.  Binding a simulator (pushing the written state to the physics engine)
 and ``_generate_fall_states`` (which needs physics) stay with the caller; the target resets of the four tasks are
 ``env_tensors.HumanoidTensors.reset_task`` - for the strike task called after ``apply_reset``, as the reference does.
+
+``reset_due`` (N10) is the same reset without the host: ONE launch (``ase_hip_amp_reset_due``) tests ``reset_buf``, draws and
+applies, and exports the decisions as a full-length plan whose ``env_ids`` hold -1 where nothing was reset.  The draws of
+environment e depend on (seed, stream position, e) only, so a partial reset draws other values than ``draw_reset`` under a
+torch generator: the method is separate and opt-in.  The reset sequence of a step then makes no torch op that waits for the
+host (``tensors``: the ``HumanoidTensors`` of the task, ``amp``: this class, ``agent``: an ``ASEAgent``)::
+
+    reset_buf, terminate_buf = tensors.compute_reset(state, progress_buf)
+    amp.mask_recovery(reset_buf, terminate_buf)
+    plan = amp.reset_due(state, progress_buf, reset_buf, terminate_buf)
+    tensors.reset_task(state, plan['env_ids'], progress_buf)           # skips the -1 rows
+    backend.latent_renew(latents, env_ids=plan['env_ids'], rng_state=agent_rng_state, reset_steps=latent_reset_steps,
+                         steps_low=latent_steps_min, steps_high=latent_steps_max)
 """
 import numpy as np
 import torch
@@ -23,7 +36,7 @@ STATE_INIT = ('Default', 'Start', 'Random', 'Hybrid')        # HumanoidAMP.State
 class HumanoidAMPTensors:
     def __init__(self, backend, motion_lib, num_envs, num_amp_obs_steps=10, dt=1.0 / 30.0, state_init='Random', hybrid_init_prob=0.5,
                  local_root_obs=True, root_height_obs=True, recovery_episode_prob=None, recovery_steps=None, fall_init_prob=None,
-                 generator=None, device=None):
+                 generator=None, device=None, seed=0):
         if state_init not in STATE_INIT:
             raise ValueError(f"state_init must be one of {STATE_INIT}, got {state_init!r}")
         getup = (recovery_episode_prob, recovery_steps, fall_init_prob)
@@ -47,6 +60,10 @@ class HumanoidAMPTensors:
         self.amp_obs_buf = torch.zeros(self.num_envs, self._num_amp_obs_steps, self._num_amp_obs_per_step, dtype=torch.float32, device=dev)
         self.recovery_counter = torch.zeros(self.num_envs, dtype=torch.int32, device=dev) if self.getup else None
         self._initial, self._fall, self._table = None, None, None
+        # reset_due: the Philox {seed, offset} of the device-side draws and the plan it exports, one element per environment
+        self.rng_state = torch.tensor([int(seed), 0], dtype=torch.int64, device=dev)
+        self.plan = {k: torch.zeros(self.num_envs, dtype=torch.float32 if k == 'motion_times' else torch.int32, device=dev)
+                     for k in ('env_ids', 'kind', 'motion_ids', 'motion_times', 'src_rows')}
 
     def get_num_amp_obs(self):
         """humanoid_amp.py:61-62."""
@@ -183,6 +200,30 @@ class HumanoidAMPTensors:
         plan = self.draw_reset(env_ids, terminate_buf)
         self.apply_reset(state, plan, progress_buf, reset_buf, terminate_buf)
         return plan
+
+    def reset_due(self, state, progress_buf, reset_buf, terminate_buf=None, advance=True):
+        """``_reset_envs`` for every environment with ``reset_buf != 0``, due test, draws, apply and ``_reset_env_tensors`` in
+        ONE launch (``ase_hip_amp_reset_due``; the draw table is in include/ase_hip.h) -> ``self.plan``: five [N] device
+        tensors that the launch fills, ``env_ids`` = e for a reset environment and -1 otherwise - a valid plan of
+        ``apply_reset`` and an id list for ``HumanoidTensors.reset_task`` / ``latent_renew``, which skip -1.  No torch op, no
+        ``host_call``, no synchronisation: it can be recorded in a launch program and follows the buffers at replay.
+        ``rng_state`` moves on by one unless advance is false.  The clip of a motion row comes from ``DeviceMotionLib.clip_cdf``."""
+        if self.getup and terminate_buf is None:
+            raise ValueError("the get-up task draws recovery episodes from terminate_buf")
+        init = STATE_INIT.index(self._state_init)
+        if init in (L.INIT_DEFAULT, L.INIT_HYBRID) and self._initial is None:
+            raise ValueError("Default / Hybrid state initialisation needs set_initial_state")
+        getup = None
+        if self.getup:
+            if self._fall_init_prob > 0 and self._fall is None:
+                raise ValueError("fall episodes need set_fall_states")
+            getup = (self._recovery_episode_prob, self._recovery_steps, self._fall_init_prob)
+        s, ml = state, self._motion_lib
+        self.be.amp_reset_due(ml.clips, ml.clip_cdf, self._table, init, self._hybrid_init_prob, getup, self.rng_state, progress_buf,
+                              reset_buf, terminate_buf, self.recovery_counter, self.plan, s['humanoid_root_states'], s['dof_pos'],
+                              s['dof_vel'], s['rigid_body_pos'], s['rigid_body_rot'], s['rigid_body_vel'], s['rigid_body_ang_vel'],
+                              self._local_root_obs, self._root_height_obs, self.dt, self.amp_obs_buf, advance=advance)
+        return self.plan
 
     def compute_amp_observations(self, state, env_ids):
         """``_compute_amp_observations(env_ids)`` (humanoid_amp.py:267-274): slot 0 of those rows, nothing else."""

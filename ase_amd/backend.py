@@ -488,6 +488,69 @@ class HipBackend:
                                            int(local_root_obs), int(root_height_obs), float(env_dt), _ptr(hist), S, self._stream()),
                 "amp_reset")
 
+    def amp_reset_due(self, clips, clip_cdf, table, state_init, hybrid_init_prob, getup, rng_state, progress_buf, reset_buf,
+                      terminate_buf, recovery_counter, plan, root_states, dof_pos, dof_vel, body_pos, body_rot, body_vel,
+                      body_ang_vel, local_root_obs, root_height_obs, env_dt, hist, advance=True):
+        """The resets of amp_reset with the due test and the draws inside the launch (N10; operands and the draw table: see
+        ase_hip_amp_reset_due): every environment with reset_buf != 0 is reset, its draws depend on (seed, stream position,
+        environment) only.  state_init: L.INIT_*; getup: None or (recovery_episode_prob, recovery_steps, fall_init_prob),
+        then terminate_buf and recovery_counter (int32 [N]) are needed.  clips / table as for amp_reset (the clip tensors
+        and clip_cdf, uint32 bits in an int32 [n_clips] tensor, unless state_init is INIT_DEFAULT; the table for INIT_DEFAULT /
+        INIT_HYBRID and fall episodes, fall states behind the N initial rows).  rng_state int64 [2] = seed | offset, advanced
+        by one unless advance is false.  progress_buf / reset_buf / terminate_buf (int64 [N]; progress_buf and, without
+        getup, terminate_buf may be None), recovery_counter and the state are written in place, for the reset rows only.
+        plan: None or the dict of five [N] tensors (env_ids, kind, motion_ids, src_rows int32, motion_times f32) that receives
+        every environment's decision, env_ids -1 where none was made."""
+        n, S, F = hist.shape
+        B, D = body_pos.shape[1], int(clips['dof_offsets'][-1])
+        J, K = len(clips['dof_offsets']) - 1, len(clips['key_body_ids'])
+        has_motion = state_init != L.INIT_DEFAULT
+        ia = lambda xs: (C.c_int32 * len(xs))(*[int(x) for x in xs])
+        self._f32c(body_pos, body_rot, body_vel, body_ang_vel, hist)
+        assert body_rot.shape == (n, B, 4) and body_vel.shape == body_ang_vel.shape == body_pos.shape == (n, B, 3)
+        assert F == 13 + 6 * J + D + 3 * K, "hist: [n_envs, n_steps, 13 + 6 J + D + 3 K]"
+        for t in (progress_buf, reset_buf, terminate_buf):
+            assert t is None or (t.dtype == torch.int64 and t.is_contiguous() and t.shape == (n,)), "buffers: int64 [n_envs]"
+        assert recovery_counter is None or (recovery_counter.dtype == torch.int32 and recovery_counter.is_contiguous() and
+                                            recovery_counter.shape == (n,)), "recovery_counter: int32 [n_envs]"
+        assert rng_state is None or (rng_state.dtype == torch.int64 and rng_state.numel() == 2 and rng_state.is_contiguous())
+        out = {k: None for k in ('env_ids', 'kind', 'motion_ids', 'motion_times', 'src_rows')} if plan is None else plan
+        for k, t in out.items():
+            assert t is None or (t.dtype == (torch.float32 if k == 'motion_times' else torch.int32) and t.is_contiguous() and
+                                 t.shape == (n,)), "plan: int32 / f32 [n_envs]"
+        for t in (root_states, dof_pos, dof_vel):
+            assert t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == n
+        assert root_states.shape[1] == 13 and root_states.stride(1) == 1
+        assert dof_pos.shape == dof_vel.shape == (n, D) and dof_pos.stride() == dof_vel.stride()
+        tab = (None, None, None)
+        if table is not None:
+            tab = table
+            self._f32c(*tab)
+            assert tab[0].dim() == 2 and tab[0].shape[1] == 13 and tab[1].shape == tab[2].shape == (tab[0].shape[0], D)
+        cl = {k: (clips[k] if has_motion else None) for k in ('gts', 'grs', 'lrs', 'grvs', 'gravs', 'dvs', 'lengths', 'num_frames',
+                                                                'dt', 'length_starts')}
+        n_clips = 0
+        if has_motion:
+            assert cl['gts'].shape[1] == B, "the clips' skeleton is the simulator's"
+            n_clips = cl['lengths'].numel()
+            assert clip_cdf is not None and clip_cdf.dtype == torch.int32 and clip_cdf.is_contiguous() and \
+                clip_cdf.shape == (n_clips,), "clip_cdf: int32 [n_clips]"
+        rec_prob, rec_steps, fall_prob = (0.0, 0, 0.0) if getup is None else getup
+        L.check(self.lib.ase_hip_amp_reset_due(_ptr(cl['gts']), _ptr(cl['grs']), _ptr(cl['lrs']), _ptr(cl['grvs']), _ptr(cl['gravs']),
+                                               _ptr(cl['dvs']), B, _ptr(cl['lengths']), _ptr(cl['num_frames']), _ptr(cl['dt']),
+                                               _ptr(cl['length_starts']), ia(clips['dof_body_ids']) if has_motion else None,
+                                               ia(clips['dof_offsets']), J, ia(clips['key_body_ids']), K,
+                                               _ptr(clip_cdf) if has_motion else None, n_clips, _ptr(tab[0]), _ptr(tab[1]),
+                                               _ptr(tab[2]), 0 if tab[0] is None else tab[0].shape[0], int(state_init),
+                                               float(hybrid_init_prob), int(getup is not None), float(rec_prob), float(fall_prob),
+                                               int(rec_steps), _ptr(rng_state), int(advance), _ptr(progress_buf), _ptr(reset_buf),
+                                               _ptr(terminate_buf), _ptr(recovery_counter), _ptr(out['env_ids']), _ptr(out['kind']),
+                                               _ptr(out['motion_ids']), _ptr(out['motion_times']), _ptr(out['src_rows']),
+                                               _ptr(root_states), root_states.stride(0), _ptr(dof_pos), _ptr(dof_vel),
+                                               dof_pos.stride(0), dof_pos.stride(1), _ptr(body_pos), _ptr(body_rot), _ptr(body_vel),
+                                               _ptr(body_ang_vel), n, int(local_root_obs), int(root_height_obs), float(env_dt),
+                                               _ptr(hist), S, self._stream()), "amp_reset_due")
+
     # ------------------------------------------------------------------ normaliser / gather
     def rms_moments(self, src, D, idx, remap, M, state, sums):
         L.check(self.lib.ase_hip_rms_moments(_ptr(src), _ld(src), D, _ptr(idx), remap[0], remap[1], M, _ptr(state),

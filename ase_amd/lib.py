@@ -22,6 +22,7 @@ TASK_OBS_COLS = (5, 2, 3, 15)                                       # columns as
 TASK_RESET_DRAWS = (3, 2, 3, 4)                                     # uniforms per row ase_hip_task_reset takes per kind
 RESET_FRAME, RESET_TABLE, RESET_MOTION = range(3)                   # ASE_RESET_*: the kinds of a row of ase_hip_amp_reset
 RESET_HAS_TABLE, RESET_HAS_MOTION = 1, 2                            # ASE_RESET_HAS_*: the host mask of kinds that may occur
+INIT_DEFAULT, INIT_START, INIT_RANDOM, INIT_HYBRID = range(4)       # ASE_INIT_*: the state initialisation of ase_hip_amp_reset_due
 
 # accumulator slots (ASE_ACC_*)
 (ACC_MASK_SUM, ACC_A_LOSS, ACC_B_LOSS, ACC_ENTROPY, ACC_CLIPPED, ACC_C_LOSS, ACC_KL, ACC_DIV, ACC_BCE_AGENT,
@@ -94,6 +95,8 @@ SIGNATURES = {
     "ase_hip_latent_renew": [_p, _i, _p, _i64, _p, _p, _i, _p, _i, _p, _i, _i64, _i64, _p, _i64, _p, _i64, _i, _i, _i, _p],
     "ase_hip_amp_reset": [_p] * 6 + [_i] + [_p] * 6 + [_i, _p, _i] + [_p] * 5 + [_i, _i, _p, _p, _p, _i, _p, _i64, _p, _p, _i64, _i,
                           _p, _p, _p, _p, _i, _i, _i, _f, _p, _i, _p],
+    "ase_hip_amp_reset_due": [_p] * 6 + [_i] + [_p] * 6 + [_i, _p, _i] + [_p, _i] + [_p, _p, _p, _i] + [_i, _d, _i, _d, _d, _i]
+                             + [_p, _i] + [_p] * 4 + [_p] * 5 + [_p, _i64, _p, _p, _i64, _i] + [_p] * 4 + [_i, _i, _i, _f, _p, _i, _p],
     "ase_hip_clip_frames": [_p] * 6 + [_i] + [_p] * 4 + [_i, _i, _p, _p, _i] + [_p] * 7,
     "ase_hip_gemm_nt_kernel_id": [_i, _i, _i, _i],
     "ase_hip_gemm_tn_kernel_id": [_i, _i, _i, _i, _i, _i64, _i64, _i],

@@ -121,6 +121,24 @@ def read_motion_files(motion_file, dof_body_ids, dof_offsets, key_body_ids):
             'dof_body_ids': dof_body_ids, 'dof_offsets': dof_offsets, 'key_body_ids': key_body_ids}
 
 
+def clip_cdf(weights):
+    """The table of the device-side weighted clip choice (``ase_hip_amp_reset_due``): ``cdf[m] = floor(2^24 cumsum(w)[m] /
+    sum(w) + 0.5)`` taken in f64, the last entry ``2^24``; a 24-bit draw ``v`` picks the first clip with ``v < cdf[m]``, so clip
+    m has probability ``(cdf[m] - cdf[m - 1]) / 2^24`` exactly and a clip of weight zero is never drawn.  -> int32 [n_clips]
+    (the uint32 the kernel reads: no entry exceeds 2^24).  A positive weight whose interval comes out empty is refused."""
+    w = np.asarray(torch.as_tensor(weights).detach().cpu().numpy(), dtype=np.float64).reshape(-1)
+    if w.size == 0 or not np.all(w >= 0) or not w.sum() > 0:
+        raise ValueError(f'clip weights {w.tolist()}: non-negative with a positive sum')
+    cdf = np.floor(2.0 ** 24 * np.cumsum(w) / w.sum() + 0.5).astype(np.int64)
+    cdf[-1] = 1 << 24
+    size = np.diff(cdf, prepend=0)
+    for m in np.nonzero(w > 0)[0]:
+        if size[m] <= 0:
+            raise ValueError(f'clip {int(m)}: weight {w[m]:g} of {w.sum():g} is below the 2^-24 resolution of the device-side '
+                             f'clip choice (it would never be drawn)')
+    return torch.from_numpy(cdf.astype(np.int32))
+
+
 class DeviceMotionLib:
     """``MotionLib`` (utils/motion_lib.py:57): same method names, argument meaning and return order."""
 
@@ -136,6 +154,7 @@ class DeviceMotionLib:
         n = self._motion_lengths.shape[0]
         w = torch.ones(n) if weights is None else torch.as_tensor(weights, dtype=torch.float32)
         self._motion_weights = (w / w.sum()).to(self._device)                 # motion_lib.py:213
+        self.clip_cdf = clip_cdf(w / w.sum()).to(self._device)
 
     @classmethod
     def from_arrays(cls, clips, backend, device, **kw):

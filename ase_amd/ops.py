@@ -54,6 +54,16 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
             key_body_ids, local_root_obs, root_height_obs, env_dt) -> ()      (root_states, dof_pos, dof_vel, hist written in place)
                                                       HumanoidAMP._reset_actors + _init_amp_obs, the get-up task's fall episodes
                                                       (env/tasks/humanoid_amp.py:141-246, humanoid_amp_getup.py:109-129)
+  amp_reset_due(root_states, dof_pos, dof_vel, hist, body_pos, body_rot, body_vel, body_ang_vel, reset_buf, rng_state,
+                progress_buf, terminate_buf, recovery_counter, env_ids_out, kind_out, motion_ids_out, motion_times_out,
+                src_rows_out, clip tensors ..., clip_cdf, tab_root_states, tab_dof_pos, tab_dof_vel, dof_body_ids, dof_offsets,
+                key_body_ids, state_init, hybrid_init_prob, getup, recovery_episode_prob, recovery_steps, fall_init_prob,
+                local_root_obs, root_height_obs, env_dt, advance=True) -> ()
+                                                      (state, hist, the three buffers, the counter, rng_state and the plan
+                                                      outputs written in place) the same resets for every environment with
+                                                      reset_buf != 0: due test, draws (Philox stream {seed, offset}), apply and
+                                                      _reset_env_tensors in one launch (humanoid_amp.py:132-201,
+                                                      humanoid_amp_getup.py:78-114, humanoid.py:165-167)
   clip_frames(rotation, root_translation, root_velocity, root_angular_velocity, local_translation, clip_first, clip_num_frames,
               clip_fps, frame_clip, parent_indices, dof_body_ids, dof_offsets) -> (gts, grs, lrs, grvs, gravs, dvs)
                                                       the clip loader: forward kinematics and joint velocities of every frame of
@@ -689,6 +699,50 @@ def amp_reset(root_states: torch.Tensor, dof_pos: torch.Tensor, dof_vel: torch.T
                          dof_vel, _f32c(body_pos, 'body_pos'), _f32c(body_rot, 'body_rot'), _f32c(body_vel, 'body_vel'),
                          _f32c(body_ang_vel, 'body_ang_vel'), local_root_obs, root_height_obs, env_dt, hist,
                          (L.RESET_HAS_TABLE if has_table else 0) | (L.RESET_HAS_MOTION if has_motion else 0))
+
+
+_STATE_INIT = {'Default': L.INIT_DEFAULT, 'Start': L.INIT_START, 'Random': L.INIT_RANDOM, 'Hybrid': L.INIT_HYBRID}
+
+
+@torch.library.custom_op('ase_hip::amp_reset_due',
+                         mutates_args=('root_states', 'dof_pos', 'dof_vel', 'hist', 'reset_buf', 'rng_state', 'progress_buf',
+                                       'terminate_buf', 'recovery_counter', 'env_ids_out', 'kind_out', 'motion_ids_out',
+                                       'motion_times_out', 'src_rows_out'), device_types='cuda')
+def amp_reset_due(root_states: torch.Tensor, dof_pos: torch.Tensor, dof_vel: torch.Tensor, hist: torch.Tensor, body_pos: torch.Tensor,
+                  body_rot: torch.Tensor, body_vel: torch.Tensor, body_ang_vel: torch.Tensor, reset_buf: torch.Tensor,
+                  rng_state: torch.Tensor, progress_buf: torch.Tensor | None, terminate_buf: torch.Tensor | None,
+                  recovery_counter: torch.Tensor | None, env_ids_out: torch.Tensor | None, kind_out: torch.Tensor | None,
+                  motion_ids_out: torch.Tensor | None, motion_times_out: torch.Tensor | None, src_rows_out: torch.Tensor | None,
+                  gts: torch.Tensor | None, grs: torch.Tensor | None, lrs: torch.Tensor | None, grvs: torch.Tensor | None,
+                  gravs: torch.Tensor | None, dvs: torch.Tensor | None, lengths: torch.Tensor | None, num_frames: torch.Tensor | None,
+                  dt: torch.Tensor | None, length_starts: torch.Tensor | None, clip_cdf: torch.Tensor | None,
+                  tab_root_states: torch.Tensor | None, tab_dof_pos: torch.Tensor | None, tab_dof_vel: torch.Tensor | None,
+                  dof_body_ids: list[int], dof_offsets: list[int], key_body_ids: list[int], state_init: str, hybrid_init_prob: float,
+                  getup: bool, recovery_episode_prob: float, recovery_steps: int, fall_init_prob: float, local_root_obs: bool,
+                  root_height_obs: bool, env_dt: float, advance: bool = True) -> None:
+    """HumanoidAMP / HumanoidAMPGetup resets of every environment with reset_buf != 0 in one launch, draws included (operands and
+    the draw table: see ase_hip_amp_reset_due).  state_init 'Default' | 'Start' | 'Random' | 'Hybrid'; the clip tensors and clip_cdf
+    come together (all but 'Default'), so do the three tab_* tensors ('Default', 'Hybrid', fall episodes) and the five plan
+    outputs.  Every tensor is passed by position, None where the mode has none."""
+    _check(state_init in _STATE_INIT, f'amp_reset_due: state_init is one of {list(_STATE_INIT)}')
+    clip = (gts, grs, lrs, grvs, gravs, dvs, lengths, num_frames, dt, length_starts, clip_cdf)
+    tab = (tab_root_states, tab_dof_pos, tab_dof_vel)
+    outs = (env_ids_out, kind_out, motion_ids_out, motion_times_out, src_rows_out)
+    has_clips, has_table, has_plan = (all(t is not None for t in ts) for ts in (clip, tab, outs))
+    _check(has_clips or all(t is None for t in clip), 'amp_reset_due: the clip tensors and clip_cdf come together')
+    _check(has_table or all(t is None for t in tab), 'amp_reset_due: the state table comes together')
+    _check(has_plan or all(t is None for t in outs), 'amp_reset_due: the plan outputs come all or none')
+    _check(has_clips or state_init == 'Default', f'amp_reset_due: {state_init} needs the clip tensors and clip_cdf')
+    clips = {'dof_body_ids': dof_body_ids, 'dof_offsets': dof_offsets, 'key_body_ids': key_body_ids}
+    if has_clips:
+        clips.update(gts=gts, grs=grs, lrs=lrs, grvs=grvs, gravs=gravs, dvs=dvs, lengths=lengths, num_frames=num_frames, dt=dt,
+                     length_starts=length_starts)
+    plan = dict(zip(('env_ids', 'kind', 'motion_ids', 'motion_times', 'src_rows'), outs)) if has_plan else None
+    _backend().amp_reset_due(clips, clip_cdf, tab if has_table else None, _STATE_INIT[state_init], hybrid_init_prob,
+                             (recovery_episode_prob, recovery_steps, fall_init_prob) if getup else None, rng_state, progress_buf,
+                             reset_buf, terminate_buf, recovery_counter, plan, root_states, dof_pos, dof_vel,
+                             _f32c(body_pos, 'body_pos'), _f32c(body_rot, 'body_rot'), _f32c(body_vel, 'body_vel'),
+                             _f32c(body_ang_vel, 'body_ang_vel'), local_root_obs, root_height_obs, env_dt, hist, advance)
 
 
 @torch.library.custom_op('ase_hip::clip_frames', mutates_args=(), device_types='cuda')

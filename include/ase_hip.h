@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew and ase_hip_gemm_tn_kernel_id were added WITHOUT a new version
+/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew, ase_hip_amp_reset_due and ase_hip_gemm_tn_kernel_id were added WITHOUT a new version
  *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
  *  load time) */
 #define ASE_HIP_ABI_VERSION 9
@@ -720,6 +720,54 @@ int ase_hip_amp_reset(const float* gts, const float* grs, const float* lrs, cons
                       const float* body_pos, const float* body_rot, const float* body_vel, const float* body_ang_vel,
                       int n_envs, int local_root_obs, int root_height_obs, float env_dt, float* hist, int n_steps,
                       void* stream);
+
+/* The same resets with the due test and the draws inside the launch (an addition to ABI 9, nothing else
+ * changed): ONE launch over all n_envs environments, no plan from the host, no nonzero, no host round trip, a fixed grid.
+ * Environment e is reset iff reset_buf[e] != 0 (progress_buf / reset_buf / terminate_buf: DEVICE int64 [n_envs]).  How it is
+ * reset follows from draws that depend on (seed, offset, e) only, rng_state = u64[2] {seed, offset} on the device as in
+ * ase_hip_task_reset.  Draw j of environment e comes from element 8 e + j of the stream; all six are defined for every
+ * environment, whichever branch uses them ("uniform": the 24-bit uniform (c[2] >> 8) * 2^-24 of the element, f32):
+ *   j = 0  uniform u0     getup: a recovery episode (ASE_RESET_FRAME) iff u0 < (float)recovery_episode_prob and
+ *                         terminate_buf[e] == 1
+ *   j = 1  uniform u1     getup, else: a fall episode iff u1 < (float)fall_init_prob
+ *   j = 2  output word 0  the fall row: ASE_RESET_TABLE with src = n_envs + (((uint64)word * (uint64)n_fall) >> 32),
+ *                         n_fall = n_tab - n_envs (exact, never reaches n_tab)
+ *   j = 3  uniform u3     ASE_INIT_HYBRID: a motion row iff u3 < (float)hybrid_init_prob, else the default row
+ *   j = 4  v = c[2] >> 8  the 24-bit integer behind the uniform: the clip of a motion row is the first m with v < cdf[m]
+ *   j = 5  uniform u5     motion_time = u5 * lengths[clip], one f32 product; ASE_INIT_START: 0
+ * Otherwise state_init decides: ASE_INIT_DEFAULT: ASE_RESET_TABLE with src = e; ASE_INIT_START / ASE_INIT_RANDOM:
+ * ASE_RESET_MOTION; ASE_INIT_HYBRID: j = 3.  Without getup, j = 0 .. 2 are unused.
+ * cdf: DEVICE uint32 [n_clips], non-decreasing, cdf[m] = floor(2^24 * cumsum(w)[m] / sum(w) + 0.5) taken in f64, the last entry
+ * 2^24: clip m has probability (cdf[m] - cdf[m - 1]) / 2^24 exactly, a clip of weight zero is never drawn.
+ * A reset row is then treated exactly as ase_hip_amp_reset treats a plan row of that (kind, motion_id, motion_time, src_row):
+ * the same kernel body.  The state table holds the initial state in rows [0, n_envs) and the fall states behind it.
+ * In the same launch, for reset rows only: progress_buf[e] = reset_buf[e] = terminate_buf[e] = 0 (progress_buf and, without
+ * getup, terminate_buf may be NULL) and, with getup, recovery_counter[e] (int32 [n_envs]) = recovery_steps for recovery and
+ * fall rows, else 0.
+ * The plan export (nullable, all five or none; int32 [n_envs], motion_times_out f32 [n_envs]): EVERY element is written -
+ * env_ids_out[e] = e for a reset row and -1 otherwise, the other four the row's decision (0 where it has none, and for rows
+ * that are not reset).  It is a valid plan of ase_hip_amp_reset and an id list for ase_hip_task_reset / ase_hip_latent_renew,
+ * which skip -1.
+ * advance != 0: the offset moves on by one behind the launch, also when no row was due (a call is one stream position).
+ * Refused: NULL reset_buf / rng_state; a state_init or a fall_init_prob > 0 that needs the table without it, or with n_tab <
+ * n_envs (n_tab <= n_envs for falls); ASE_INIT_START / _RANDOM / _HYBRID without the clip tensors or cdf; getup without
+ * terminate_buf or recovery_counter; a partial plan export; probabilities outside [0, 1]; the limits of ase_hip_amp_reset.
+ * Replaces: HumanoidAMP._reset_envs' draws and _reset_env_tensors (env/tasks/humanoid_amp.py:132-201, humanoid.py:165-167),
+ *   HumanoidAMPGetup._reset_actors / _reset_recovery_episode / _reset_fall_episode (env/tasks/humanoid_amp_getup.py:78-114). */
+enum { ASE_INIT_DEFAULT = 0, ASE_INIT_START = 1, ASE_INIT_RANDOM = 2, ASE_INIT_HYBRID = 3 };
+int ase_hip_amp_reset_due(const float* gts, const float* grs, const float* lrs, const float* grvs, const float* gravs,
+                          const float* dvs, int n_bodies, const float* lengths, const int32_t* num_frames, const float* dt,
+                          const int32_t* length_starts, const int32_t* dof_body_ids, const int32_t* dof_offsets, int n_joints,
+                          const int32_t* key_body_ids, int n_key, const uint32_t* cdf, int n_clips,
+                          const float* tab_root_states, const float* tab_dof_pos, const float* tab_dof_vel, int n_tab,
+                          int state_init, double hybrid_init_prob, int getup, double recovery_episode_prob,
+                          double fall_init_prob, int recovery_steps, uint64_t* rng_state, int advance, int64_t* progress_buf,
+                          int64_t* reset_buf, int64_t* terminate_buf, int32_t* recovery_counter, int32_t* env_ids_out,
+                          int32_t* kind_out, int32_t* motion_ids_out, float* motion_times_out, int32_t* src_rows_out,
+                          float* root_states, int64_t ld_root, float* dof_pos, float* dof_vel, int64_t ld_dof, int dof_stride,
+                          const float* body_pos, const float* body_rot, const float* body_vel, const float* body_ang_vel,
+                          int n_envs, int local_root_obs, int root_height_obs, float env_dt, float* hist, int n_steps,
+                          void* stream);
 
 /* Motion-clip loader: the frame arrays of ase_hip_motion_state / ase_hip_amp_reset from the raw contents of
  * SkeletonMotion clip files, every frame of every clip in ONE launch.  Inputs (DEVICE, all clips concatenated along the
