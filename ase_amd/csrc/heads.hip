@@ -7,6 +7,12 @@ namespace {
 
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;  // 0.5 * ln(2*pi)
 
+// max(x, lo), min(x, hi) and clamp as torch.clamp_min / clamp_max / clamp have them: a NaN x stays NaN (fmaxf / fminf would
+// return the bound, and a NaN mu would leave the surrogate, the bound loss, the diversity loss and the diversity rows' gradient
+// finite, a NaN value the clipped critic loss)
+__device__ __forceinline__ float floor_nan(float x, float lo) { return x < lo ? lo : x; }
+__device__ __forceinline__ float ceil_nan(float x, float hi) { return x > hi ? hi : x; }
+
 __global__ __launch_bounds__(256) void reduce_sum_kernel(const float* __restrict__ x, int64_t n, int square,
                                                          double* __restrict__ acc) {
     __shared__ double sm[16];
@@ -97,7 +103,7 @@ __global__ __launch_bounds__(256, 8) void ppo_head_kernel(PpoArgs p) {
         const float nlp = 0.5f * sum_d2 + kHalfLog2Pi * (float)D + sum_ls;
         const float ratio = expf(p.old_logp[i] - nlp);
         const float adv = p.adv[i];
-        const float rc = fminf(fmaxf(ratio, 1.f - p.e_clip), 1.f + p.e_clip);
+        const float rc = ceil_nan(floor_nan(ratio, 1.f - p.e_clip), 1.f + p.e_clip);   // (a NaN ratio reaches a_loss through both surrogates)
         const float s1 = -adv * ratio, s2 = -adv * rc;
         const float a_loss = fmaxf(s1, s2);
         float g;  // d a_loss / d ratio  (torch.max splits ties evenly; clamp passes gradient inside [lo, hi])
@@ -105,7 +111,7 @@ __global__ __launch_bounds__(256, 8) void ppo_head_kernel(PpoArgs p) {
         else g = (s1 > s2) ? -adv : ((s1 == s2) ? -0.5f * adv : 0.f);
 
         // bound loss, entropy, KL (rl_games policy_kl(p0 = new, p1 = old))
-        const float bh = fmaxf(m - 1.f, 0.f), bl = fminf(m + 1.f, 0.f);
+        const float bh = floor_nan(m - 1.f, 0.f), bl = ceil_nan(m + 1.f, 0.f);
         const float b_row = group_sum<LPR>(act_ok ? bh * bh + bl * bl : 0.f);
         const float ent_row = group_sum<LPR>(act_ok ? 0.5f + kHalfLog2Pi + ls : 0.f);
         float klj = 0.f;
@@ -137,8 +143,8 @@ __global__ __launch_bounds__(256, 8) void ppo_head_kernel(PpoArgs p) {
             if (act_ok) {
                 const float raw2 = p.mu[(int64_t)(p.M + i) * p.ld_mu + lane];
                 m2 = p.mu_tanh ? tanhf(raw2) : raw2;
-                cm = fminf(fmaxf(m, -1.f), 1.f);
-                cm2 = fminf(fmaxf(m2, -1.f), 1.f);
+                cm = ceil_nan(floor_nan(m, -1.f), 1.f);
+                cm2 = ceil_nan(floor_nan(m2, -1.f), 1.f);
             }
             const float diff = cm - cm2;
             const float a_diff = group_sum<LPR>(act_ok ? diff * diff : 0.f) / (float)D;
@@ -178,7 +184,7 @@ __global__ __launch_bounds__(256, 8) void ppo_head_kernel(PpoArgs p) {
             if (p.clip_value) {
                 const float ov = p.old_value[i];
                 const float dlt = v - ov;
-                const float vpc = ov + fminf(fmaxf(dlt, -p.e_clip), p.e_clip);
+                const float vpc = ov + ceil_nan(floor_nan(dlt, -p.e_clip), p.e_clip);
                 const float l1 = (v - R) * (v - R), l2 = (vpc - R) * (vpc - R);
                 const float inside = (dlt >= -p.e_clip && dlt <= p.e_clip) ? 1.f : 0.f;
                 c = fmaxf(l1, l2);
@@ -340,7 +346,7 @@ __global__ __launch_bounds__(256) void enc_head_kernel(const float* __restrict__
             }
         }
         const float ss = wave_sum(ev[0] * ev[0] + ev[1] * ev[1]);
-        const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+        const float nrm = floor_nan(sqrtf(ss), 1e-12f);          // (F.normalize: a NaN norm stays NaN)
         const float h0 = ev[0] / nrm, h1 = ev[1] / nrm;
         const float dot = wave_sum(h0 * zv[0] + h1 * zv[1]);
         const float sc = enc_coef / (float)amb_global;
@@ -375,7 +381,7 @@ __global__ __launch_bounds__(256) void enc_head_kernel(const float* __restrict__
 // Encoder gradient penalty (learning/ase_agent.py:431-441), seed and return of the chain.  Per row, with n = |e|,
 // eh = e / n, a = eh . z, the error is err = -a and
 //   u = d err / d e = -(z - eh a) / n                                   (seed of the chain W_e^T u -> ... -> d err / d x)
-//   J = d u / d e  (symmetric):  J r = [z (eh . r) + eh (z . r) + a r - 3 a eh (eh . r)] / n^2
+//   J = d u / d e  (symmetric):  J r = [z (eh . r) + eh (z . r) + a r - 3 a eh (eh . r)] / n^2      (0 where |e| < 1e-12)
 // MODE 0: u_out = scale * u.   MODE 1: d_e += J du (du = what the chain's backward returns at u), the bias gradient
 // receives the change of the STORED d_e (db == column sums of what is stored).  One wave per row, z_dim <= 128.
 template <typename T, int MODE>
@@ -399,7 +405,9 @@ __global__ __launch_bounds__(256) void enc_gp_kernel(const float* __restrict__ e
                 if (MODE == 1) dv[q] = du[(int64_t)r * ld_du + j];
             }
         }
-        const float nrm = fmaxf(sqrtf(wave_sum(ev[0] * ev[0] + ev[1] * ev[1])), 1e-12f);
+        const float len = sqrtf(wave_sum(ev[0] * ev[0] + ev[1] * ev[1]));
+        const float nrm = floor_nan(len, 1e-12f);
+        const bool flat = len < 1e-12f;      // on F.normalize's floor eh = e / 1e-12 and u = -z / 1e-12 does not depend on e: J = 0
         const float h0 = ev[0] / nrm, h1 = ev[1] / nrm;
         const float a = wave_sum(h0 * zv[0] + h1 * zv[1]);
         float hr = 0.f, zr = 0.f;
@@ -417,7 +425,7 @@ __global__ __launch_bounds__(256) void enc_gp_kernel(const float* __restrict__ e
                     out[(int64_t)r * ld_out + j] = o;
                     bad |= ovf_hit1(o);
                 } else {
-                    const float jr = (zv[q] * hr + h * zr + a * dv[q] - 3.f * a * h * hr) / (nrm * nrm);
+                    const float jr = flat ? 0.f : (zv[q] * hr + h * zr + a * dv[q] - 3.f * a * h * hr) / (nrm * nrm);
                     const float old = to_f32(out[(int64_t)r * ld_out + j]);      // (carries the gradient scale)
                     const T nw = from_f32<T>(old + scale * jr);
                     out[(int64_t)r * ld_out + j] = nw;
@@ -589,7 +597,7 @@ __global__ void finalize_scalars_kernel(const double* __restrict__ acc, float* _
         out[ASE_RES_ENC_GP] = (float)egp;
     }
     if (a.has_div) {
-        const double dv = acc[ASE_ACC_DIV] / S;
+        const double dv = acc[ASE_ACC_DIV] / den;      // the denominator of ppo_head's diversity gradient
         loss += a.div_coef * dv;
         out[ASE_RES_DIV_LOSS] = (float)dv;
     }

@@ -279,6 +279,9 @@ int ase_hip_reduce_sum(const float* x, int64_t n, int square, double* acc, int s
  *   mu_tanh: 1 -> mu_out = tanh(mu) precedes the losses (HRL high-level policy,
  *            learning/hrl_network_builder.py:26-29)
  *   acc[ASE_ACC_MASK_SUM] must already hold the GLOBAL mask sum.
+ *   The diversity loss is weighted like the other masked means: mask / acc[ASE_ACC_MASK_SUM] with masked, 1 / m_global without.
+ *   A NaN in mu or value stays NaN wherever the reference's torch.clamp / torch.max keep it: in the surrogate, the bound loss,
+ *   the diversity loss and the clipped critic loss, in their accumulators and in the gradients of both row blocks.
  *   grad_scale (all loss heads): the STORED head gradients d_* are multiplied by it (the bias gradients and the loss
  *            scalars are not) - the static loss scale of ASE_F16 storage, whose back-propagated gradients would
  *            otherwise fall into half's subnormal range; the weight-gradient launches undo it through their alpha.
@@ -324,7 +327,8 @@ int ase_hip_disc_head(const float* logit, int64_t ld_l, void* d_logit, int64_t l
 
 /* Encoder head (learning/ase_network_builder.py:217, learning/ase_agent.py:413-418,469-472):
  * e f32 [amb, ld_e] pre-normalisation output, z f32 [amb, z_dim]; d_e dtype [amb, ld_de].
- * enc_out (nullable) f32 [amb, z_dim] receives normalize(e). */
+ * enc_out (nullable) f32 [amb, z_dim] receives normalize(e) (torch.nn.functional.normalize, eps 1e-12: a row with a NaN is
+ * NaN in every column). */
 int ase_hip_enc_head(const float* e, int64_t ld_e, const float* z, int64_t ld_z, void* d_e,
                      int64_t ld_de, float* db_enc, float* enc_out, double* acc, int amb, int amb_global,
                      int z_dim, float enc_coef, float grad_scale, float* grad_scale_dev, int dtype, void* stream);
@@ -333,7 +337,8 @@ int ase_hip_enc_head(const float* e, int64_t ld_e, const float* z, int64_t ld_z,
  * the two per-row pieces around the GEMM chain.  e f32 [rows, ld_e] pre-normalisation encoder output, z f32 [rows, ld_z].
  *   seed: u[r, :] = scale * d enc_err / d e = -scale (z - eh <eh, z>) / |e|          (dtype [rows, ld_u]; eh = e / |e|)
  *   back: d_e[r, :] += grad_scale * J du[r, :],  J = d u / d e (unscaled), du f32 [rows, ld_du] = what the chain's backward
- *         returns at u (d_e carries the gradient scale of ase_hip_enc_head);
+ *         returns at u (d_e carries the gradient scale of ase_hip_enc_head); J = 0 for a row with |e| < 1e-12, where
+ *         normalize(e) = e / 1e-12 and u does not depend on e;
  *         db_enc (nullable, f32 [z_dim]) += column sums of the change of the stored d_e. */
 int ase_hip_enc_gp_seed(const float* e, int64_t ld_e, const float* z, int64_t ld_z, void* u, int64_t ld_u, int rows,
                         int z_dim, float scale, int dtype, void* stream);
@@ -368,7 +373,9 @@ int ase_hip_sqnorm(const void* x, int64_t ld, int rows, int cols, double* acc, i
  * minibatch (learning/common_agent.py:204-208; lr_schedule: adaptive, kl_threshold): kl > 2 thr: lr / 1.5 (>= 1e-6),
  * kl < thr / 2: lr * 1.5 (<= 1e-2) - on the device, no .item() per step.  out[ASE_RES_LR] = the learning rate THIS step was
  * taken with (the reference's train_result['last_lr'], learning/common_agent.py:430), 0 with a constant rate (the host
- * knows it).  ABI 3: ASE_RES_COUNT 16 -> 20 (ASE_RES_LR; result vectors are slots of a per-update ring, 80-byte pitch). */
+ * knows it).  The masked means (a_loss, b_loss, entropy, clip fraction, diversity loss) divide by acc[ASE_ACC_MASK_SUM] when
+ * masked != 0 and by m_global when masked == 0 - ASE_RES_DIV_LOSS uses the denominator that ase_hip_ppo_head used for the
+ * diversity gradient.  ABI 3: ASE_RES_COUNT 16 -> 20 (ASE_RES_LR; result vectors are slots of a per-update ring, 80-byte pitch). */
 enum {
     ASE_RES_A_LOSS = 0, ASE_RES_C_LOSS, ASE_RES_B_LOSS, ASE_RES_ENTROPY, ASE_RES_CLIP_FRAC, ASE_RES_KL,
     ASE_RES_DISC_LOSS, ASE_RES_DISC_GP, ASE_RES_DISC_LOGIT_LOSS, ASE_RES_DISC_AGENT_ACC,

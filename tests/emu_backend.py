@@ -337,8 +337,9 @@ class EmuBackend:
             div_row = (div_tar - bonus) ** 2
             dl = div_coef * w * 2 * (bonus - div_tar)
             db = (dl * inv).unsqueeze(-1) * 2 * diff / D
-            gm = gm + db * ((m >= -1) & (m <= 1))
-            gm2 = -db * ((m2 >= -1) & (m2 <= 1))
+            zero = torch.zeros_like(db)                    # (where, not a product: a NaN db behind a closed gate is 0, as in the kernel)
+            gm = gm + torch.where((m >= -1) & (m <= 1), db, zero)
+            gm2 = torch.where((m2 >= -1) & (m2 <= 1), -db, zero)
             if mu_tanh:
                 gm2 = gm2 * (1 - m2 * m2)
         if mu_tanh:
@@ -418,7 +419,7 @@ class EmuBackend:
         nrm = ev.norm(dim=-1, keepdim=True).clamp_min(1e-12)
         h = ev / nrm
         a = (h * zv).sum(-1, keepdim=True)
-        u[:rows, :z_dim] = (-scale * (zv - h * a) / nrm).to(u.dtype)
+        u[:rows, :z_dim] = _store(-scale * (zv - h * a) / nrm, u.dtype)
 
     def enc_gp_back(self, e, z, du, d_e, db_enc, rows, z_dim, grad_scale=1.0, dyn=None):
         grad_scale = grad_scale * _dyn(dyn)
@@ -428,6 +429,7 @@ class EmuBackend:
         a = (h * zv).sum(-1, keepdim=True)
         hr, zr = (h * r).sum(-1, keepdim=True), (zv * r).sum(-1, keepdim=True)
         jr = (zv * hr + h * zr + a * r - 3 * a * h * hr) / (nrm * nrm)
+        jr = torch.where(ev.norm(dim=-1, keepdim=True) < 1e-12, torch.zeros_like(jr), jr)      # on the floor u = -z / 1e-12
         old = d_e[:rows, :z_dim].float().clone()
         new = _store(old + grad_scale * jr, d_e.dtype)
         d_e[:rows, :z_dim] = new
@@ -489,7 +491,7 @@ class EmuBackend:
             out[L.RES_ENC_LOSS] = el
             out[L.RES_ENC_GP] = egp
         if has_div:
-            dv = a[L.ACC_DIV] / S
+            dv = a[L.ACC_DIV] / den
             loss += c['amp_diversity_bonus'] * dv
             out[L.RES_DIV_LOSS] = dv
         out[L.RES_LOSS] = loss

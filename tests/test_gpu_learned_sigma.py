@@ -9,6 +9,7 @@ import torch
 
 from ase_amd import lib as L
 from tests.helpers import close, close_entry
+from tests.ref_heads import _head_inputs, _reference
 from tests.test_agent_emu import check_rollout_inference, make_agent, regenerate, replay_epochs
 
 pytestmark = pytest.mark.gpu
@@ -28,69 +29,6 @@ def be():
 
 
 # ------------------------------------------------------------------------------------------------ the loss head
-def _head_inputs(M, A, Z, seed, div_on):
-    g = torch.Generator().manual_seed(seed)
-    r = lambda *s: torch.randn(*s, generator=g)
-    mu = r(2 * M if div_on else M, A) * 0.6
-    ls_rows = -1.0 + 0.3 * r(M, A)
-    ls_vec = -1.0 + 0.3 * r(A)
-    old_mu = mu[:M] + 0.05 * r(M, A)
-    old_sigma = torch.exp(-1.0 + 0.3 * r(M, A))
-    actions = old_mu + old_sigma * r(M, A)
-    old_logp = (0.5 * (((actions - old_mu) / old_sigma) ** 2).sum(-1) + 0.5 * math.log(2 * math.pi) * A
-                + torch.log(old_sigma).sum(-1) + 0.1 * r(M))
-    mb = {'actions': actions, 'mu': old_mu, 'sigma': old_sigma, 'old_logp_actions': old_logp.view(M, 1),
-          'advantages': r(M, 1), 'old_values': r(M, 1), 'returns': r(M, 1),
-          'rand_action_mask': (torch.rand(M, 1, generator=g) < 0.7).float(),
-          'ase_latents': torch.nn.functional.normalize(r(M, Z), dim=-1)}
-    new_z = torch.nn.functional.normalize(r(M, Z), dim=-1)
-    value = r(M, 1)
-    return mu, ls_rows, ls_vec, mb, new_z, value
-
-
-def _reference(mu, ls, mb, new_z, value, M, A, masked, div_on, mu_tanh, clip_value, e_clip, cc, bc, dc, dt, ec):
-    """f64 autograd of the reference's expressions (learning/common_agent.py:456-534, ase_agent.py:228-258,445-467, rl_games
-    neglogp / entropy / policy_kl with sigma detached)."""
-    mu = mu.double().requires_grad_(True)
-    ls = ls.double().requires_grad_(True)
-    value = value.double().requires_grad_(True)
-    d = {k: v.double() for k, v in mb.items()}
-    raw = mu[:M]
-    m = torch.tanh(raw) if mu_tanh else raw
-    lsr = ls if ls.dim() == 2 else ls.expand(M, A)
-    sg = torch.exp(lsr)
-    a = d['actions']
-    nlp = 0.5 * (((a - m) / sg) ** 2).sum(-1) + 0.5 * math.log(2 * math.pi) * A + lsr.sum(-1)
-    ratio = torch.exp(d['old_logp_actions'].view(-1) - nlp)
-    adv = d['advantages'].view(-1)
-    a_loss = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1 - e_clip, 1 + e_clip))
-    if clip_value:
-        ov = d['old_values'].view(-1)
-        vpc = ov + (value.view(-1) - ov).clamp(-e_clip, e_clip)
-        c_loss = torch.max((value.view(-1) - d['returns'].view(-1)) ** 2, (vpc - d['returns'].view(-1)) ** 2)
-    else:
-        c_loss = (d['returns'].view(-1) - value.view(-1)) ** 2
-    b_loss = ((m - 1).clamp_min(0) ** 2 + (m + 1).clamp_max(0) ** 2).sum(-1)
-    ent = (0.5 + 0.5 * math.log(2 * math.pi) + lsr).sum(-1)
-    sgd = sg.detach()
-    kl = (torch.log(d['sigma'] / sgd + 1e-5) + (sgd ** 2 + (d['mu'] - m) ** 2) / (2 * (d['sigma'] ** 2 + 1e-5)) - 0.5).sum(-1)
-    mk = d['rand_action_mask'].view(-1) if masked else torch.ones(M, dtype=torch.float64)
-    mean = lambda x: (x * mk).sum() / mk.sum()
-    loss = mean(a_loss) + cc * c_loss.mean() + bc * mean(b_loss) - ec * mean(ent)
-    div = torch.zeros((), dtype=torch.float64)
-    if div_on:
-        raw2 = mu[M:]
-        m2 = torch.tanh(raw2) if mu_tanh else raw2
-        diff = m.clamp(-1, 1) - m2.clamp(-1, 1)
-        a_diff = (diff ** 2).sum(-1) / A
-        z_diff = 0.5 - 0.5 * (new_z.double() * d['ase_latents']).sum(-1)
-        div = mean((dt - a_diff / (z_diff + 1e-5)) ** 2)
-        loss = loss + dc * div
-    loss.backward()
-    stats = [mean(a_loss), c_loss.mean(), mean(b_loss), mean(ent), mean(((ratio - 1).abs() > e_clip).double()), kl.mean()]
-    return torch.stack([s.detach() for s in stats]), mu.grad, ls.grad, value.grad
-
-
 @pytest.mark.parametrize('dtype', [torch.float32, torch.float16, torch.bfloat16])
 @pytest.mark.parametrize('A', [31, 64])
 @pytest.mark.parametrize('rows', [False, True])
