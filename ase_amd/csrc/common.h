@@ -60,6 +60,16 @@ template <> __device__ __forceinline__ f32s_t from_f32<f32s_t>(float x) { return
 template <> __device__ __forceinline__ f32h_t from_f32<f32h_t>(float x) { return f32h_t{x}; }
 // f16: RNE, saturating at the largest finite half (a scaled gradient that overflows must not turn into inf -> NaN)
 template <> __device__ __forceinline__ f16_t from_f32<f16_t>(float x) { return (f16_t)__builtin_amdgcn_fmed3f(x, -65504.f, 65504.f); }
+// (the median-of-three returns the MINIMUM of its operands when one of them is a NaN: a NaN is stored as -65504.  Producers whose
+//  values are bounded by construction and must keep a NaN - the normalised observations - use from_f32_plain)
+template <typename T> __device__ __forceinline__ T from_f32_plain(float x) { return from_f32<T>(x); }
+template <> __device__ __forceinline__ f16_t from_f32_plain<f16_t>(float x) { return (f16_t)x; }  // RNE, NaN stays NaN, no saturation
+
+// max(x, lo), min(x, hi) and clamp as torch.clamp_min / clamp_max / clamp have them: a NaN x stays NaN (fmaxf / fminf would
+// return the bound, and a NaN mu would leave the surrogate, the bound loss, the diversity loss and the diversity rows' gradient
+// finite, a NaN value the clipped critic loss, a NaN observation a plausible -5 for the policy, a NaN gradient norm the coefficient 1)
+__device__ __forceinline__ float floor_nan(float x, float lo) { return x < lo ? lo : x; }
+__device__ __forceinline__ float ceil_nan(float x, float hi) { return x > hi ? hi : x; }
 
 // ---- f32h_t shadows (ASE_F32H3): W * 2^e split into half hi / lo parts, packed [8 hi | 8 lo] per group of 8 consecutive elements of the
 // contracted dimension (written by ase_hip_refresh_shadow and ase_hip_apply_multi_v2, read by Mma<f32h_t>) -----------------------------

@@ -7,12 +7,6 @@ namespace {
 
 constexpr float kHalfLog2Pi = 0.91893853320467274178f;  // 0.5 * ln(2*pi)
 
-// max(x, lo), min(x, hi) and clamp as torch.clamp_min / clamp_max / clamp have them: a NaN x stays NaN (fmaxf / fminf would
-// return the bound, and a NaN mu would leave the surrogate, the bound loss, the diversity loss and the diversity rows' gradient
-// finite, a NaN value the clipped critic loss)
-__device__ __forceinline__ float floor_nan(float x, float lo) { return x < lo ? lo : x; }
-__device__ __forceinline__ float ceil_nan(float x, float hi) { return x > hi ? hi : x; }
-
 __global__ __launch_bounds__(256) void reduce_sum_kernel(const float* __restrict__ x, int64_t n, int square,
                                                          double* __restrict__ acc) {
     __shared__ double sm[16];

@@ -303,7 +303,7 @@ inline int grid_for(int64_t n) {
 __global__ __launch_bounds__(256) void clip_scale_kernel(float* __restrict__ g, int64_t n, const double* __restrict__ sqnorm,
                                                          float max_norm) {
     const float total = (float)sqrt(*sqnorm);
-    const float coef = fminf(max_norm / (total + 1e-6f), 1.0f);
+    const float coef = ceil_nan(max_norm / (total + 1e-6f), 1.0f);      // torch.clamp(max=1): a NaN norm makes every gradient NaN
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) g[i] *= coef;
 }
 

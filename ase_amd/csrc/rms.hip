@@ -129,12 +129,12 @@ __global__ __launch_bounds__(256) void rms_normalize_multi_kernel(RmsStreams S, 
     const f32x4 mu = *reinterpret_cast<const f32x4*>(S.mean[s] + j), sd = *reinterpret_cast<const f32x4*>(S.stdv[s] + j);
     f32x4 y;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) y[c] = fminf(fmaxf((x[c] - mu[c]) / sd[c], -5.f), 5.f);
+    for (int c = 0; c < 4; ++c) y[c] = ceil_nan(floor_nan((x[c] - mu[c]) / sd[c], -5.f), 5.f);
     if (S.out32[s]) *reinterpret_cast<f32x4*>(S.out32[s] + (int64_t)r * S.ld_out32[s] + j) = y;
     if constexpr (sizeof(T) == 2) {
         typename V16<T>::x4 v;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] = from_f32<T>(y[c]);
+        for (int c = 0; c < 4; ++c) v[c] = from_f32_plain<T>(y[c]);
         *reinterpret_cast<typename V16<T>::x4*>(reinterpret_cast<T*>(S.out[s]) + (int64_t)r * S.ld_out[s] + j) = v;
     } else {
         *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(S.out[s]) + (int64_t)r * S.ld_out[s] + j) = y;
@@ -177,8 +177,9 @@ __global__ __launch_bounds__(1024) void rms_finalize_kernel(double* __restrict__
     if (threadIdx.x == 0 && n_streams > 0) state[2 * D] = count0 + (double)n_streams * (double)count;
 }
 
+// (a normalised value is in [-5, 5] or NaN: half storage needs no saturating conversion, and the plain cast keeps the NaN)
 template <typename T> __device__ __forceinline__ void store_opt(void* base, int64_t ld, int r, int j, float v) {
-    if (base) reinterpret_cast<T*>(base)[(int64_t)r * ld + j] = from_f32<T>(v);
+    if (base) reinterpret_cast<T*>(base)[(int64_t)r * ld + j] = from_f32_plain<T>(v);
 }
 
 // grid (col tiles of 256, rows/4); block 256 = 64 cols x 4 rows  -> coalesced 256-B row segments
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(256) void rms_normalize_kernel(const float* __restr
     const float* row = src + p * ld_src;
     for (int j = blockIdx.x * 256 + tx; j < min(D, (int)(blockIdx.x + 1) * 256); j += 64) {
         float y = (row[j] - mean[j]) / stdv[j];
-        y = fminf(fmaxf(y, -5.f), 5.f);
+        y = ceil_nan(floor_nan(y, -5.f), 5.f);      // torch.clamp: a NaN observation stays NaN
         store_opt<T>(out0, ld0, r, j, y);
         store_opt<T>(out1, ld1, r, j, y);
         store_opt<T>(out2, ld2, r, j, y);
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(256) void rms_normalize4_kernel(const float* __rest
     const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + j), sd = *reinterpret_cast<const f32x4*>(stdv + j);
     f32x4 y;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) y[c] = fminf(fmaxf((x[c] - mu[c]) / sd[c], -5.f), 5.f);
+    for (int c = 0; c < 4; ++c) y[c] = ceil_nan(floor_nan((x[c] - mu[c]) / sd[c], -5.f), 5.f);
     void* outs[3] = {out0, out1, out2};
     const int64_t lds[3] = {ld0, ld1, ld2};
 #pragma unroll
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(256) void rms_normalize4_kernel(const float* __rest
         if constexpr (sizeof(T) == 2) {
             typename V16<T>::x4 v;
 #pragma unroll
-            for (int c = 0; c < 4; ++c) v[c] = from_f32<T>(y[c]);
+            for (int c = 0; c < 4; ++c) v[c] = from_f32_plain<T>(y[c]);
             *reinterpret_cast<typename V16<T>::x4*>(reinterpret_cast<T*>(outs[o]) + (int64_t)r * lds[o] + j) = v;
         } else {
             *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(outs[o]) + (int64_t)r * lds[o] + j) = y;
@@ -239,7 +240,7 @@ __global__ void rms_unnormalize_kernel(const double* __restrict__ state, const f
                                        float* __restrict__ y, int64_t n) {
     const float mean = (float)state[0], sd = sqrtf((float)state[1] + 1e-5f);
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float c = fminf(fmaxf(x[i], -5.f), 5.f);
+        const float c = ceil_nan(floor_nan(x[i], -5.f), 5.f);
         y[i] = sd * c + mean;
     }
 }

@@ -216,18 +216,24 @@ int ase_hip_rms_normalize_multi_v2(const float* const* srcs, const int64_t* ld_s
 int ase_hip_rms_finalize(double* state, int D, const double* sums, const int32_t* counts /* HOST */,
                          int n_streams, float* mean_out, float* std_out, void* stream);
 
-/* out_i[r, col_off_i + j] = clamp((x[map(r), j] - mean[j]) / std[j], -5, 5), i < 3 destinations. */
+/* out_i[r, col_off_i + j] = clamp((x[map(r), j] - mean[j]) / std[j], -5, 5), i < 3 destinations.  The clamp is torch.clamp's:
+ * +-inf -> +-5, a NaN is KEPT (a diverged observation must not reach the policy as a plausible -5).  A normalised value is in
+ * [-5, 5] or NaN, so 16-bit outputs (here and in ase_hip_rms_normalize_multi / _v2) are stored with a plain RNE cast: the NaN
+ * survives in all three storage types. */
 int ase_hip_rms_normalize(const float* src, int64_t ld_src, int D, const int32_t* idx, int remap_h,
                           int remap_n, int M, const float* mean, const float* std,
                           void* out0, int64_t ld0, void* out1, int64_t ld1, void* out2, int64_t ld2,
                           int dtype, void* stream);
 
 /* y = sqrt(f32(var)+1e-5) * clamp(x,-5,5) + f32(mean): RunningMeanStd(..., unnorm=True)
- * (learning/ase_agent.py:140-141,391-392), D == 1. */
+ * (learning/ase_agent.py:140-141,391-392), D == 1.  torch.clamp: a NaN x gives a NaN y. */
 int ase_hip_rms_unnormalize(const double* state, const float* x, float* y, int64_t n, void* stream);
 
 /* Generic row gather + cast: dst[r, 0:D] = src[map(r), 0:D]; dst dtype = dst_dtype
- * (learning/amp_datasets.py:21-22 for the small per-row tensors). */
+ * (learning/amp_datasets.py:21-22 for the small per-row tensors).  The cast is RNE; ASE_F16 saturating: beyond +-65504 and
+ * +-inf -> +-65504, and a NaN -> -65504 (the saturating conversion is a median of three with the two bounds, which returns the
+ * minimum of its operands when one is a NaN; every producer that stores ASE_F16 through it shares this, the GEMM epilogues
+ * included).  ASE_BF16 and ASE_F32 keep inf and NaN. */
 int ase_hip_gather_rows(const float* src, int64_t ld_src, int D, const int32_t* idx, int remap_h,
                         int remap_n, int M, void* dst, int64_t ld_dst, int dst_dtype, void* stream);
 
@@ -399,7 +405,8 @@ int ase_hip_finalize_scalars(const double* acc, float* out, int m_global, int am
  * ------------------------------------------------------------------------------------------- */
 /* Global-norm gradient clipping, torch.nn.utils.clip_grad_norm_(parameters, grad_norm) (learning/ase_agent.py:273-288,
  * truncate_grads): g *= min(1, max_norm / (sqrt(*sqnorm) + 1e-6)); *sqnorm = sum of g^2 over all parameters (device f64,
- * e.g. accumulated by ase_hip_reduce_sum with square = 1). */
+ * e.g. accumulated by ase_hip_reduce_sum with square = 1).  The min is torch.clamp(coef, max=1.0): a NaN norm is KEPT, the
+ * coefficient and with it every gradient become NaN (an infinite norm: coefficient 0). */
 int ase_hip_clip_scale(float* g, int64_t n, const double* sqnorm, float max_norm, void* stream);
 
 /* One small launch at the head of every optimisation step: + zeroes a second f64 buffer (the per-step partial statistics the

@@ -46,9 +46,10 @@ def _rows(idx, remap, M):
 
 
 def _store(v, dtype):
-    """f32 -> storage type as the kernels convert: round to nearest even; half saturates at its largest finite value."""
+    """f32 -> storage type as the kernels convert: round to nearest even; half saturates at its largest finite value, and the
+    saturating conversion (csrc/common.h from_f32<f16_t>, a median of three) stores a NaN as -65504."""
     if dtype == torch.float16:
-        v = v.clamp(-65504.0, 65504.0)
+        v = torch.where(torch.isnan(v), torch.full_like(v, -65504.0), v.clamp(-65504.0, 65504.0))
     return v.to(dtype)
 
 
@@ -234,9 +235,11 @@ class EmuBackend:
                 if coef != 0:
                     self.axpy(gW, W, coef)
                 self.adam(W, gW, mW, vW, opt_state)
-                self.adam(b, gb, mb, vb, opt_state)
+                if b is not None:                 # (desc[9] == 0: a layer without a bias)
+                    self.adam(b, gb, mb, vb, opt_state)
             self.refresh_shadow(W, ws, wts, ss, sd)
-            bs[:b.numel()] = b
+            if b is not None:
+                bs[:b.numel()] = b
 
     def gather_multi(self, desc, items, idx, remap, M):
         for src, D, dst in items:
@@ -291,7 +294,7 @@ class EmuBackend:
         y.copy_(torch.sqrt(state[1].float() + 1e-5) * torch.clamp(x, -5.0, 5.0) + state[0].float())
 
     def gather_rows(self, src, D, idx, remap, M, dst):
-        dst[:M, :D] = src[_rows(idx, remap, M), :D].to(dst.dtype)
+        dst[:M, :D] = _store(src[_rows(idx, remap, M), :D], dst.dtype)
 
     # ------------------------------------------------------------------ heads
     def reduce_sum(self, x, n, square, acc, slot):
@@ -520,8 +523,8 @@ class EmuBackend:
         w.sub_(step_size * (m / denom))
 
     def clip_scale(self, g, acc, slot, max_norm):
-        total = float(acc[slot]) ** 0.5
-        g.mul_(min(max_norm / (total + 1e-6), 1.0))
+        total = torch.sqrt(acc[slot]).float()
+        g.mul_(torch.clamp(float(max_norm) / (total + 1e-6), max=1.0))      # torch.clamp: a NaN norm stays NaN (csrc/common.h ceil_nan)
 
     def axpy(self, g, w, c):
         g.add_(c * w)
