@@ -11,7 +11,7 @@ __device__ __forceinline__ float act_sigmoid(float z) { return 1.f / (1.f + expf
 
 __device__ __forceinline__ float act_apply(int act, float z) {
     switch (act) {
-        case ASE_ACT_RELU: return fmaxf(z, 0.f);
+        case ASE_ACT_RELU: return z <= 0.f ? 0.f : z;      // a NaN stays, as in torch.relu; -0 -> +0
         case ASE_ACT_TANH: return tanhf(z);
         case ASE_ACT_SILU: return z * act_sigmoid(z);
         case ASE_ACT_ELU: return z > 0.f ? z : expm1f(z);

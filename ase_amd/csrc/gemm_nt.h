@@ -81,9 +81,11 @@ __device__ __forceinline__ f32x16 nt8_mfma(const i32x4& a, const i32x4& b, const
 // ---- row-per-lane epilogues (swapped MFMA operands): one 32 x 32 accumulator fragment of a lane = 16 outputs of ONE row, the columns
 // 8 g + 4 h + q (g = e >> 2, q = e & 3, h = lane >> 5).  Two outputs at a time on the packed instructions of gfx950:
 //     v_pk_fma_f32 (alpha * acc + bias) -> [bit-mask operand: v_bfe_i32 + v_and per output] -> v_cvt_pk_{bf16,f16}_f32 ->
-//     v_pk_max_i16 (ReLU on the packed 16-bit patterns: sign-magnitude formats order like integers, -0 included) ->
-//     [mask_out: v_pk_min_i16 with 1 = "stored value > 0", v_pk_lshlrev_b16 to its bit, v_or]
-// i.e. ~3 VALU operations per output where the scalar form of rounds 2-5 (per output: fma, max, select on the runtime activation
+//     ReLU as an IEEE-754 maximum, which KEEPS a NaN (torch.relu; v_pk_max_i16 on the packed patterns turned a NaN with the sign set
+//     into 0): bf16 v_maximum3_f32 before the conversion, f16 v_pk_minimum3_f16 / v_pk_maximum3_f16 after it (they are its saturation
+//     too - the same stored value as from_f32<f16_t> for every non-NaN input, see cvt_relu_pk16) ->
+//     [mask_out: "0 < stored <= inf" on the patterns (v_pk_sub_u16, v_pk_sub_u16 clamp, v_pk_min_u16), v_pk_lshlrev_b16 to its bit, v_or]
+// i.e. ~4 VALU operations per output (~3 with the integer ReLU, which dropped NaNs) where the scalar form of rounds 2-5 (per output: fma, max, select on the runtime activation
 // code, a one-sided cvt_pk + shift + or to pack, compare + select + shift-or for the mask bit) cost 8-10 - with ONE wave per SIMD
 // (or two in lock-step) nothing overlaps the epilogue, and at 256 outputs per lane it was 5-6 us of a 35-us launch (round 6).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -93,13 +95,19 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-template <typename T> __device__ __forceinline__ uint32_t cvt_pk16(f32x2 v);
-template <> __device__ __forceinline__ uint32_t cvt_pk16<bf16_t>(f32x2 v) {      // RNE
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+// max(v, lo) and the conversion of two outputs; lo = 0 (ReLU) or -inf (none).  A NaN stays a NaN in both storage types.
+template <typename T> __device__ __forceinline__ uint32_t cvt_relu_pk16(f32x2 v, float lo);
+template <> __device__ __forceinline__ uint32_t cvt_relu_pk16<bf16_t>(f32x2 v, float lo) {      // RNE
+    const f32x2 l = {lo, lo};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(__builtin_elementwise_maximum(v, l), bf16x2));
 }
-template <> __device__ __forceinline__ uint32_t cvt_pk16<f16_t>(f32x2 v) {       // RNE, saturating like from_f32<f16_t>
-    const f32x2 c = {__builtin_amdgcn_fmed3f(v[0], -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v[1], -65504.f, 65504.f)};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(c, f16x2));
+// RNE, saturating at +-65504: rounding first and clamping the half stores what from_f32<f16_t> (clamp, then round) stores - a value in
+// (65504, 65520) rounds to 65504 either way, one from 65520 on rounds to inf and is clamped back
+template <> __device__ __forceinline__ uint32_t cvt_relu_pk16<f16_t>(f32x2 v, float lo) {
+    const f16_t l16 = (f16_t)__builtin_amdgcn_fmed3f(lo, -65504.f, 65504.f);
+    const f16x2 hi = {(f16_t)65504.f, (f16_t)65504.f}, l = {l16, l16};
+    const f16x2 c = __builtin_elementwise_maximum(__builtin_elementwise_minimum(__builtin_convertvector(v, f16x2), hi), l);
+    return __builtin_bit_cast(uint32_t, c);
 }
 
 // ---- overflow detection of the dynamic loss scale, fused into the producers (round 6; rounds 4-5 re-read every half buffer of the step,
@@ -119,10 +127,10 @@ template <typename T> __device__ __forceinline__ bool ovf_hit(uint32_t run) {
 }
 
 // bias: the lane's 16 bias values of the fragment as 4 x f32x4 (columns 8 g + 4 h ..); w: the fragment's mask word >> 4 h (AUXK = 2);
-// relu_lo: packed lower bound of v_pk_max_i16 (0 = ReLU, -32768 = none); pk[g][0 / 1]: the packed outputs q = 0, 1 / 2, 3;
+// relu_lo: lower bound of the stored value (0 = ReLU, -inf = none); pk[g][0 / 1]: the packed outputs q = 0, 1 / 2, 3;
 // returns (MASK) the lane's 16 "stored > 0" bits at their places 8 g + 4 h + q of the fragment's 32-bit mask word
 template <typename T, int AUXK, bool MASK>
-__device__ __forceinline__ uint32_t rows_frag(const f32x16& c, const f32x4 (&bias)[4], uint32_t w, f32x2 al, i16x2 relu_lo, int h,
+__device__ __forceinline__ uint32_t rows_frag(const f32x16& c, const f32x4 (&bias)[4], uint32_t w, f32x2 al, float relu_lo, int h,
                                               uint32_t (&pk)[4][2]) {
     uint32_t mlo = 0, mhi = 0;
 #pragma unroll
@@ -138,11 +146,19 @@ __device__ __forceinline__ uint32_t rows_frag(const f32x16& c, const f32x4 (&bia
                 const i32x2 keep = {(int)__builtin_amdgcn_sbfe(w, 8 * g + 2 * pr, 1), (int)__builtin_amdgcn_sbfe(w, 8 * g + 2 * pr + 1, 1)};
                 v = __builtin_bit_cast(f32x2, __builtin_bit_cast(i32x2, v) & keep);
             }
-            const i16x2 o = __builtin_elementwise_max(__builtin_bit_cast(i16x2, cvt_pk16<T>(v)), relu_lo);
-            pk[g][pr] = __builtin_bit_cast(uint32_t, o);
-            if constexpr (MASK) {       // assumes ReLU (o >= 0, so min(o, 1) is 0 or 1): rows_epi() sends every other mask_out launch to the slab
-                const i16x2 one = {1, 1};
-                const u16x2 t = __builtin_bit_cast(u16x2, __builtin_elementwise_min(o, one));      // 1 where the stored value is > 0
+            pk[g][pr] = cvt_relu_pk16<T>(v, relu_lo);
+            if constexpr (MASK) {       // assumes ReLU (a pattern is +0 ... +inf or a NaN): rows_epi() sends every other mask_out launch to the slab
+                // 1 where the stored value is > 0, i.e. pattern - 1 < the pattern of +inf (unsigned: +0 wraps; a NaN of either sign is
+                // above), as inf - (pattern - 1) saturating at 0, then min with 1
+                // (as asm statements: written with __builtin_elementwise_sub_sat / _min hipcc turned the three packed operations into a
+                //  compare + select per 16-bit half)
+                constexpr uint32_t INF = std::is_same<T, f16_t>::value ? 0x7C007C00u : 0x7F807F80u;
+                const u16x2 one = {1, 1};
+                const uint32_t d = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, pk[g][pr]) - one);
+                uint32_t tw;
+                asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(tw) : "s"(INF), "v"(d));
+                asm("v_pk_min_u16 %0, %0, %1" : "+v"(tw) : "s"(0x00010001u));
+                const u16x2 t = __builtin_bit_cast(u16x2, tw);
                 const u16x2 sh = {(unsigned short)((g & 1) * 8 + 2 * pr), (unsigned short)((g & 1) * 8 + 2 * pr + 1)};
                 const uint32_t m = __builtin_bit_cast(uint32_t, t << sh);
                 if (g < 2) mlo |= m; else mhi |= m;
@@ -166,8 +182,7 @@ __device__ __forceinline__ void nt8_epilogue_rows_impl(const NTParams& p, f32x16
                                                        const uint32_t (&bits)[NI][NJ]) {
     const int r = lane & 31, h = lane >> 5;
     const f32x2 al = {p.alpha, p.alpha};
-    const short lo = (p.act == ASE_ACT_RELU) ? (short)0 : (short)-32768;
-    const i16x2 relu_lo = {lo, lo};
+    const float relu_lo = (p.act == ASE_ACT_RELU) ? 0.f : -__builtin_inff();
     uint32_t ovf = 0;
     f32x4 bias[NJ][4];
 #pragma unroll

@@ -283,7 +283,7 @@ __device__ __forceinline__ double nt_epilogue_impl(const NTParams& p, f32x16 (&a
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     float v = p.alpha * acc[ic + ii][j][e] + bias;
-                    if (p.act == ASE_ACT_RELU) v = fmaxf(v, 0.f);
+                    if (p.act == ASE_ACT_RELU) v = v <= 0.f ? 0.f : v;       // torch.relu: a NaN stays (fmaxf returns 0); -0 -> +0 as fmaxf and the row-per-lane maximum
                     else if (p.act == ASE_ACT_TANH) v = tanhf(v);
                     slab[(ii * 32 + row_hi + (e & 3) + 8 * (e >> 2)) * WCOLS + jj * 32 + col_in] = v;
                 }
@@ -427,8 +427,7 @@ __device__ __forceinline__ void nt_epilogue_rows_impl(const NTParams& p, f32x16 
                                                       const uint32_t (&bits)[FM][FN]) {
     const int r = lane & 31, h = lane >> 5;
     const f32x2 al = {p.alpha, p.alpha};
-    const short lo = (p.act == ASE_ACT_RELU) ? (short)0 : (short)-32768;
-    const i16x2 relu_lo = {lo, lo};
+    const float relu_lo = (p.act == ASE_ACT_RELU) ? 0.f : -__builtin_inff();
     uint32_t ovf = 0;
 #pragma unroll
     for (int j = 0; j < FN; ++j) {

@@ -94,6 +94,15 @@ int ase_hip_debug_nt_profile_clock(int shader_clock);
  *   saturate at +-65504 where autocast would produce inf): GradScaler's found_inf, detected by the producer instead of a pass that
  *   re-reads every buffer of the step (ase_hip_scaler_check).  The same convention for every `*_dev` argument below; the loss heads
  *   report their stored head gradients, ase_hip_gemm_tn(_grouped) and ase_hip_sqnorm only read the factor.
+ *   NON-FINITE values pass through as torch's nn.Linear + activation pass them: a NaN in A, B or bias makes every element of its
+ *   row / column NaN (with a mask operand: where the mask keeps the element - ASE_AUX_RELU_MASK / ASE_AUX_RELU_BITS SELECT, so a
+ *   masked-out element is 0 even where the product is NaN or inf, unlike torch's grad * mask) and NO activation turns it into a number - ASE_ACT_RELU is torch.relu, max(z, 0) that KEEPS a NaN (so an
+ *   ASE_F32H3 operand beyond half's range stays loud behind ReLU too), tanh(+-inf) = +-1, sigmoid(+-inf) = 1 / 0, relu(-inf) = 0, +inf
+ *   stays +inf.  ASE_F32, ASE_F32X3, ASE_F32H3, ASE_BF16 and out_f32 store the NaN / inf as such; ASE_F16 saturates: +-inf -> +-65504,
+ *   and a NaN is stored as NaN by the launches that convert two outputs at a time (16-bit output, no colsum, act <= RELU, no value
+ *   mask operand, N a whole number of wave tiles) and as -65504 by every other launch (the shared conversion, see
+ *   ase_hip_gather_rows) - either way a scale record counts it.  mask_out's bit is (stored > 0): 0 for a NaN; a colsum entry is NaN
+ *   where a stored value of its column is.  Elements the non-finite inputs do not reach are bitwise what they are without them.
  * Replaces: nn.Linear + activation forward  (learning/ase_network_builder.py:255-259,305-324,
  *   learning/amp_network_builder.py:81-84), and autograd's data-gradient of the same layers
  *   (B = the transposed weight shadow; mask = derivative of the previous activation), and the

@@ -88,10 +88,15 @@ def _twin_factors(act, t):
     return d1, torch.where(d1 != 0, d2 / d1, torch.zeros_like(d1))
 
 
-def half_split(x, e):
-    """x (f32) -> (hi, lo) as the ASE_F32H3 kernels form them: sx = x * 2^e, hi = half(sx) saturating at +-65504, lo = half(sx - hi)
-    (csrc/gemm_nt_kernels.h split_f16), both returned as f64 values."""
+def half_split(x, e, saturate=True):
+    """x (f32) -> (hi, lo) as the ASE_F32H3 kernels form them: sx = x * 2^e, hi = half(sx), lo = half(sx - hi), both returned as f64
+    values.  saturate: the SHADOWS' split (csrc/common.h split_half) clamps to +-65504; the A operand's split in the kernel's loop
+    (csrc/gemm_nt_kernels.h split_f16) is a plain cast: beyond half's range hi is inf and the product NaN (include/ase_hip.h:
+    "overflow turns the output into NaN")."""
     sx = x.float() * (2.0 ** e)
+    if not saturate:
+        hi = sx.half()
+        return hi.double(), (sx - hi.float()).half().double()
     hi = sx.clamp(-65504.0, 65504.0).half()
     lo = (sx - hi.float()).clamp(-65504.0, 65504.0).half()
     return hi.double(), lo.double()
@@ -107,7 +112,7 @@ def unpack_split(buf, rows, cols, e):
 
 def x3_half_product(a, b, ea, eb):
     """a @ b^T as the three-product form hi*hi + hi*lo + lo*hi of the scaled half splits, exact accumulation (f64), scale undone."""
-    ah, al = half_split(a, ea)
+    ah, al = half_split(a, ea, saturate=False)
     bh, bl = half_split(b, eb)
     v = ah @ bh.t() + ah @ bl.t() + al @ bh.t()
     return (v * 2.0 ** -(ea + eb)).float()

@@ -620,6 +620,10 @@ def test_gemm_x3_half_split_rejects_bad_scales():
     bh.refresh_shadow(torch.ones(64, 64).cuda(), B, None, 64, 64, x3_exp=11)
     bh.gemm_nt(A, B, C_, 64, 64, 64, x3_exps=(12, 11))
     assert bool(torch.isnan(C_[3]).all()) and bool(torch.isfinite(C_[4]).all())
+    # ... behind ReLU too (the penalty's value path launches the half split with ACT_RELU): torch.relu keeps a NaN
+    C_.zero_()
+    bh.gemm_nt(A, B, C_, 64, 64, 64, x3_exps=(12, 11), act=L.ACT_RELU)
+    assert bool(torch.isnan(C_[3]).all()) and bool(torch.isfinite(C_[4]).all())
 
 
 @pytest.mark.parametrize('dt', DT)
