@@ -72,11 +72,15 @@ extern "C" int ase_hip_build_amp_obs(const float* root_pos, const float* root_ro
                                      const float* key_body_pos, int n_envs, int n_dof, int n_key,
                                      const int32_t* dof_offsets, int n_joints, int local_root_obs, int root_height_obs,
                                      float* hist, int n_steps, int shift, void* stream) {
-    ASE_CHECK_ARG(root_pos && root_rot && root_vel && root_ang_vel && dof_pos && dof_vel && key_body_pos && hist && dof_offsets,
+    ASE_CHECK_ARG(root_pos && root_rot && root_vel && root_ang_vel && dof_pos && dof_vel && (key_body_pos || n_key == 0) && hist &&
+                      dof_offsets,
                   "build_amp_obs: null operand");
     ASE_CHECK_ARG(n_envs > 0 && n_dof > 0 && n_key >= 0 && n_steps >= 1 && n_joints >= 1 && n_joints <= kMaxJoints,
                   "build_amp_obs: bad sizes (envs %d, dofs %d, joints %d)", n_envs, n_dof, n_joints);
     AmpObsArgs a;
+    a.F = 13 + 6 * n_joints + n_dof + 3 * n_key;
+    ASE_CHECK_ARG(kEnvPerBlock * (a.F + 1) * (int)sizeof(float) <= 64 * 1024,
+                  "build_amp_obs: frame of %d floats does not fit the staging tile", a.F);
     a.root_pos = root_pos; a.root_rot = root_rot; a.root_vel = root_vel; a.root_ang_vel = root_ang_vel;
     a.dof_pos = dof_pos; a.dof_vel = dof_vel; a.key_pos = key_body_pos; a.hist = hist;
     a.N = n_envs; a.D = n_dof; a.K = n_key; a.J = n_joints; a.S = n_steps;
@@ -89,9 +93,7 @@ extern "C" int ase_hip_build_amp_obs(const float* root_pos, const float* root_ro
         }
     }
     ASE_CHECK_ARG(dof_offsets[0] == 0 && dof_offsets[n_joints] == n_dof, "build_amp_obs: dof_offsets do not cover the dofs");
-    a.F = 13 + 6 * n_joints + n_dof + 3 * n_key;
     const int lds = kEnvPerBlock * (a.F + 1) * (int)sizeof(float);
-    ASE_CHECK_ARG(lds <= 64 * 1024, "build_amp_obs: frame of %d floats does not fit the staging tile", a.F);
     if (shift && n_steps > 1) {
         const int64_t cols = (int64_t)n_envs * a.F;
         ASE_LAUNCH(amp_hist_shift_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, (hipStream_t)stream, hist,
@@ -116,6 +118,7 @@ extern "C" int ase_hip_motion_state(const float* gts, const float* grs, const fl
                   "motion_state: null operand");
     ASE_CHECK_ARG(n > 0 && n_bodies > 0 && n_joints >= 1 && n_joints <= kMaxJoints && n_key >= 0 && n_key <= kMaxJoints,
                   "motion_state: bad sizes (n %d, bodies %d, joints %d, key bodies %d)", n, n_bodies, n_joints, n_key);
+    ASE_CHECK_ARG(dof_offsets[0] == 0, "motion_state: dof_offsets do not cover the dofs (first offset %d)", dof_offsets[0]);
     MotionArgs a;
     MotionClips& c = a.c;
     c.gts = gts; c.grs = grs; c.lrs = lrs; c.grvs = grvs; c.gravs = gravs; c.dvs = dvs;

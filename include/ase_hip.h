@@ -532,7 +532,17 @@ int ase_hip_apply_multi_v2(const int64_t* desc, int n_layers, const int64_t* des
  * (heading-local when local_root_obs), heading-local root velocity and angular velocity, per joint tangent + normal of
  * its rotation (3-dof joints: exponential map; 1-dof: hinge about y), dof velocities, heading-local key body
  * positions}.  shift != 0: slots move one step into the past first; the new frame takes slot 0.  Quaternions xyzw.
- * dof_offsets: HOST int32[n_joints + 1].
+ * dof_offsets: HOST int32[n_joints + 1], starting at 0 and ending at n_dof, joints of 1 or 3 dofs, n_joints in 1..32.
+ * n_key == 0: no key columns, key_body_pos may be NULL.  F <= 255 (the 64 x (F + 1) float staging tile is 64 KB at F = 255);
+ * a wider frame is refused.  n_steps == 1 with shift: nothing but slot 0 changes.
+ * Pinned by tests/test_gpu_amp_obs.py (the reference's values, tests/ref_amp_obs.py): column 0, the dof velocity columns
+ * and every shifted slot are copies, bit for bit.  An exponential map whose wrapped length is at most 1e-5 - and any map
+ * with a NaN or infinite component, or a length that overflows f32 (|e| ~ 1e30: sin(inf) is NaN and NaN > 1e-5 is false)
+ * - is the identity rotation (1, 0, 0, 0, 0, 1), not NaN.  A NaN or infinite hinge angle gives NaN in that joint's six
+ * columns; in root_rot, NaN in every root and key column but column 0; in root_vel, root_ang_vel or a key position,
+ * that vector's three columns and no other: all NaN for a NaN or an infinite x / y component (0 * inf inside the
+ * rotation about z), NaN, NaN and an infinity or NaN for an infinite z component.
+ * A root rotation whose x axis turns exactly vertical has heading atan2(0, 0) = 0.
  * Replaces: build_amp_observations + _update_hist_amp_obs (env/tasks/humanoid_amp.py:248-266,280-316),
  *   dof_to_obs (env/tasks/humanoid.py:523-552). */
 int ase_hip_build_amp_obs(const float* root_pos, const float* root_rot, const float* root_vel,
@@ -546,7 +556,16 @@ int ase_hip_build_amp_obs(const float* root_pos, const float* root_rot, const fl
  * grvs / gravs [frames, 3], dof velocities dvs [frames, D]; per motion: lengths [s], num_frames, dt, length_starts):
  * frame pair + blend, linear interpolation of positions, spherical interpolation of rotations, local rotations ->
  * dof positions (3-dof: exponential map, 1-dof: angle about y).  Outputs feed ase_hip_build_amp_obs (demo stream).
- * dof_body_ids / dof_offsets / key_body_ids: HOST int32 arrays; everything else device memory.
+ * dof_body_ids / dof_offsets / key_body_ids: HOST int32 arrays; everything else device memory.  dof_offsets start at 0
+ * (refused otherwise), joints of 1 or 3 dofs, body ids inside [0, n_bodies); n_key == 0: key_pos and key_body_ids may be
+ * NULL.  motion_ids are NOT checked on the device.
+ * Times are used as given (pinned by tests/test_gpu_amp_obs.py): outside [0, length] the frame pair clips to the first
+ * two frames / the last frame twice while the blend (t - i0 dt) / dt keeps following t, so positions and rotations
+ * EXTRAPOLATE below 0 exactly as the reference's do (the demo fetch and the reset history ask for times down to
+ * -(n_steps - 1) dt) and stay on the last frame above the length; velocities are copies of frame i0.  slerp: neighbours
+ * with a negative dot product are negated first, sin(half angle) < 0.001 gives the midpoint 0.5 q0 + 0.5 q1 whatever
+ * the blend, a dot product >= 1 gives q0.  A local rotation with |w| >= 1 (sin_theta <= 1e-5, or NaN from w > 1) gives
+ * dof positions 0; w < 0 gives angles past pi, wrapped into (-pi, pi]; a hinge angle is wrapped a second time.
  * Replaces: MotionLib.get_motion_state (utils/motion_lib.py:122-172,263-272,296-325). */
 int ase_hip_motion_state(const float* gts, const float* grs, const float* lrs, const float* grvs, const float* gravs,
                          const float* dvs, int n_bodies, const float* lengths, const int32_t* num_frames, const float* dt,
