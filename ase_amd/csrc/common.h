@@ -35,6 +35,16 @@ void ase_set_error(const char* fmt, ...);
         }                                                                   \
     } while (0)
 
+// Dynamic-LDS opt-in of kernel KERN (`bytes` past the default 64 KiB), asked of the runtime ONCE per kernel instantiation: the outcome is
+// a function-local static of this instantiation, so its initialisation is thread-safe, and a failure is kept - every later launch of
+// that kernel reports it again without asking the runtime a second time.
+template <auto KERN> inline int ase_dynamic_lds(const char* name, int bytes) {
+    static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) return ASE_OK;
+    ase_set_error("%s: dynamic LDS opt-in (%d bytes) failed: %s", name, bytes, hipGetErrorString(e));
+    return ASE_ELAUNCH;
+}
+
 // f32 storage whose matrix products run as THREE bf16 MFMAs on a hi/lo split (a = hi + lo, hi = bf16(a),
 // lo = bf16(a - hi); a*b ~= hi*hi + hi*lo + lo*hi): ~16 mantissa bits per operand at 1/3 of the bf16 MFMA rate
 // instead of the 1/16 of the exact-f32 MFMA (gfx950 has no TF32).

@@ -59,6 +59,39 @@ struct NTParams {
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
+// ---- LDS-DMA of the phased kernels and the 4-wave kernel (NT and TN) --------------------------------------------------
+// DMA pieces go out as `buffer_load_dwordx4 ... lds` (round 6): an SGPR buffer descriptor per operand, ONE 32-bit offset register per
+// piece (the 64-bit per-lane addresses of global_load_lds cost 16 registers and two VALU adds per piece), the K-tile's byte offset as
+// the instruction's SGPR offset, M0 = LDS destination.  What it buys is REGISTERS: the kernel's allocation decides how many of the 512
+// registers per SIMD its two waves leave to the small HBM-bound kernels of the step's other branches, which run in exactly that space
+// (profiles/r06_nt_policy_ab.txt: a matrix kernel that owns the whole file costs the update 2.2 %).
+//
+// a whole operand as a raw buffer: stride 0, byte extent 2^31 - 1, 32-bit data format (rows past the operand are clamped in the
+// callers' per-lane offsets, not by the descriptor)
+__device__ __forceinline__ i32x4 raw_buffer(const void* base) {
+    const uint64_t a = (uint64_t)(uintptr_t)base;
+    return i32x4{(int)(uint32_t)a, (int)(uint32_t)(a >> 32), (int)0x7FFFFFFF, 0x00020000};
+}
+// one DMA piece of 64 lanes x 16 bytes: lane l reads rs base + voff + soff and lands at LDS byte address M0 + 16 l.
+// M0 = the wave-uniform lds_s (s_mov_b32), or lds_s + IMM with ADD (s_add_u32, which also writes SCC; ADD with IMM = 0 stays an
+// s_add_u32).  M0 is written and read inside ONE statement and declared clobbered: the same kernels fetch their mask words with
+// __builtin_amdgcn_global_load_lds, whose M0 the compiler manages itself and may otherwise keep live across this statement.
+// (hipcc reserves M0 and warns about the clobber - "may not be preserved across the asm statement", which is exactly what is declared)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+#define LDS_DMA16_ASM(SET_M0, ...)                                            \
+    asm volatile(SET_M0 "\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"          \
+                 :                                                              \
+                 : "s"(lds_s), "v"(voff), "s"(rs), "s"(soff), "n"(IMM)          \
+                 : "memory", "m0", ##__VA_ARGS__)
+template <int IMM = 0, bool ADD = (IMM != 0)>
+__device__ __forceinline__ void lds_dma16(uint32_t lds_s, uint32_t voff, i32x4 rs, uint32_t soff) {
+    if constexpr (ADD) LDS_DMA16_ASM("s_add_u32 m0, %0, %4", "scc");
+    else LDS_DMA16_ASM("s_mov_b32 m0, %0");
+}
+#undef LDS_DMA16_ASM
+#pragma clang diagnostic pop
+
 // SW: operands swapped in the MFMA (D = B-fragment x A-fragment): the accumulator then holds the TRANSPOSED 32 x 32
 // block - a lane owns one output ROW and 4 x 4 consecutive columns - which nt8_epilogue_rows stores straight from
 // registers (no LDS transposition).
@@ -265,6 +298,22 @@ __device__ __forceinline__ void nt8_sync_out() {                    // end of th
     __builtin_amdgcn_s_setprio(0);
     NT8_BARRIER();
 }
+
+// ---- debug phase stamps (ase_hip_debug_nt_profile): thread 0 writes prof[slot]; prof null = off.  Stamps 0 - 2 open the prologue, the
+// main loop (optionally in shader clocks) and the epilogue; NT_PROF_CLOSE is stamp 3, taken once every store of the workgroup has retired.
+// (macros: as inline functions - the same statements - hipcc allocated the scalar registers of all three phased kernels differently)
+#define NT_PROF_STAMP(prof, tid, slot, shader_clk)                                                              \
+    do {                                                                                                        \
+        if ((prof) && (tid) == 0) (prof)[slot] = (shader_clk) ? (unsigned long long)clock64() : wall_clock64(); \
+    } while (0)
+#define NT_PROF_CLOSE(prof, tid, slot)                         \
+    do {                                                       \
+        if (prof) {                                            \
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   \
+            __syncthreads();                                   \
+            if ((tid) == 0) (prof)[slot] = wall_clock64();     \
+        }                                                      \
+    } while (0)
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 extern unsigned long long* g_nt_prof;      // tuning aid, see ase_hip_debug_nt_profile (defined in gemm.hip)

@@ -58,18 +58,11 @@ __device__ __forceinline__ void nt4_retire8(i32x4 (&f0)[4], i32x4 (&f1)[4]) {
                  :
                  : "memory");
 }
-// one DMA piece: M0 = wave-uniform LDS destination, lane l lands at M0 + 16 l
-template <int IMM> __device__ __forceinline__ void nt4_dma(uint32_t lds_s, uint32_t voff, i32x4 rs, uint32_t soff) {
-    asm volatile("s_add_u32 m0, %0, %1\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds"
-                 :
-                 : "s"(lds_s), "n"(IMM), "v"(voff), "s"(rs), "s"(soff)
-                 : "memory", "scc");
-}
 
-// DMA piece q of operand A / B into the buffer L.dst* points at, K-tile byte offset soff
+// DMA piece q of operand A / B into the buffer L.dst* points at (M0 = L.dst* + q * 4096: every piece an s_add_u32), K-tile byte offset soff
 template <int q, bool isB>
 __device__ __forceinline__ void nt4_piece(const NT4L& L, i32x4 rsA, i32x4 rsB, uint32_t soff) {
-    nt4_dma<q * 4096>(isB ? L.dstB : L.dstA, isB ? L.voffB[q] : L.voffA[q], isB ? rsB : rsA, soff);
+    lds_dma16<q * 4096, true>(isB ? L.dstB : L.dstA, isB ? L.voffB[q] : L.voffA[q], isB ? rsB : rsA, soff);
 }
 template <int... Q>
 __device__ __forceinline__ void nt4_tile_dma(const NT4L& L, i32x4 rsA, i32x4 rsB, uint32_t soff, std::integer_sequence<int, Q...>) {
@@ -175,15 +168,10 @@ __global__ __launch_bounds__(256) void gemm_nt4_kernel(NTParams p) {
     const int tile = xcd_remap(blockIdx.x, nwg);
     const int bm0 = (tile / p.tiles_n) * BM, bn0 = (tile % p.tiles_n) * 256;
 
-    if (p.prof && tid == 0) p.prof[blockIdx.x * 4 + 0] = wall_clock64();
+    NT_PROF_STAMP(p.prof, tid, blockIdx.x * 4 + 0, false);
     // whole operands as raw buffers (stride 0, byte extent): rows past M / N are CLAMPED to the last row in the per-lane offsets (their
     // products only reach outputs that are never stored)
-    i32x4 rsA, rsB;
-    {
-        const uint64_t a = (uint64_t)(uintptr_t)p.A, b = (uint64_t)(uintptr_t)p.B;
-        rsA = i32x4{(int)(uint32_t)a, (int)(uint32_t)(a >> 32), (int)0x7FFFFFFF, 0x00020000};
-        rsB = i32x4{(int)(uint32_t)b, (int)(uint32_t)(b >> 32), (int)0x7FFFFFFF, 0x00020000};
-    }
+    const i32x4 rsA = raw_buffer(p.A), rsB = raw_buffer(p.B);
     NT4L L;
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem;          // (the one LDS object of the kernel: offset 0, so ^ 65536 flips buffers)
     {
@@ -245,7 +233,7 @@ __global__ __launch_bounds__(256) void gemm_nt4_kernel(NTParams p) {
     }
     L.dstA ^= 65536u; L.dstB ^= 65536u;         // the loop's first DMA (K-tile 2) refills buffer 0
     NT8_BARRIER();
-    if (p.prof && tid == 0) p.prof[blockIdx.x * 4 + 1] = p.prof_clk ? (unsigned long long)clock64() : wall_clock64();
+    NT_PROF_STAMP(p.prof, tid, blockIdx.x * 4 + 1, p.prof_clk);
     i32x4 FA[4][4], FB[4][4];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -266,7 +254,7 @@ __global__ __launch_bounds__(256) void gemm_nt4_kernel(NTParams p) {
         NT4Ktile<T, false, false> k{acc, FA, FB, L, rsA, rsB, 0u};
         k.run(std::make_integer_sequence<int, 64>{});
     }
-    if (p.prof && tid == 0) p.prof[blockIdx.x * 4 + 2] = p.prof_clk ? (unsigned long long)clock64() : wall_clock64();
+    NT_PROF_STAMP(p.prof, tid, blockIdx.x * 4 + 2, p.prof_clk);
 
     uint32_t row_bits[4][4];
     if (masked) {
@@ -278,26 +266,14 @@ __global__ __launch_bounds__(256) void gemm_nt4_kernel(NTParams p) {
         nt8_epilogue_rows<T, 2, 4>(p, acc, lane, bm0 + wr * 128, bn0 + wc * 128, row_bits);
     } else
         nt8_epilogue_rows<T, 0, 4>(p, acc, lane, bm0 + wr * 128, bn0 + wc * 128, row_bits);
-    if (p.prof) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) p.prof[blockIdx.x * 4 + 3] = wall_clock64();
-    }
+    NT_PROF_CLOSE(p.prof, tid, blockIdx.x * 4 + 3);
 }
 
 
 template <typename T> int launch_nt4(const NTParams& p0, hipStream_t stream) {
     constexpr int lds = 2 * 512 * 128 + 4 * 2048;          // ring + 2 KiB of mask words per wave
-    static bool attr_done = false;
-    auto kern = gemm_nt4_kernel<T>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) {
-            ase_set_error("gemm_nt4: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return ASE_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    constexpr auto kern = gemm_nt4_kernel<T>;
+    if (const int rc = ase_dynamic_lds<kern>("gemm_nt4", lds)) return rc;
     NTParams p = p0;
     p.prof = g_nt_prof;
     p.prof_clk = g_nt_prof_clk;

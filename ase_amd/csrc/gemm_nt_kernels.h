@@ -603,17 +603,8 @@ int launch_nt(const NTParams& p0, hipStream_t stream) {
     constexpr int slab = WGM * WGN * (FM * 32) * ((FN > 2 ? 2 : FN) * 32) * 4;
     constexpr int lds = ring > slab ? ring : slab;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static bool attr_done = false;
-    auto kern = gemm_nt_kernel<T, WGM, WGN, FM, FN, RB, S, WPE, SW, FUSE>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) {
-            ase_set_error("gemm_nt: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return ASE_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    constexpr auto kern = gemm_nt_kernel<T, WGM, WGN, FM, FN, RB, S, WPE, SW, FUSE>;
+    if (const int rc = ase_dynamic_lds<kern>("gemm_nt", lds)) return rc;
     NTParams p = p0;
     p.tiles_m = (p.M + BM - 1) / BM;
     p.tiles_n = (p.N + BN - 1) / BN;
@@ -650,11 +641,7 @@ int launch_nt(const NTParams& p0, hipStream_t stream) {
 //   behind a lab switch in this file up to commit 9f99095; their results are in profiles/r03_lab_*.log, r04_lab_mfma_shape.txt.)
 // ------------------------------------------------------------------------------------------------
 
-// DMA pieces go out as `buffer_load_dwordx4 ... lds` (round 6, like gemm_nt4.h): an SGPR buffer descriptor per operand, ONE 32-bit
-// offset register per piece (the 64-bit per-lane addresses of global_load_lds cost 16 registers and two VALU adds per piece), the
-// K-tile's byte offset as the instruction's SGPR offset, M0 = LDS destination.  What it buys is REGISTERS: the kernel's allocation
-// decides how many of the 512 registers per SIMD its two waves leave to the small HBM-bound kernels of the step's other branches,
-// which run in exactly that space (profiles/r06_nt_policy_ab.txt: a matrix kernel that owns the whole file costs the update 2.2 %).
+// (DMA pieces: lds_dma16 in gemm_nt.h, like gemm_nt4.h and the TN twin)
 struct NT8Lane {
     uint32_t voff[4][2];       // per-lane byte offset (row * ld + swizzled chunk) of unit kind x piece from its operand's base
     uint32_t dst[4][2];        // wave-uniform LDS byte ADDRESS of the piece in K-tile buffer 0 (buffer 1: + 65536)
@@ -662,18 +649,15 @@ struct NT8Lane {
     i32x4 rsA, rsB;            // raw buffer descriptors of the two operands (SGPRs)
 };
 
-__device__ __forceinline__ void nt8_dma(uint32_t lds_s, uint32_t voff, i32x4 rs, uint32_t soff) {
-    asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" : : "s"(lds_s), "v"(voff), "s"(rs), "s"(soff) : "memory");
-}
 template <int KIND>
 __device__ __forceinline__ void nt8_piece(const NT8Lane& L, int g, int tile) {
     constexpr bool isB = (KIND == 1 || KIND == 2);
-    nt8_dma(__builtin_amdgcn_readfirstlane(L.dst[KIND][g] + (uint32_t)(tile & 1) * 65536u), L.voff[KIND][g], isB ? L.rsB : L.rsA,
-            (uint32_t)tile * 128u);
+    lds_dma16(__builtin_amdgcn_readfirstlane(L.dst[KIND][g] + (uint32_t)(tile & 1) * 65536u), L.voff[KIND][g], isB ? L.rsB : L.rsA,
+              (uint32_t)tile * 128u);
 }
 
 template <int KIND>
-__device__ __forceinline__ void nt8_issue(const NT8Lane& L, char* smem, int tile) {
+__device__ __forceinline__ void nt8_issue(const NT8Lane& L, int tile) {
 #pragma unroll
     for (int g = 0; g < 2; ++g) nt8_piece<KIND>(L, g, tile);
 }
@@ -690,33 +674,16 @@ __device__ __forceinline__ void nt8_read(i32x4 (&f)[4], const char* base, const 
 // wait and a priority switch (~70 of the ~650 cycles a phase took, round 5's cycle stamps).  With two MFMAs (64 cycles of
 // matrix-pipe work) still to issue behind the barrier, the pipe stays fed across the hand-over.  Nothing those two MFMAs touch
 // is shared: their operands are in registers since the phase's first barrier.
-template <typename T, int KIND, bool SW>
+// NA = 1 (the 192 x 256 tile's third A block): 4 MFMAs of a0 on c0 alone, same DMA / barrier placement; c1 and a1 are not touched.
+// (accumulators by reference: handed over as the array and two indices hipcc moved the 256-row kernels' accumulator registers)
+template <typename T, int KIND, bool SW, int NA = 2>
 __device__ __forceinline__ void nt8_mma_issue(f32x16& c0, f32x16& c1, const i32x4 (&a0)[4], const i32x4 (&a1)[4],
-                                              const i32x4 (&b)[4], const NT8Lane& L, char* smem, int tile, bool live) {
+                                              const i32x4 (&b)[4], const NT8Lane& L, int tile, bool live) {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
         if (ks == 3) NT8_BARRIER();                       // (closes the phase: see above)
         c0 = nt8_mfma<T, SW>(a0[ks], b[ks], c0);
-        c1 = nt8_mfma<T, SW>(a1[ks], b[ks], c1);
-        if (ks == 0 || ks == 2) {
-            __builtin_amdgcn_sched_barrier(0);
-            if (live) nt8_piece<KIND>(L, ks >> 1, tile);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-// ... and its half-height twin for the 192 x 256 tile's third A block: 4 MFMAs on one accumulator, same DMA / barrier placement
-template <typename T, int KIND, bool SW>
-__device__ __forceinline__ void nt8_mma_issue1(f32x16& c0, const i32x4 (&a0)[4], const i32x4 (&b)[4], const NT8Lane& L, char* smem,
-                                               int tile, bool live) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        if (ks == 3) NT8_BARRIER();
-        c0 = nt8_mfma<T, SW>(a0[ks], b[ks], c0);
+        if constexpr (NA == 2) c1 = nt8_mfma<T, SW>(a1[ks], b[ks], c1);
         if (ks == 0 || ks == 2) {
             __builtin_amdgcn_sched_barrier(0);
             if (live) nt8_piece<KIND>(L, ks >> 1, tile);
@@ -731,7 +698,7 @@ __device__ __forceinline__ void nt8_mma_issue1(f32x16& c0, const i32x4 (&a0)[4],
 // one K-tile = 4 phases.  TAIL = false: every issued unit exists (t + 2 < nk) and the waits are compile-time counts.
 // NI = 4: wave tile 128 x 64 (256 x 256 tile); NI = 3: wave tile 96 x 64 (192 x 256 tile) - phases 2 and 3 multiply ONE A block
 template <typename T, bool TAIL, bool SW, int NI = 4>
-__device__ __forceinline__ void nt8_ktile(int t, int nk, const NT8Lane& L, char* smem, const char* aP, const char* bP,
+__device__ __forceinline__ void nt8_ktile(int t, int nk, const NT8Lane& L, const char* aP, const char* bP,
                                           f32x16 (&acc)[NI][2], i32x4 (&a0)[4], i32x4 (&a1)[4], i32x4 (&b0)[4],
                                           i32x4 (&b1)[4]) {
     constexpr int RB = 128;
@@ -744,25 +711,23 @@ __device__ __forceinline__ void nt8_ktile(int t, int nk, const NT8Lane& L, char*
     if (!TAIL) wait_dma_units<3>();
     else wait_dma_units_rt(min(U, 4 * t + 6) - (4 * t + 3));
     nt8_sync_in();
-    nt8_mma_issue<T, 2, SW>(acc[0][0], acc[1][0], a0, a1, b0, L, smem, t + 1, l1);
+    nt8_mma_issue<T, 2, SW>(acc[0][0], acc[1][0], a0, a1, b0, L, t + 1, l1);
     // ---- phase 1: B fragment 1 -> quadrant (0, 1); issues A1 of K-tile t + 1
     nt8_read(b1, bP + 32 * RB, L);
     if (!TAIL) wait_dma_units<3>();
     else wait_dma_units_rt(min(U, 4 * t + 7) - (4 * t + 4));
     nt8_sync_in();
-    nt8_mma_issue<T, 3, SW>(acc[0][1], acc[1][1], a0, a1, b1, L, smem, t + 1, l1);
+    nt8_mma_issue<T, 3, SW>(acc[0][1], acc[1][1], a0, a1, b1, L, t + 1, l1);
     // ---- phase 2: A sub-tile 1 -> quadrant (1, 1); issues A0 of K-tile t + 2
     nt8_read(a0, aP + 64 * RB, L);
     if constexpr (NI == 4) nt8_read(a1, aP + 96 * RB, L);
     nt8_sync_in();
-    if constexpr (NI == 4) nt8_mma_issue<T, 0, SW>(acc[2][1], acc[3][1], a0, a1, b1, L, smem, t + 2, l2);
-    else nt8_mma_issue1<T, 0, SW>(acc[2][1], a0, b1, L, smem, t + 2, l2);
+    nt8_mma_issue<T, 0, SW, NI - 2>(acc[2][1], acc[NI - 1][1], a0, a1, b1, L, t + 2, l2);     // (NI = 3: acc[2] alone)
     // ---- phase 3: quadrant (1, 0); issues B0 of K-tile t + 2; the wait retires A0 / B0 of K-tile t + 1 for the next phase 0
     if (!TAIL) wait_dma_units<3>();
     else if (t + 1 < nk) wait_dma_units_rt(min(U, 4 * t + 9) - (4 * t + 6));
     nt8_sync_in();
-    if constexpr (NI == 4) nt8_mma_issue<T, 1, SW>(acc[2][0], acc[3][0], a0, a1, b0, L, smem, t + 2, l2);
-    else nt8_mma_issue1<T, 1, SW>(acc[2][0], a0, b0, L, smem, t + 2, l2);
+    nt8_mma_issue<T, 1, SW, NI - 2>(acc[2][0], acc[NI - 1][0], a0, a1, b0, L, t + 2, l2);
 }
 
 
@@ -787,7 +752,7 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(NTParams p) {
     const int tile = xcd_remap(blockIdx.x, nwg);
     const int bm0 = (tile / p.tiles_n) * BM, bn0 = (tile % p.tiles_n) * BN;
 
-    if (p.prof && tid == 0) p.prof[blockIdx.x * 4 + 0] = wall_clock64();
+    NT_PROF_STAMP(p.prof, tid, blockIdx.x * 4 + 0, false);
     NT8Lane L;
     {
         const int lr = lane >> 3, slot = lane & 7;
@@ -810,9 +775,8 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(NTParams p) {
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) L.roff[ks] = r * RB + (((ks * 2 + h) ^ sw) << 4);
         // whole operands as raw buffers (rows past M / N are clamped in the per-lane offsets above)
-        const uint64_t a = (uint64_t)(uintptr_t)p.A, b = (uint64_t)(uintptr_t)p.B;
-        L.rsA = i32x4{(int)(uint32_t)a, (int)(uint32_t)(a >> 32), (int)0x7FFFFFFF, 0x00020000};
-        L.rsB = i32x4{(int)(uint32_t)b, (int)(uint32_t)(b >> 32), (int)0x7FFFFFFF, 0x00020000};
+        L.rsA = raw_buffer(p.A);
+        L.rsB = raw_buffer(p.B);
     }
 
     f32x16 acc[NI][2];
@@ -833,13 +797,13 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(NTParams p) {
 
     const int nk = p.K / BK;
     // prologue: units 0..5 (K-tile 0 and A0, B0 of K-tile 1); A0 / B0 of K-tile 0 must have landed for phase 0
-    nt8_issue<0>(L, smem, 0);
-    nt8_issue<1>(L, smem, 0);
-    nt8_issue<2>(L, smem, 0);
-    nt8_issue<3>(L, smem, 0);
+    nt8_issue<0>(L, 0);
+    nt8_issue<1>(L, 0);
+    nt8_issue<2>(L, 0);
+    nt8_issue<3>(L, 0);
     if (nk > 1) {
-        nt8_issue<0>(L, smem, 1);
-        nt8_issue<1>(L, smem, 1);
+        nt8_issue<0>(L, 1);
+        nt8_issue<1>(L, 1);
     }
     bool mask_dma = false;
     if constexpr (SW) {
@@ -868,7 +832,7 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(NTParams p) {
         if (mask_dma) wait_vmcnt<4 + NI>(); else wait_dma_units<2>();
     }
     NT8_BARRIER();
-    if (p.prof && tid == 0) p.prof[blockIdx.x * 4 + 1] = p.prof_clk ? (unsigned long long)clock64() : wall_clock64();
+    NT_PROF_STAMP(p.prof, tid, blockIdx.x * 4 + 1, p.prof_clk);
     if (wr == 1) NT8_BARRIER();                  // the second wave group runs one barrier behind
 
     i32x4 a0[4], a1[4], b0[4], b1[4];
@@ -876,15 +840,15 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(NTParams p) {
     int t = 0;
     for (; t + 2 < nk; ++t) {
         const char* buf = smem + (t & 1) * kBuf;
-        nt8_ktile<T, false, SW, NI>(t, nk, L, smem, buf + aoff, buf + boff, acc, a0, a1, b0, b1);
+        nt8_ktile<T, false, SW, NI>(t, nk, L, buf + aoff, buf + boff, acc, a0, a1, b0, b1);
     }
     for (; t < nk; ++t) {
         const char* buf = smem + (t & 1) * kBuf;
-        nt8_ktile<T, true, SW, NI>(t, nk, L, smem, buf + aoff, buf + boff, acc, a0, a1, b0, b1);
+        nt8_ktile<T, true, SW, NI>(t, nk, L, buf + aoff, buf + boff, acc, a0, a1, b0, b1);
     }
     if (wr == 0) NT8_BARRIER();
     __syncthreads();                             // the ring becomes the epilogue slab
-    if (p.prof && tid == 0) p.prof[blockIdx.x * 4 + 2] = p.prof_clk ? (unsigned long long)clock64() : wall_clock64();
+    NT_PROF_STAMP(p.prof, tid, blockIdx.x * 4 + 2, p.prof_clk);
 
     float* slab = reinterpret_cast<float*>(smem) + wid * (64 * 64);
     if constexpr (SW) {
@@ -903,26 +867,13 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(NTParams p) {
         else
             nt_epilogue<T, 4, 2, 2, 2>(p, acc, slab, lane, bm0 + wr * 128, bn0 + wc * 64);
     }
-    if (p.prof) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) p.prof[blockIdx.x * 4 + 3] = wall_clock64();
-    }
+    NT_PROF_CLOSE(p.prof, tid, blockIdx.x * 4 + 3);
 }
 
 template <typename T, bool SW = false, int BM = 256> int launch_nt8(const NTParams& p0, hipStream_t stream) {
     constexpr int lds = 2 * 512 * 128 + (SW ? 8 * 1024 : 0);     // ring + (row-per-lane epilogue) 1 KiB of mask words per wave
-    static bool attr_done = false;
-    auto kern = gemm_nt8_kernel<T, SW, BM>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) {
-            ase_set_error("gemm_nt8: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return ASE_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    constexpr auto kern = gemm_nt8_kernel<T, SW, BM>;
+    if (const int rc = ase_dynamic_lds<kern>("gemm_nt8", lds)) return rc;
     NTParams p = p0;
     p.prof = g_nt_prof;
     p.prof_clk = g_nt_prof_clk;

@@ -277,9 +277,7 @@ __global__ __launch_bounds__(kThreads) void gemm_tn_kernel(TNParams p) {
 // ------------------------------------------------------------------------------------------------
 constexpr int kTnSlab = 65536 + 256;       // floats per work item in the partial-sum workspace: 256 x 256 tile + 256 bias sums
 
-// (DMA pieces as `buffer_load_dwordx4 ... lds`, round 6 - see NT8Lane in gemm_nt_kernels.h: one 32-bit offset register per piece
-//  instead of a 64-bit address, the K-tile's byte offset as the instruction's SGPR offset; the registers it frees are what the
-//  small kernels of the step's other branches co-reside in.)
+// (DMA pieces: lds_dma16 in gemm_nt.h - one 32-bit offset register per piece, the K-tile's byte offset as the SGPR offset)
 struct TN8Lane {
     uint32_t voff[4][2];       // per-lane byte offset of unit kind (B-lo, A-lo, B-hi, A-hi) x piece from its operand's base, at K-tile 0
     uint32_t dst[4][2];        // wave-uniform LDS byte ADDRESS of the piece in K-tile buffer 0 (buffer 1: + 65536)
@@ -291,15 +289,12 @@ struct TN8Lane {
 
 template <int KIND>
 __device__ __forceinline__ void tn8_piece(const TN8Lane& L, int g, int tile) {
-    const uint32_t lds_s = __builtin_amdgcn_readfirstlane(L.dst[KIND][g] + (uint32_t)(tile & 1) * 65536u);
-    asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :
-                 : "s"(lds_s), "v"(L.voff[KIND][g]), "s"(L.rs[KIND & 1]), "s"((uint32_t)tile * L.kstep[KIND & 1])
-                 : "memory");
+    lds_dma16(__builtin_amdgcn_readfirstlane(L.dst[KIND][g] + (uint32_t)(tile & 1) * 65536u), L.voff[KIND][g], L.rs[KIND & 1],
+              (uint32_t)tile * L.kstep[KIND & 1]);
 }
 
 template <int KIND>
-__device__ __forceinline__ void tn8_issue(const TN8Lane& L, char* smem, int tile) {
+__device__ __forceinline__ void tn8_issue(const TN8Lane& L, int tile) {
 #pragma unroll
     for (int g = 0; g < 2; ++g) tn8_piece<KIND>(L, g, tile);
 }
@@ -324,7 +319,7 @@ template <typename T> __device__ __forceinline__ typename V16<T>::x8 tn8_join(co
 template <typename T, bool BIAS, int KIND>
 __device__ __forceinline__ void tn8_mma(f32x16& c00, f32x16& c01, f32x16& c10, f32x16& c11, f32x16& bacc,
                                         const tr_pair (&a)[2][2], const tr_pair (&b)[2][2], int bias_sel,
-                                        typename V16<T>::x8 bvec, const TN8Lane& L, char* smem, int tile, bool live) {
+                                        typename V16<T>::x8 bvec, const TN8Lane& L, int tile, bool live) {
     typedef typename V16<T>::x8 x8;
     x8 a0[2], a1[2];
 #pragma unroll
@@ -358,7 +353,7 @@ __device__ __forceinline__ void tn8_mma(f32x16& c00, f32x16& c01, f32x16& c10, f
 
 // HALF = 0 / 1: phases 0, 1 (rows 0-31 of the K-tile) / phases 2, 3 (rows 32-63)
 template <typename T, bool TAIL, bool BIAS, int HALF>
-__device__ __forceinline__ void tn8_half(int t, int nk, const TN8Lane& L, char* smem, const uint32_t (&adA)[4],
+__device__ __forceinline__ void tn8_half(int t, int nk, const TN8Lane& L, const uint32_t (&adA)[4],
                                          const uint32_t (&adB)[2], int bias_frag, typename V16<T>::x8 bvec,
                                          f32x16 (&acc)[4][2], f32x16& bacc) {
     constexpr int RO = HALF * 2 * 8192;           // k-steps 2 HALF, 2 HALF + 1
@@ -377,7 +372,7 @@ __device__ __forceinline__ void tn8_half(int t, int nk, const TN8Lane& L, char* 
     tn8_read<RO + 8192>(a[1][1], adA[1]);
     nt8_sync_in();
     tn8_mma<T, BIAS, HALF == 0 ? 2 : 0>(acc[0][0], acc[0][1], acc[1][0], acc[1][1], bacc, a, b, bias_frag < 2 ? bias_frag : -1,
-                                     bvec, L, smem, itile, live);
+                                     bvec, L, itile, live);
     nt8_sync_out();
     // ---- odd phase: A fragments 2, 3; the wait retires what the next phase reads (the newest issued unit is the even
     // phase's: three units may stay in flight)
@@ -390,12 +385,12 @@ __device__ __forceinline__ void tn8_half(int t, int nk, const TN8Lane& L, char* 
     else if (t + 1 < nk) wait_dma_units_rt(min(U, 4 * t + 9) - (4 * t + 6));
     nt8_sync_in();
     tn8_mma<T, BIAS, HALF == 0 ? 3 : 1>(acc[2][0], acc[2][1], acc[3][0], acc[3][1], bacc, a, b, bias_frag >= 2 ? bias_frag - 2 : -1,
-                                     bvec, L, smem, itile, live);
+                                     bvec, L, itile, live);
     nt8_sync_out();
 }
 
 template <typename T, bool TAIL, bool BIAS>
-__device__ __forceinline__ void tn8_ktile(int t, int nk, const TN8Lane& L, char* smem, uint32_t lds0, int bias_frag,
+__device__ __forceinline__ void tn8_ktile(int t, int nk, const TN8Lane& L, uint32_t lds0, int bias_frag,
                                           bool bias_on, f32x16 (&acc)[4][2], f32x16& bacc) {
     const uint32_t pa = lds0 + (t & 1) * 65536 + L.rbase;
     uint32_t adA[4], adB[2];
@@ -406,8 +401,8 @@ __device__ __forceinline__ void tn8_ktile(int t, int nk, const TN8Lane& L, char*
     typename V16<T>::x8 bvec;
 #pragma unroll
     for (int q = 0; q < 8; ++q) bvec[q] = (T)(bias_on ? 1.0f : 0.0f);
-    tn8_half<T, TAIL, BIAS, 0>(t, nk, L, smem, adA, adB, bias_frag, bvec, acc, bacc);
-    tn8_half<T, TAIL, BIAS, 1>(t, nk, L, smem, adA, adB, bias_frag, bvec, acc, bacc);
+    tn8_half<T, TAIL, BIAS, 0>(t, nk, L, adA, adB, bias_frag, bvec, acc, bacc);
+    tn8_half<T, TAIL, BIAS, 1>(t, nk, L, adA, adB, bias_frag, bvec, acc, bacc);
 }
 
 // one work item: output tile (bn0, bk0) of problem p over the K-tiles [m_begin, m_begin + 64 nk)
@@ -420,7 +415,7 @@ __device__ __forceinline__ void tn8_body(const TNParams& p, char* smem, int bn0,
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wid >> 2, wc = wid & 3;
-    if (prof && tid == 0) prof[0] = wall_clock64();
+    NT_PROF_STAMP(prof, tid, 0, false);
 
     TN8Lane L;
     {
@@ -441,9 +436,8 @@ __device__ __forceinline__ void tn8_body(const TNParams& p, char* smem, int bn0,
         }
         L.kstep[0] = (uint32_t)(64 * p.ldb);
         L.kstep[1] = (uint32_t)(64 * p.lda);
-        const uint64_t pa_ = (uint64_t)(uintptr_t)p.A, pb_ = (uint64_t)(uintptr_t)p.B;
-        L.rs[0] = i32x4{(int)(uint32_t)pb_, (int)(uint32_t)(pb_ >> 32), (int)0x7FFFFFFF, 0x00020000};
-        L.rs[1] = i32x4{(int)(uint32_t)pa_, (int)(uint32_t)(pa_ >> 32), (int)0x7FFFFFFF, 0x00020000};
+        L.rs[0] = raw_buffer(p.B);
+        L.rs[1] = raw_buffer(p.A);
         const int t = lane & 15, g4 = lane >> 4, h = g4 >> 1, cg = g4 & 1, s2 = (t >> 2) & 3;
         L.rbase = (h * 8 + (t >> 2)) * 512 + (cg * 2 + ((t & 3) >> 1)) * 16 + (t & 1) * 8;
 #pragma unroll
@@ -466,36 +460,36 @@ __device__ __forceinline__ void tn8_body(const TNParams& p, char* smem, int bn0,
     // whole K-tiles below bias_rows contribute to the bias gradient (the host checks bias_rows % 64 == 0)
     const int bias_tiles = do_bias ? max(0, min(nk, (p.bias_rows - m_begin) / 64)) : 0;
 
-    tn8_issue<0>(L, smem, 0);
-    tn8_issue<1>(L, smem, 0);
-    tn8_issue<2>(L, smem, 0);
-    tn8_issue<3>(L, smem, 0);
+    tn8_issue<0>(L, 0);
+    tn8_issue<1>(L, 0);
+    tn8_issue<2>(L, 0);
+    tn8_issue<3>(L, 0);
     if (nk > 1) {
-        tn8_issue<0>(L, smem, 1);
-        tn8_issue<1>(L, smem, 1);
+        tn8_issue<0>(L, 1);
+        tn8_issue<1>(L, 1);
         wait_dma_units<4>();
     } else {
         wait_dma_units<2>();
     }
     NT8_BARRIER();
-    if (prof && tid == 0) prof[1] = wall_clock64();
+    NT_PROF_STAMP(prof, tid, 1, false);
     if (wr == 1) NT8_BARRIER();
 
     const uint32_t lds0 = (uint32_t)(uintptr_t)smem;           // LDS byte address of the ring (low half of the flat address)
     int t = 0;
     if (bias_tiles > 0) {
         for (; t + 2 < nk; ++t)
-            tn8_ktile<T, false, true>(t, nk, L, smem, lds0, wc, t < bias_tiles, acc, bacc);
+            tn8_ktile<T, false, true>(t, nk, L, lds0, wc, t < bias_tiles, acc, bacc);
         for (; t < nk; ++t)
-            tn8_ktile<T, true, true>(t, nk, L, smem, lds0, wc, t < bias_tiles, acc, bacc);
+            tn8_ktile<T, true, true>(t, nk, L, lds0, wc, t < bias_tiles, acc, bacc);
     } else {
         for (; t + 2 < nk; ++t)
-            tn8_ktile<T, false, false>(t, nk, L, smem, lds0, wc, false, acc, bacc);
+            tn8_ktile<T, false, false>(t, nk, L, lds0, wc, false, acc, bacc);
         for (; t < nk; ++t)
-            tn8_ktile<T, true, false>(t, nk, L, smem, lds0, wc, false, acc, bacc);
+            tn8_ktile<T, true, false>(t, nk, L, lds0, wc, false, acc, bacc);
     }
     if (wr == 0) NT8_BARRIER();
-    if (prof && tid == 0) prof[2] = wall_clock64();
+    NT_PROF_STAMP(prof, tid, 2, false);
 
     const int col_in = lane & 31, row_hi = (lane >> 5) * 4;
     if (ws) {
@@ -513,11 +507,7 @@ __device__ __forceinline__ void tn8_body(const TNParams& p, char* smem, int bn0,
 #pragma unroll
             for (int e = 0; e < 16; ++e) wsb[nl + (e & 3) + 8 * (e >> 2)] = bacc[e];
         }
-        if (prof) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) prof[3] = wall_clock64();
-        }
+        NT_PROF_CLOSE(prof, tid, 3);
         return;
     }
     if (bias_tiles > 0 && col_in == 0) {           // every column of bacc holds the sums: column 0 writes them
@@ -546,11 +536,7 @@ __device__ __forceinline__ void tn8_body(const TNParams& p, char* smem, int bn0,
             }
         }
     }
-    if (prof) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) prof[3] = wall_clock64();
-    }
+    NT_PROF_CLOSE(prof, tid, 3);
 }
 
 template <typename T>
@@ -677,17 +663,8 @@ __global__ __launch_bounds__(256, 8) void tn_reduce_kernel(const int64_t* __rest
 
 template <typename T> int launch_tn8(TNParams p, hipStream_t stream) {
     constexpr int lds = 2 * 65536;
-    static bool attr_done = false;
-    auto kern = gemm_tn8_kernel<T>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) {
-            ase_set_error("gemm_tn8: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return ASE_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    constexpr auto kern = gemm_tn8_kernel<T>;
+    if (const int rc = ase_dynamic_lds<kern>("gemm_tn8", lds)) return rc;
     p.tiles_n = (p.n_real + 255) / 256;
     p.tiles_k = (p.K + 255) / 256;
     const int tiles = p.tiles_n * p.tiles_k;
@@ -708,17 +685,8 @@ template <typename T> int launch_tn8(TNParams p, hipStream_t stream) {
 template <typename T> int launch_tn8g(const int64_t* problems, const int32_t* work, int n_work, const int32_t* red,
                                              int n_red, float* ws, const float* alpha_dev, hipStream_t stream) {
     constexpr int lds = 2 * 65536;
-    static bool attr_done = false;
-    auto kern = gemm_tn8g_kernel<T>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) {
-            ase_set_error("gemm_tn_grouped: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return ASE_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    constexpr auto kern = gemm_tn8g_kernel<T>;
+    if (const int rc = ase_dynamic_lds<kern>("gemm_tn_grouped", lds)) return rc;
     ASE_LAUNCH(kern, dim3(n_work), dim3(512), lds, stream, problems, work, n_work, g_nt_prof, ws, alpha_dev);
     if (ws) ASE_LAUNCH(tn_reduce_kernel, dim3(n_red, 16), dim3(256), 0, stream, problems, red, (const float*)ws, alpha_dev);
     ASE_CHECK_LAUNCH("gemm_tn_grouped");
@@ -728,17 +696,8 @@ template <typename T> int launch_tn8g(const int64_t* problems, const int32_t* wo
 template <typename T> int launch_tn(TNParams p, hipStream_t stream) {
     using Gm = TNGeom<T>;
     constexpr int lds = 4 * Gm::BKM * Gm::STRIDE;
-    static bool attr_done = false;
-    auto kern = gemm_tn_kernel<T>;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) {
-            ase_set_error("gemm_tn: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return ASE_ELAUNCH;
-        }
-        attr_done = true;
-    }
+    constexpr auto kern = gemm_tn_kernel<T>;
+    if (const int rc = ase_dynamic_lds<kern>("gemm_tn", lds)) return rc;
     p.tiles_n = (p.n_real + 127) / 128;
     p.tiles_k = (p.K + 127) / 128;
     const int tiles = p.tiles_n * p.tiles_k;
