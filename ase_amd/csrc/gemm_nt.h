@@ -90,6 +90,13 @@ __device__ __forceinline__ void lds_dma16(uint32_t lds_s, uint32_t voff, i32x4 r
     else LDS_DMA16_ASM("s_mov_b32 m0, %0");
 }
 #undef LDS_DMA16_ASM
+// the same piece from a 64-bit per-lane address (operands a 32-bit byte offset does not reach): M0 = lds_s + IMM.  As an asm statement
+// and not __builtin_amdgcn_global_load_lds, which the compiler books as a flat access of both address spaces - while one is pending by
+// its count (the kernels wait for their DMA with vmcnt of their own, which it does not see) every LDS wait it emits is lgkmcnt(0).
+template <int IMM>
+__device__ __forceinline__ void lds_dma16_global(uint32_t lds_s, const char* src) {
+    asm volatile("s_add_u32 m0, %0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" : : "s"(lds_s), "v"(src), "n"(IMM) : "memory", "m0", "scc");
+}
 #pragma clang diagnostic pop
 
 // SW: operands swapped in the MFMA (D = B-fragment x A-fragment): the accumulator then holds the TRANSPOSED 32 x 32

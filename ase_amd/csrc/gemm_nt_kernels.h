@@ -15,10 +15,18 @@
 #pragma once
 #include "gemm_nt.h"
 #include <stdlib.h>
+#include <utility>
 
 namespace {
 
 using namespace ase_nt;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index can be a template argument
+template <int N, typename F, int... I> __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) { static_for_impl<N>(f, std::make_integer_sequence<int, N>{}); }
 
 template <typename T> struct Mma;
 
@@ -129,45 +137,119 @@ template <> struct Mma<f32s_t> {
 //     element is needed by every row tile of the launch (64 of them at 4096 rows): splitting it once per optimisation step instead
 //     of once per tile removes two thirds of the kernel's VALU work, which is what bounded it (round 5: 5 VALU operations per
 //     element and fragment against 3 MFMAs of 32 cycles per fragment pair).
-__device__ __forceinline__ void split_f16(const f32x4& x0, const f32x4& x1, float scale, f16x8& hi, f16x8& lo) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float s0 = x0[q] * scale, s1 = x1[q] * scale;
-        hi[q] = (f16_t)s0;
-        hi[q + 4] = (f16_t)s1;
-        lo[q] = (f16_t)(s0 - (float)hi[q]);
-        lo[q + 4] = (f16_t)(s1 - (float)hi[q + 4]);
-    }
+//   The split of two elements is four instructions, written out because the compiler reaches this form for a quarter of the elements
+//     only (the rest it converts back to f32 and SLP-packs into v_pk_mul_f32 / v_pk_fma_f32, the costliest VALU form beside MFMAs):
+//       hi = half(sa x)       v_fma_mix{lo,hi}_f16: f32 sources, ONE rounding, into the low / high half of the packed register
+//       lo = half(sa x - hi)  the same, hi read back as a half source (op_sel / op_sel_hi of source 2)
+//     and equals half(f32(sa x)), half(f32(f32(sa x) - hi)) bit for bit: sa is a power of two, so sa x is exact in f32 (or inf in both
+//     forms), and sa x - hi is a multiple of the f32 ulp of sa x no larger than half an ulp of hi, hence exact in f32 as well
+//     (tests/test_h3_split_rounding.py).  Two differences no output can see: sa x = -0 gives hi = +0 (the fma adds +0), lo = -0; a
+//     finite x whose sa x leaves f32's range gives lo = -inf where inf - inf gave NaN - with hi = inf the products sum to NaN either way.
+__device__ __forceinline__ void split_f16_pair(float x0, float x1, float sa, uint32_t& hi, uint32_t& lo) {
+    asm("v_fma_mixlo_f16 %0, %4, %2, 0\n\t"
+        "v_fma_mixhi_f16 %0, %4, %3, 0\n\t"
+        "v_fma_mixlo_f16 %1, %4, %2, -%0 op_sel_hi:[0,0,1]\n\t"
+        "v_fma_mixhi_f16 %1, %4, %3, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+        : "=&v"(hi), "=&v"(lo)
+        : "v"(x0), "v"(x1), "s"(sa));
 }
+// the two wait states between a VALU write inside an asm statement and an MFMA that reads the register as an operand (the compiler
+// pads nothing it cannot see); naming the registers keeps every MFMA that reads them below it
+__device__ __forceinline__ void split_f16_fence(u32x4& hi, u32x4& lo) { asm("s_nop 1" : "+v"(hi), "+v"(lo)); }
 
 template <> struct Mma<f32h_t> {
     // rows of 128 / 64 bytes = 32 / 16 k-values; per k-step of 16 a lane (r, h) owns the 8 k-values of group 2 ks + h = two
-    // 16-byte chunks: A - 8 floats to split; B - its 8 hi halves and its 8 lo halves
-    template <int FM, int FN, int RB>
-    static __device__ __forceinline__ void tile(const char* sA, const char* sB, int lane, f32x16 (&acc)[FM][FN], float sa) {
+    // 16-byte chunks: A - 8 floats to split; B - its 8 hi halves and its 8 lo halves.
+    //   Schedule of one K-tile (pinned with sched_barrier: the split is asm the scheduler cannot weigh):
+    //     read A(0), B(0) | split A(0) under B(0)'s latency | read A(1), B(1) | MFMAs(0) with the split of A(1) spread between them |
+    //     MFMAs(1).   Every wait is the compiler's counted lgkmcnt of reads issued in order.  Tiles of more than four accumulators
+    //     read B(1) after MFMAs(0) instead (PF: their fragments would not fit the registers twice).
+    //   MFMA order per accumulator and k-step: al bh, ah bl, ah bh, k ascending - the order of every earlier version (bitwise results).
+    //   Addresses: fa / fb = the lane's byte offsets of its two chunks per k-step in the A / B part of ring buffer 0 (frag_offsets: loop
+    //     invariant), sbuf = the K-tile's ring buffer as a scalar byte offset: one add per chunk, the fragment index is the ds_read's
+    //     immediate offset.
+    template <int RB>
+    static __device__ __forceinline__ void frag_offsets(int lane, uint32_t a0, uint32_t b0, uint32_t (&fa)[RB / 64][2], uint32_t (&fb)[RB / 64][2]) {
         const int r = lane & 31, h = lane >> 5, sw = lds_swz<RB>(r);
 #pragma unroll
-        for (int ks = 0; ks < RB / 64; ++ks) {
-            f16x8 ah[FM], al[FM], bh[FN], bl[FN];
-            const int c0 = ks * 4 + h * 2;
-            const int o0 = r * RB + ((c0 ^ sw) << 4), o1 = r * RB + (((c0 + 1) ^ sw) << 4);
+        for (int ks = 0; ks < RB / 64; ++ks)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const uint32_t o = r * RB + (((ks * 4 + h * 2 + c) ^ sw) << 4);
+                fa[ks][c] = a0 + o;
+                fb[ks][c] = b0 + o;
+                asm volatile("" : "+v"(fa[ks][c]), "+v"(fb[ks][c]));      // kept whole: eight registers, not a sum re-formed per K-tile
+            }
+    }
+    template <int FM, int FN, int RB>
+    static __device__ __forceinline__ void tile(const char* smem, uint32_t sbuf, const uint32_t (&fa)[RB / 64][2], const uint32_t (&fb)[RB / 64][2],
+                                                f32x16 (&acc)[FM][FN], float sa) {
+        constexpr int KS = RB / 64, NM = FM * FN * 3, NP = FM * 4;
+        constexpr bool PF = FM * FN <= 4;
+        f32x4 ax[2][FM][2];
+        u32x4 ah[2][FM], al[2][FM];
+        f16x8 bh[2][FN], bl[2][FN];
+        auto read_a = [&](int ks) {
 #pragma unroll
             for (int i = 0; i < FM; ++i)
-                split_f16(*reinterpret_cast<const f32x4*>(sA + i * 32 * RB + o0),
-                          *reinterpret_cast<const f32x4*>(sA + i * 32 * RB + o1), sa, ah[i], al[i]);
+#pragma unroll
+                for (int c = 0; c < 2; ++c) ax[ks & 1][i][c] = *reinterpret_cast<const f32x4*>(smem + (fa[ks][c] + sbuf) + i * 32 * RB);
+        };
+        auto read_b = [&](int ks) {
 #pragma unroll
             for (int j = 0; j < FN; ++j) {
-                bh[j] = *reinterpret_cast<const f16x8*>(sB + j * 32 * RB + o0);
-                bl[j] = *reinterpret_cast<const f16x8*>(sB + j * 32 * RB + o1);
+                bh[PF ? ks & 1 : 0][j] = *reinterpret_cast<const f16x8*>(smem + (fb[ks][0] + sbuf) + j * 32 * RB);
+                bl[PF ? ks & 1 : 0][j] = *reinterpret_cast<const f16x8*>(smem + (fb[ks][1] + sbuf) + j * 32 * RB);
             }
+        };
+        // pair q of k-step ks = packed register q & 3 of row fragment q >> 2: elements 0, 1 or 2, 3 of chunk (q >> 1) & 1
+        auto split_pair = [&](int ks, int q) {
+            const int i = q >> 2, c = (q >> 1) & 1, e = (q & 1) * 2;
+            uint32_t hi, lo;
+            split_f16_pair(ax[ks & 1][i][c][e], ax[ks & 1][i][c][e + 1], sa, hi, lo);
+            ah[ks & 1][i][c * 2 + (q & 1)] = hi;
+            al[ks & 1][i][c * 2 + (q & 1)] = lo;
+        };
+        auto fence = [&](int ks) {
+#pragma unroll
+            for (int i = 0; i < FM; ++i) split_f16_fence(ah[ks & 1][i], al[ks & 1][i]);
+        };
+        read_a(0);
+        read_b(0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < NP; ++q) split_pair(0, q);
+        fence(0);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const bool more = ks + 1 < KS;
+            if (more) {
+                read_a(ks + 1);
+                if constexpr (PF) read_b(ks + 1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < FM; ++i)
 #pragma unroll
-                for (int j = 0; j < FN; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < FN; ++j)
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) {
+                        const f16x8 a = __builtin_bit_cast(f16x8, t == 0 ? al[ks & 1][i] : ah[ks & 1][i]);
+                        const f16x8 b = (t == 1) ? bl[PF ? ks & 1 : 0][j] : bh[PF ? ks & 1 : 0][j];
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc[i][j], 0, 0, 0);
+                        if (more) {                      // the next k-step's NP pairs, spread evenly behind this one's NM MFMAs
+                            const int m = (i * FN + j) * 3 + t;
+                            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                            for (int q = 0; q < NP; ++q)
+                                if (q * NM >= m * NP && q * NM < (m + 1) * NP) split_pair(ks + 1, q);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+            if (more) {
+                fence(ks + 1);
+                if constexpr (!PF) read_b(ks + 1);
+            }
         }
     }
 };
@@ -468,6 +550,54 @@ __device__ __forceinline__ void nt_epilogue_rows(const NTParams& p, f32x16 (&acc
     else nt_epilogue_rows_impl<T, FM, FN, AUXK, false>(p, acc, lane, mrow0, ncol0, bits);
 }
 
+// The S-stage ring of gemm_nt_kernel (see there) for f32h_t storage, with the loop's address work taken out of the vector unit: the
+// fragment reads are a per-lane register plus the ring buffer's scalar offset, and where both operands fit 32-bit byte offsets (the
+// phased kernels' launch guard) the DMA pieces go out as lds_dma16 - per-lane offsets that never change, the K-tile's byte offset and
+// the LDS destination as scalars; operands beyond that keep their 64-bit per-lane addresses (lds_dma16_global).  Neither is the
+// compiler's LDS-DMA builtin, so that the fragment reads' waits come out counted (see lds_dma16_global).
+template <int WGM, int WGN, int FM, int FN, int RB, int S, int A_PASSES, int B_PASSES>
+__device__ __forceinline__ void nt_h3_loop(const NTParams& p, char* smem, const char* const (&srcA)[A_PASSES], const char* const (&srcB)[B_PASSES],
+                                           int lane, int wid, int wm, int wn, int nk, f32x16 (&acc)[FM][FN]) {
+    constexpr int BM = WGM * FM * 32, BN = WGN * FN * 32, RPW = 64 / (RB / 16), RPP = WGM * WGN * RPW, P = A_PASSES + B_PASSES;
+    constexpr int kBuf = (BM + BN) * RB;
+    uint32_t fa[RB / 64][2], fb[RB / 64][2];
+    Mma<f32h_t>::template frag_offsets<RB>(lane, (wm * FM * 32) * RB, (BM + wn * FN * 32) * RB, fa, fb);
+    const bool fits32 = (int64_t)p.M * p.lda < (int64_t)0x7FFFFFFF && (int64_t)p.N * p.ldb < (int64_t)0x7FFFFFFF;
+    const i32x4 rsA = raw_buffer(p.A), rsB = raw_buffer(p.B);
+    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)smem + wid * RPW * RB);      // the wave's piece of pass 0
+    uint32_t voffA[A_PASSES], voffB[B_PASSES];
+#pragma unroll
+    for (int i = 0; i < A_PASSES; ++i) voffA[i] = (uint32_t)(srcA[i] - p.A);
+#pragma unroll
+    for (int i = 0; i < B_PASSES; ++i) voffB[i] = (uint32_t)(srcB[i] - p.B);
+    auto stage = [&](int t, int b) {                             // K-tile t into ring buffer b
+        const uint32_t dst = lds0 + (uint32_t)b * kBuf;
+        if (fits32) {
+            const uint32_t soff = (uint32_t)t * RB;
+            static_for<A_PASSES>([&](auto i) { lds_dma16<i.value * RPP * RB, true>(dst, voffA[i.value], rsA, soff); });
+            static_for<B_PASSES>([&](auto i) { lds_dma16<(BM + i.value * RPP) * RB, true>(dst, voffB[i.value], rsB, soff); });
+        } else {
+            const int64_t koff = (int64_t)t * RB;
+            static_for<A_PASSES>([&](auto i) { lds_dma16_global<i.value * RPP * RB>(dst, srcA[i.value] + koff); });
+            static_for<B_PASSES>([&](auto i) { lds_dma16_global<(BM + i.value * RPP) * RB>(dst, srcB[i.value] + koff); });
+        }
+    };
+#pragma unroll
+    for (int t = 0; t < S - 1; ++t)
+        if (t < nk) stage(t, t);
+    __builtin_amdgcn_s_waitcnt(0xC07F);                          // lgkmcnt(0): no scalar load is pending inside the loop either
+    int buf = 0, prev = S - 1;
+    for (int kt = 0; kt < nk; ++kt) {
+        if (kt + S - 2 < nk) wait_vmcnt<P*(S - 2)>();
+        else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        if (kt + S - 1 < nk) stage(kt + S - 1, prev);            // (kt + S - 1) % S = the buffer K-tile kt - 1 occupied
+        Mma<f32h_t>::template tile<FM, FN, RB>(smem, (uint32_t)buf * kBuf, fa, fb, acc, p.sa);
+        prev = buf;
+        buf = (buf + 1 == S) ? 0 : buf + 1;
+    }
+}
+
 // WPE = minimum waves per SIMD the register allocation must leave room for (k workgroups of T threads per CU <=> k T / 256)
 // SW (bf16): swapped MFMA operands + row-per-lane epilogue (16-byte stores from registers, no LDS slab)
 // FUSE: the epilogue's fused duties (nt_epilogue_impl), an instantiation of its own so that every other launch keeps its registers
@@ -541,29 +671,32 @@ __global__ __launch_bounds__(WGM * WGN * 64, WPE) void gemm_nt_kernel(NTParams p
     //   every wave AND every wave is done reading tile kt-1) -> issue the DMA of tile kt+S-1 into the buffer tile
     //   kt-1 occupied -> MFMAs on tile kt.
     const int nk = p.K / BK;
+    if constexpr (std::is_same<T, f32h_t>::value) {
+        nt_h3_loop<WGM, WGN, FM, FN, RB, S>(p, smem, srcA, srcB, lane, wid, wm, wn, nk, acc);
+    } else {
 #pragma unroll
-    for (int t = 0; t < S - 1; ++t) {
-        if (t < nk) {
-            nt_stage<A_PASSES, RPP, RB>(srcA, (int64_t)t * RB, ldsA + t * kBuf);
-            nt_stage<B_PASSES, RPP, RB>(srcB, (int64_t)t * RB, ldsB + t * kBuf);
+        for (int t = 0; t < S - 1; ++t) {
+            if (t < nk) {
+                nt_stage<A_PASSES, RPP, RB>(srcA, (int64_t)t * RB, ldsA + t * kBuf);
+                nt_stage<B_PASSES, RPP, RB>(srcB, (int64_t)t * RB, ldsB + t * kBuf);
+            }
         }
-    }
-    int buf = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        if (kt + S - 2 < nk) wait_vmcnt<P*(S - 2)>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        if (kt + S - 1 < nk) {
-            const int nb = (buf == 0) ? S - 1 : buf - 1;           // (kt + S - 1) % S
-            nt_stage<A_PASSES, RPP, RB>(srcA, (int64_t)(kt + S - 1) * RB, ldsA + nb * kBuf);
-            nt_stage<B_PASSES, RPP, RB>(srcB, (int64_t)(kt + S - 1) * RB, ldsB + nb * kBuf);
+        int buf = 0;
+        for (int kt = 0; kt < nk; ++kt) {
+            if (kt + S - 2 < nk) wait_vmcnt<P*(S - 2)>();
+            else wait_vmcnt<0>();
+            __builtin_amdgcn_s_barrier();
+            if (kt + S - 1 < nk) {
+                const int nb = (buf == 0) ? S - 1 : buf - 1;           // (kt + S - 1) % S
+                nt_stage<A_PASSES, RPP, RB>(srcA, (int64_t)(kt + S - 1) * RB, ldsA + nb * kBuf);
+                nt_stage<B_PASSES, RPP, RB>(srcB, (int64_t)(kt + S - 1) * RB, ldsB + nb * kBuf);
+            }
+            const char* sA = smem + buf * kBuf + (wm * FM * 32) * RB;
+            const char* sB = smem + buf * kBuf + (BM + wn * FN * 32) * RB;
+            if constexpr (SW && sizeof(T) == 2) Mma<T>::template tile<FM, FN, RB, true>(sA, sB, lane, acc);
+            else Mma<T>::template tile<FM, FN, RB>(sA, sB, lane, acc);
+            buf = (buf + 1 == S) ? 0 : buf + 1;
         }
-        const char* sA = smem + buf * kBuf + (wm * FM * 32) * RB;
-        const char* sB = smem + buf * kBuf + (BM + wn * FN * 32) * RB;
-        if constexpr (SW && sizeof(T) == 2) Mma<T>::template tile<FM, FN, RB, true>(sA, sB, lane, acc);
-        else if constexpr (std::is_same<T, f32h_t>::value) Mma<T>::template tile<FM, FN, RB>(sA, sB, lane, acc, p.sa);
-        else Mma<T>::template tile<FM, FN, RB>(sA, sB, lane, acc);
-        buf = (buf + 1 == S) ? 0 : buf + 1;
     }
     if constexpr (SW) {
         if constexpr (S != 2) load_bits();
