@@ -8,6 +8,9 @@ in ``ASEAgent.calc_gradients`` (learning/ase_agent.py:159-308 under /root/refere
 ``CommonAgent.calc_gradients`` (learning/common_agent.py:353-435), plus the rollout tail
 (rewards / GAE / advantage + value normalisation).
 
+``UpdateEngine`` derives from ``forward.ForwardEngine``, which owns the layer table, the shadow weights, the running statistics
+and the rollout / inference forward; this module adds what only a trainer needs.
+
 Data layout in HBM
   * master parameters, gradients, Adam moments: four flat f32 buffers in checkpoint layout
     (one fused optimizer launch, one RCCL all-reduce over the flat gradient buffer);
@@ -27,41 +30,7 @@ import math
 import torch
 
 from . import lib as L
-
-
-def P(x, m=64):
-    return (int(x) + m - 1) // m * m
-
-
-# rl_games activations_factory names (learning/ase_network_builder.py:162) -> epilogue codes; 'swish' is SiLU
-_ACT = {'relu': L.ACT_RELU, 'tanh': L.ACT_TANH, 'None': L.ACT_NONE, 'none': L.ACT_NONE, None: L.ACT_NONE,
-        'swish': L.ACT_SILU, 'silu': L.ACT_SILU, 'elu': L.ACT_ELU, 'gelu': L.ACT_GELU, 'sigmoid': L.ACT_SIGMOID,
-        'selu': L.ACT_SELU, 'softplus': L.ACT_SOFTPLUS}
-# what the data-gradient epilogue multiplies by: ReLU - the activation's sign (bit-mask twin), tanh - 1 - y^2 of the output
-# itself, the smooth activations - act'(z) of the pre-activation the forward launch kept in the layer's twin buffer
-_AUX = {L.ACT_RELU: L.AUX_RELU_MASK, L.ACT_TANH: L.AUX_TANH_GRAD, L.ACT_NONE: L.AUX_NONE}
-_AUX.update({a: L.AUX_PREACT | (a << 8) for a in range(L.ACT_SILU, L.ACT_SOFTPLUS + 1)})
-
-
-class Dense:
-    """One linear layer (or a group of heads sharing an input, stacked along N at 64-aligned offsets)."""
-
-    def __init__(self, parts, k_in, act, split=None):
-        # parts: list of (param prefix, n_real, row offset in the padded N dimension)
-        self.parts = parts
-        self.K = k_in
-        self.act = _ACT[act] if not isinstance(act, int) else act
-        if split is None:
-            self.split_src = self.split_dst = k_in
-            self.k_pad = P(k_in)
-        else:
-            self.split_src, self.split_dst, self.k_pad = split
-        self.n_pad = max(off + P(n) for _, n, off in parts)
-        self.N = parts[0][1]
-
-    @property
-    def name(self):
-        return self.parts[0][0]
+from .forward import _ACT, _AUX, Dense, ForwardEngine, P      # noqa: F401  (_ACT, Dense: importable from here as before)
 
 
 class _StepState:
@@ -95,20 +64,21 @@ class _StepState:
         self.merged_stats = self.stats_exchanged = self.enc_z_ready = self.gp_x_done = self.acc_in_bucket = self.lr_live = False
 
 
-class UpdateEngine:
-    """kind: 'ase' | 'amp' | 'ppo'.  sizes: rows handled by THIS rank (M, AMB) and global counts."""
+class UpdateEngine(ForwardEngine):
+    """The trainer on top of the forward engine: gradients, Adam state, the step and its schedule, the gradient penalty, the loss
+    scaler, the collectives and the epoch tail.  kind: 'ase' | 'amp' | 'ppo'.  sizes: rows handled by THIS rank (M, AMB) and
+    global counts."""
 
     def __init__(self, kind, net, cfg, backend, *, minibatch, amp_minibatch=0, dtype=torch.bfloat16,
-                 world_size=1, rank=0, infer_rows=0, dp_mode='shard', grad_scale=None):
+                 world_size=1, rank=0, dp_mode='shard', grad_scale=None):
         """dp_mode (world_size > 1):
           'shard'    every minibatch is row-sharded over the ranks; global denominators, normaliser moments summed over
                      the ranks, gradients SUM-reduced: the R-rank update equals the 1-rank update (BASELINE config 3);
           'horovod'  the reference's multi-GPU semantics (rl_games HorovodWrapper, learning/common_agent.py:94-107): every
                      rank owns its environments and minibatches, local statistics, gradients AVERAGED over the ranks,
-                     running statistics averaged once per epoch (CommonAgent.sync_stats)."""
-        self.kind, self.net, self.cfg, self.be = kind, net, cfg, backend
-        self.dtype = dtype
-        self.dev = net.flat_params.device
+                     running statistics averaged once per epoch (CommonAgent.sync_stats).
+        The training options are resolved first: the base constructor, called at the end, runs _bind_params / _alloc /
+        refresh_shadows, whose overrides here read them."""
         self.R, self.rank = world_size, rank
         assert dp_mode in ('shard', 'horovod')
         self.shard = dp_mode == 'shard'
@@ -156,36 +126,23 @@ class UpdateEngine:
         # device factor the same launches multiply in (self.scale_tab, written by _bind_params / set_grad_scale / every scaler_step)
         self._gs_init = float(grad_scale)
         self.gs = 1.0 if self.dyn_scale else float(grad_scale)
-        # flags resolved once (rl_games defaults: normalize_value False, bounds_loss_coef None = no bound loss)
+        # flags resolved once (rl_games default: bounds_loss_coef None = no bound loss)
         # truncate_grads: global-norm clip of the whole gradient before Adam (learning/ase_agent.py:273-288): the norm needs every
         # gradient (weight-only loss terms included), so the per-branch optimizer steps give way to the end-of-step form
         self.truncate = bool(cfg.get('truncate_grads', False))
         self.grad_norm = float(cfg.get('grad_norm', 1.0))
-        self.norm_value = bool(cfg.get('normalize_value', False))
         self.bounds_coef = float(cfg.get('bounds_loss_coef') or 0.0)
         # lr_schedule: adaptive (rl_games AdaptiveScheduler under the default 'legacy' schedule_type): the learning rate follows
         # every step's kl - on the device, inside the launch that forms the reported scalars
         self.adaptive_lr = cfg.get('lr_schedule', 'constant') == 'adaptive'
         self.kl_threshold = float(cfg.get('kl_threshold', 0.008))
-        self.obs, self.act = net.obs_size, net.actions_num
-        self.z = net.latent_dim if kind == 'ase' else 0
-        self.amp = net.amp_obs_size if kind in ('amp', 'ase') else 0
         self.masked = kind in ('amp', 'ase')
-        self.has_disc = kind in ('amp', 'ase')
-        self.has_enc = kind == 'ase'
         self.div_on = kind == 'ase' and cfg.get('amp_diversity_bonus', 0) != 0
-        self.enc_sep = bool(getattr(net, 'enc_separate', False))
         self.enc_gp = kind == 'ase' and cfg.get('enc_grad_penalty', 0) != 0 and cfg.get('enc_coef', 0) != 0
-        self.mu_tanh = kind == 'ppo' and getattr(net, 'mu_tanh', False)
-        # the policy's log-std (network space.continuous): 'frozen' (learn_sigma False: the reference's configurations),
-        # 'vector' (a learned state-independent vector, one bias-only row of the Adam table) or 'head' (the sigma head, stacked
-        # beside mu in one head group: mu columns [0, act), log-std columns [64, 64 + act))
-        self.sigma_mode = getattr(net, 'sigma_mode', 'frozen')
-        self.ls_mode = {'frozen': L.LS_FROZEN, 'vector': L.LS_VECTOR, 'head': L.LS_ROWS}[self.sigma_mode]
+        self.ls_mode = {'frozen': L.LS_FROZEN, 'vector': L.LS_VECTOR, 'head': L.LS_ROWS}[getattr(net, 'sigma_mode', 'frozen')]
         # gp_f32: the gradient penalty's value path (demo-row forward, chain) in exact f32 inside a 16-bit engine (_gp_f32)
-        self.gp32 = bool(cfg.get('gp_f32', False)) and self.has_disc and dtype in (torch.float16, torch.bfloat16) and \
+        self.gp32 = bool(cfg.get('gp_f32', False)) and kind in ('amp', 'ase') and dtype in (torch.float16, torch.bfloat16) and \
             cfg.get('disc_coef', 0) * cfg.get('disc_grad_penalty', 0) != 0
-        self._scratch = {}
         self.multi_stream = bool(cfg.get('multi_stream', True)) and getattr(backend, 'name', '') == 'hip'
         self._side_streams = None
         # Scheduling options (cfg['engine_opts'], a dict; every default is the measured best of its A/B on MI355X):
@@ -278,68 +235,15 @@ class UpdateEngine:
         self.dp_grad_dtype = cfg.get('dp_grad_dtype', 'f32')
         assert self.dp_grad_dtype in ('f32', 'bf16'), self.dp_grad_dtype
         self._xbuf = {}
-        self._refresh_desc = None
         self._mb_desc = None
         self._mb_desc_key = None
-        self._build_layers()
-        self._bind_params()
-        self._alloc(infer_rows)
-        self.refresh_shadows()
-
-    # ------------------------------------------------------------------ structure
-    def _build_layers(self):
-        net, z = self.net, self.z
-        act = net.activation
-        split = (self.obs, P(self.obs), P(self.obs) + P(z)) if z else None
-        self.style = []
-        if self.kind == 'ase':
-            k = z
-            for i, u in enumerate(net.style_units):
-                self.style.append(Dense([(f'actor_mlp._style_mlp.{2 * i}', u, 0)], k, act))
-                k = u
-            self.style.append(Dense([('actor_mlp._style_dense', z, 0)], k, 'tanh'))
-            names_a = [f'actor_mlp._dense_layers.{i}' for i in range(len(net.units))]
-            names_c = [f'critic_mlp._mlp.{2 * i}' for i in range(len(net.units))]
-        else:
-            names_a = [f'actor_mlp.{2 * i}' for i in range(len(net.units))]
-            names_c = [f'critic_mlp.{2 * i}' for i in range(len(net.units))]
-        self.actor, self.critic = [], []
-        k = self.obs + z
-        for i, u in enumerate(net.units):
-            sp = split if (i == 0 and z) else None
-            self.actor.append(Dense([(names_a[i], u, 0)], k, act, sp))
-            self.critic.append(Dense([(names_c[i], u, 0)], k, act, sp))
-            k = u
-        if self.sigma_mode == 'head':
-            self.mu_head = Dense([('mu', self.act, 0), ('sigma', self.act, P(self.act))], k, 'None')
-        else:
-            self.mu_head = Dense([('mu', self.act, 0)], k, 'None')
-        self.value_head = Dense([('value', 1, 0)], k, 'None')
-        self.disc, self.enc_chain = [], []
-        self.disc_head = self.enc_head = None
-        if self.has_disc:
-            k = self.amp
-            for i, u in enumerate(net.disc_units):
-                self.disc.append(Dense([(f'_disc_mlp.{2 * i}', u, 0)], k, net.disc_activation))
-                k = u
-            parts = [('_disc_logits', 1, 0)]
-            if self.has_enc and not self.enc_sep:
-                parts.append(('_enc', z, P(1)))
-            self.disc_head = Dense(parts, k, 'None')
-            if self.has_enc and self.enc_sep:
-                k = self.amp
-                for i, u in enumerate(net.enc_units):
-                    self.enc_chain.append(Dense([(f'_enc_mlp.{2 * i}', u, 0)], k, net.enc_activation))
-                    k = u
-                self.enc_head = Dense([('_enc', z, 0)], k, 'None')
-        self.layers = (self.style + self.actor + [self.mu_head] + self.critic + [self.value_head] + self.disc +
-                       ([self.disc_head] if self.disc_head else []) + self.enc_chain +
-                       ([self.enc_head] if self.enc_head else []))
+        super().__init__(kind, net, cfg, backend, dtype=dtype)
 
     def _bind_params(self):
-        net, dev, T = self.net, self.dev, self.dtype
-        self.params = net.flat_params
-        net._engine_bound = True          # A2CNetwork._apply refuses to re-allocate the flat buffer from now on
+        """The training half of the binding: gradients, Adam moments and their per-layer views, optimizer and loss-scaler
+        state, the weight-only loss terms."""
+        super()._bind_params()
+        net, dev = self.net, self.dev
         n = self.params.numel()
         self.grads = torch.zeros(n, dtype=torch.float32, device=dev)
         self.adam_m = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -361,27 +265,19 @@ class UpdateEngine:
         self._scaler_list = None
         self._check_tabs = {}
         for d in self.layers:
-            d.Ws = torch.zeros(d.n_pad, d.k_pad, dtype=T, device=dev)
-            d.Wts = torch.zeros(d.k_pad, d.n_pad, dtype=T, device=dev)
-            d.bs = torch.zeros(d.n_pad, dtype=torch.float32, device=dev)
-            d.W, d.b, d.gW, d.gb = [], [], [], []
+            d.gW, d.gb = [], []
             for name, nr, off in d.parts:
-                o, shp = net.param_slices[name + '.weight']
-                assert tuple(shp) == (nr, d.K), (name, shp, nr, d.K)
-                d.W.append(self.params[o:o + nr * d.K].view(nr, d.K))
+                o, _ = net.param_slices[name + '.weight']
                 d.gW.append(self.grads[o:o + nr * d.K].view(nr, d.K))
                 ob, _ = net.param_slices[name + '.bias']
-                d.b.append(self.params[ob:ob + nr])
                 d.gb.append(self.grads[ob:ob + nr])
-        self.logstd = self.glogstd = None           # 'head': the log-std is the sigma columns of the head output
+        self.glogstd = None
         if self.ls_mode != L.LS_FROZEN and hasattr(self.be, 'reserve_learned_logstd'):
             self.be.reserve_learned_logstd()
-        if self.sigma_mode != 'head':
+        if self.sigma_mode == 'vector':
             o, shp = net.param_slices['sigma']
-            self.logstd = self.params[o:o + shp[0]]
-            if self.sigma_mode == 'vector':
-                assert o + shp[0] <= self.n_train, "the learned log-std vector must be trainable"
-                self.glogstd = self.grads[o:o + shp[0]]
+            assert o + shp[0] <= self.n_train, "the learned log-std vector must be trainable"
+            self.glogstd = self.grads[o:o + shp[0]]
         # weight-only loss terms (learning/amp_agent.py:449-466, learning/ase_agent.py:420-425): ranges of the flat buffer
         self.l2_terms = []
         c = self.cfg
@@ -399,7 +295,13 @@ class UpdateEngine:
             ei = 0 if self.enc_sep else 1
             self.l2_terms.append((eh.W[ei], eh.gW[ei], ew, L.ACC_ENC_W2))
 
-    def _alloc(self, infer_rows):
+    def _latent_seed(self):
+        """Horovod mode: rank-distinct seeds (independent streams per rank, like the reference's ranks); sharded mode: one
+        stream indexed by the global row, identical on every rank."""
+        return super()._latent_seed() + (0 if self.shard else 7919 * self.rank)
+
+    def _alloc(self):
+        super()._alloc()     # (running statistics, the rollout's latent stream, the empty twin map _bits that with_bits fills)
         dev, T = self.dev, self.dtype
         M, AMB = self.M, self.AMB
         Ra = 2 * M if self.div_on else M
@@ -407,8 +309,6 @@ class UpdateEngine:
 
         def zt(r, c, dt=T):
             return torch.zeros(r, c, dtype=dt, device=dev)
-
-        self._bits = {}      # activation buffer (storage pointer) -> (buffer, bit-mask twin [rows, n_pad / 32] int32)
 
         def with_bits(h, d):
             """Twin of an activation buffer, written by the forward epilogue (mask_out) and read by the data-gradient
@@ -445,16 +345,10 @@ class UpdateEngine:
             self.Hs, self.dZs = chain_bufs(self.style[:-1], Ra)
             self.dStyle = zt(Ra, P(self.z))
             self.new_z = zt(M, self.z, f32)
-            # Philox stream of the latent draws {seed, offset}: seeded by the run, advanced on device, part of the
-            # checkpoint (CommonAgent.get_full_state_weights)
-            # Two streams: the ROLLOUT's latents (sample_latents(n) of the network, read-then-advance) and the in-step
-            # DIVERSITY draw (advanced by begin_step, read without advancing) never share a (seed, offset) pair - with one
-            # stream the first rollout draw after an update repeated the last diversity draw.  Horovod mode: rank-distinct
-            # seeds (independent streams per rank, like the reference's ranks); sharded mode: one stream indexed by the
-            # global row, identical on every rank.
-            seed = int(self.cfg.get('seed', 0)) + (0 if self.shard else 7919 * self.rank)
-            self.rng_state = torch.tensor([seed ^ 0x5EED, 0], dtype=torch.int64, device=dev)
-            self.div_rng = torch.tensor([seed ^ 0xD1755EED, 0], dtype=torch.int64, device=dev)
+            # Philox stream of the in-step DIVERSITY draw {seed, offset} (advanced by begin_step, read without advancing), part of
+            # the checkpoint like the rollout's stream rng_state: the two never share a (seed, offset) pair - with one stream
+            # the first rollout draw after an update repeated the last diversity draw
+            self.div_rng = torch.tensor([self._latent_seed() ^ 0xD1755EED, 0], dtype=torch.int64, device=dev)
         if self.has_disc:
             Rd = 3 * AMB
             # Rows [0, 3 AMB) = agent | replay | demo.  A 4th block of AMB rows carries the gradient-penalty chain of
@@ -506,8 +400,6 @@ class UpdateEngine:
                 self.DUe = zt(AMB, ehead.n_pad, f32)                     # what the backward returns at u
             self.amp_mean = zt(3, self.amp, f32)
             self.amp_std = zt(3, self.amp, f32)
-            self.amp_state = torch.zeros(2 * self.amp + 1, dtype=torch.float64, device=dev)
-            self.amp_state[self.amp:] = 1.0
         # every per-step partial statistic that the data-parallel ranks exchange lives in ONE f64 buffer
         # [amp sums x3 | obs sums | mask sum]: one small all-reduce per step when the step runs its statistics in a
         # serial prologue; with the branch heads un-chained (cross-step schedule) each head exchanges ITS slice on its own stream -
@@ -520,9 +412,6 @@ class UpdateEngine:
             self.amp_sums = self.amp_sums_flat.view(3, 2 * self.amp)
         self.obs_mean = zt(1, self.obs, f32)
         self.obs_std = zt(1, self.obs, f32)
-        self.obs_state = torch.zeros(2 * self.obs + 1, dtype=torch.float64, device=dev)
-        self.obs_state[self.obs:] = 1.0
-        self.val_state = torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=dev)
         self.acc = torch.zeros(L.ACC_COUNT, dtype=torch.float64, device=dev)
         self.set_result_slots(1)
         # packed f32 minibatch fields
@@ -565,18 +454,8 @@ class UpdateEngine:
 
     # ------------------------------------------------------------------ shadows
     def refresh_shadows(self):
-        """Master f32 weights -> compute-dtype shadows (W, W^T, padded bias) for every layer: one launch."""
-        if self._refresh_desc is None:
-            rows, items = [], []
-            for d in self.layers:
-                for (name, nr, off), W, b in zip(d.parts, d.W, d.b):
-                    ws, wts, bs = d.Ws[off:], d.Wts[:, off:], d.bs[off:off + nr]
-                    rows.append([W.data_ptr(), nr, d.K, ws.data_ptr(), ws.stride(0), wts.data_ptr(), wts.stride(0),
-                                 d.split_src, d.split_dst - d.split_src, b.data_ptr(), bs.data_ptr(), (d.K + 31) // 32])
-                    items.append((W, ws, wts, d.split_src, d.split_dst, b, bs))
-            self._refresh_desc = torch.tensor(rows, dtype=torch.int64, device=self.dev)
-            self._refresh_items = items
-        self.be.refresh_shadow_multi(self._refresh_desc, self._refresh_items, self.dtype)
+        """The base's one launch, then (gp_fuse) the value path's half-split shadows of the discriminator trunk."""
+        super().refresh_shadows()
         if self._gp_split:
             self._gp_refresh()
 
@@ -682,11 +561,6 @@ class UpdateEngine:
             self._apply_groups['disc'] = (n_pol, len(items)) + span(items[n_pol:])
 
     # ------------------------------------------------------------------ primitive layer ops
-    def _fwd(self, d, X, Y, rows, act=None):
-        act = d.act if act is None else act
-        self._nt(X, d.Ws, Y, rows, d.n_pad, d.k_pad, bias=d.bs, act=act,
-                        mask_out=self._mask_of(Y) if (act == L.ACT_RELU or act >= L.ACT_SILU) else None)
-
     def _aux(self, aux, mode):
         """(aux tensor, aux mode) of a data-gradient launch: the bit-mask twin replaces a ReLU activation."""
         if mode == L.AUX_RELU_MASK:
@@ -699,18 +573,6 @@ class UpdateEngine:
             return pre, mode
         return (aux if mode else None), mode
 
-    def _mask_of(self, h):
-        """Bit-mask twin of (a row range of) an activation buffer, or None."""
-        e = self._bits.get(h.untyped_storage().data_ptr()) if h is not None else None
-        if e is None:
-            return None
-        base, bits = e
-        off = (h.data_ptr() - base.data_ptr()) // base.element_size()
-        r0, c0 = divmod(off, base.stride(0))
-        if c0 != 0 or h.shape[1] != base.shape[1]:
-            return None
-        return bits[r0:r0 + h.shape[0]]
-
     def _twin(self, h, d):
         """Twin of activation buffer h of layer d as the gradient-penalty kernels read it (ase_hip_gp_seed / gp_second): the
         output itself for ReLU / tanh, the stored pre-activation for the smooth activations."""
@@ -719,12 +581,6 @@ class UpdateEngine:
             assert t is not None
             return t
         return h
-
-    def _fwd_chain(self, chain, X, H, rows):
-        for d, h in zip(chain, H):
-            self._fwd(d, X, h, rows)
-            X = h
-        return X
 
     def _dgrad(self, d, dY, dX, rows, aux, aux_act, wts=None, n_out=None, alpha=1.0):
         """dX = (dY @ W) * act'(aux): gradient w.r.t. the pre-activation of the layer that produced aux."""
@@ -821,12 +677,7 @@ class UpdateEngine:
         if self.style and self.shard:        # (Horovod mode: every rank keeps its own latent streams)
             bufs += [self.rng_state, self.div_rng]
         for t in bufs:
-            if t.is_cuda and dist.get_backend() == 'gloo':
-                h = t.cpu()
-                dist.broadcast(h, 0)
-                t.copy_(h)
-            else:
-                dist.broadcast(t, 0)
+            self._staged(lambda x: dist.broadcast(x, 0), t)
         self.refresh_shadows()
 
     def step(self, ds, idx, remap, amp_streams=None, new_z=None, apply=True, fence=True):
@@ -1819,20 +1670,22 @@ class UpdateEngine:
                 fn()
         self.be.host_call(run)
 
-    def _ar(self, t):
-        """SUM all-reduce of a device tensor over the data-parallel group: RCCL over xGMI in production (backend
-        'nccl').  With the 'gloo' backend (CPU test rigs, or several ranks sharing one GPU) device tensors are staged
-        through the host."""
+    @staticmethod
+    def _staged(op, t):
+        """Collective `op` on tensor t: RCCL over xGMI in production (backend 'nccl').  With the 'gloo' backend (CPU test
+        rigs, or several ranks sharing one GPU) device tensors are staged through the host."""
         import torch.distributed as dist
+        if t.is_cuda and dist.get_backend() == 'gloo':
+            h = t.cpu()
+            op(h)
+            t.copy_(h)
+        else:
+            op(t)
 
-        def run():
-            if t.is_cuda and dist.get_backend() == 'gloo':
-                h = t.cpu()
-                dist.all_reduce(h)
-                t.copy_(h)
-            else:
-                dist.all_reduce(t)
-        self._host(run)
+    def _ar(self, t):
+        """SUM all-reduce of a device tensor over the data-parallel group."""
+        import torch.distributed as dist
+        self._host(lambda: self._staged(dist.all_reduce, t))
 
     def _exchange_bucket(self, group, lo, hi, with_acc=False):
         """SUM exchange of one gradient bucket (+ with_acc: the step's loss partial sums acc[1 : ACC_LOGIT_W2], f64, travelling as
@@ -1859,12 +1712,7 @@ class UpdateEngine:
                 hi_ = a.float()
                 xb[n:n + k].copy_(hi_)
                 xb[n + k:].copy_((a - hi_.double()).float())
-            if xb.is_cuda and dist.get_backend() == 'gloo':
-                h = xb.cpu()
-                dist.all_reduce(h)
-                xb.copy_(h)
-            else:
-                dist.all_reduce(xb)
+            self._staged(dist.all_reduce, xb)
             g.copy_(xb[:n])
             if k:
                 acc[1:1 + k] = xb[n:n + k].double() + xb[n + k:].double()
@@ -1933,153 +1781,6 @@ class UpdateEngine:
         if self.div_on:
             out['amp_diversity_loss'] = r[L.RES_DIV_LOSS]
         return out
-
-    # ------------------------------------------------------------------ inference (rollout side, epoch tail)
-    def _scr(self, key, rows, cols, dt=None):
-        dt = self.dtype if dt is None else dt
-        k = (key, cols, dt)
-        t = self._scratch.get(k)
-        if t is None or t.shape[0] < rows:
-            t = torch.zeros(rows, cols, dtype=dt, device=self.dev)
-            self._scratch[k] = t
-        return t[:rows]
-
-    def _eval_stats(self, state, D, key):
-        mean, std = self._scr(key + '_m', 1, D, torch.float32), self._scr(key + '_s', 1, D, torch.float32)
-        self.be.rms_finalize(state, D, None, 0, 0, mean, std)
-        return mean[0], std[0]
-
-    def _policy_nets(self, obs, z, normalize, want_mu, want_value):
-        """Eval-mode observation normalisation + actor / critic forward on raw observations [n, obs].  Returns the padded
-        head outputs (MU f32 [n, P(act)] before any tanh, V f32 [n, 64]); every buffer is persistent scratch."""
-        be, n = self.be, obs.shape[0]
-        f32 = torch.float32
-        a0 = self.actor[0]
-        Xa, Xc = self._scr('Xa', n, a0.k_pad), self._scr('Xc', n, a0.k_pad)
-        if normalize and self.cfg.get('normalize_input', True):
-            mean, std = self._eval_stats(self.obs_state, self.obs, 'obs')
-        else:
-            mean, std = self._scr('one_m', 1, self.obs, f32)[0].zero_(), self._scr('one_s', 1, self.obs, f32)[0].fill_(1.0)
-        be.rms_normalize(obs, self.obs, None, (0, 0), n, mean, std, [Xa, Xc])
-        MU = V = None
-        if self.z:
-            sd = a0.split_dst
-            be.gather_rows(z, self.z, None, (0, 0), n, Xc[:, sd:])
-        if want_mu:
-            if self.style:
-                Zs = self._scr('Zs', n, P(self.z))
-                be.gather_rows(z, self.z, None, (0, 0), n, Zs)
-                h = Zs
-                for i, d in enumerate(self.style[:-1]):
-                    y = self._scr(f'Hs{i}', n, d.n_pad)
-                    self._fwd(d, h, y, n)
-                    h = y
-                self._fwd(self.style[-1], h, Xa[:, a0.split_dst:], n)
-            h = Xa
-            for i, d in enumerate(self.actor):
-                y = self._scr(f'Ha{i}', n, d.n_pad)
-                self._fwd(d, h, y, n)
-                h = y
-            MU = self._scr('MU', n, self.mu_head.n_pad, f32)
-            self._fwd(self.mu_head, h, MU, n)
-        if want_value:
-            h = Xc
-            for i, d in enumerate(self.critic):
-                y = self._scr(f'Hc{i}', n, d.n_pad)
-                self._fwd(d, h, y, n)
-                h = y
-            V = self._scr('V', n, self.value_head.n_pad, f32)
-            self._fwd(self.value_head, h, V, n)
-        return MU, V
-
-    def _value_out(self, V, n, unnorm_value, key='value_out'):
-        """Column 0 of the padded value head -> dense [n, 1] (un-normalised like RunningMeanStd(unnorm=True))."""
-        v = self._scr(key, n, 1, torch.float32)
-        self.be.gather_rows(V, 1, None, (0, 0), n, v)
-        if unnorm_value and self.norm_value:
-            self.be.rms_unnormalize(self.val_state, v, v)
-        return v
-
-    def _logstd_of(self, MU):
-        """The log-std operand of the loss / sampling heads: the vector, or (sigma head) the log-std columns of the head output."""
-        if self.sigma_mode == 'head':
-            off = self.mu_head.parts[1][2]
-            return MU[:, off:off + self.act]
-        return self.logstd
-
-    def policy_forward(self, obs, z=None, normalize=True, unnorm_value=True, want=('mu', 'value')):
-        """Eval-mode actor / critic on raw observations [n, obs] (learning/ase_agent.py:117-148,385-393):
-        eval-mode obs normalisation -> nets -> (mu [n, act], value [n, 1] un-normalised).  The returned tensors are
-        persistent scratch, overwritten by the next call with the same n."""
-        n = obs.shape[0]
-        MU, V = self._policy_nets(obs, z, normalize, 'mu' in want or 'logstd' in want, 'value' in want)
-        out = {}
-        if 'mu' in want:
-            mu = self._scr('mu_out', n, self.act, torch.float32)
-            self.be.gather_rows(MU, self.act, None, (0, 0), n, mu)
-            out['mu'] = torch.tanh_(mu) if self.mu_tanh else mu
-        if 'logstd' in want:          # per row [n, act] (the sigma head's output, no activation), or the vector [act]
-            if self.sigma_mode == 'head':
-                ls = self._scr('logstd_out', n, self.act, torch.float32)
-                self.be.gather_rows(self._logstd_of(MU), self.act, None, (0, 0), n, ls)
-                out['logstd'] = ls
-            else:
-                out['logstd'] = self.logstd
-        if 'value' in want:
-            out['value'] = self._value_out(V, n, unnorm_value)
-        return out
-
-    def policy_act(self, obs, z, rand_probs, rng_state):
-        """One rollout step of get_action_values (learning/amp_agent.py:139-169, learning/ase_agent.py:117-148) as an
-        explicit launch sequence: normalise -> actor + critic -> ase_hip_sample_actions (tanh / Normal sample / neglogp /
-        eps-greedy on device) -> value un-normalisation.  rand_probs None: every row stochastic (plain PPO)."""
-        n, f32 = obs.shape[0], torch.float32
-        MU, V = self._policy_nets(obs, z, True, True, True)
-        o = {k: self._scr('act_' + k, n, c, f32) for k, c in (('mus', self.act), ('sigmas', self.act), ('actions', self.act),
-                                                             ('neglogpacs', 1), ('rand_action_mask', 1))}
-        kw = dict(logstd_rows=True) if self.sigma_mode == 'head' else {}
-        self.be.sample_actions(MU, self._logstd_of(MU), rand_probs, rng_state, o['mus'], o['sigmas'], o['actions'],
-                               o['neglogpacs'], o['rand_action_mask'] if rand_probs is not None else None, n, self.act,
-                               self.mu_tanh, **kw)
-        res = {'neglogpacs': o['neglogpacs'].view(-1), 'values': self._value_out(V, n, True, 'act_values'),
-               'actions': o['actions'], 'mus': o['mus'], 'sigmas': o['sigmas'], 'rnn_states': None}
-        if rand_probs is not None:
-            res['rand_action_mask'] = o['rand_action_mask'].view(-1)
-        return res
-
-    def amp_heads(self, amp_obs, normalize=True):
-        """Eval-mode discriminator logits [n,1] (+ un-normalised encoder output [n,z]) on raw amp obs
-        (learning/amp_agent.py:547-549, learning/ase_agent.py:480-482)."""
-        be, n = self.be, amp_obs.shape[0]
-        f32 = torch.float32
-        d0 = self.disc[0]
-        X = self._scr('Xd', n, d0.k_pad)
-        if normalize and self.cfg.get('normalize_amp_input', True):
-            mean, std = self._eval_stats(self.amp_state, self.amp, 'amp')
-        else:
-            mean, std = self._scr('one_am', 1, self.amp, f32)[0].zero_(), self._scr('one_as', 1, self.amp, f32)[0].fill_(1.0)
-        be.rms_normalize(amp_obs, self.amp, None, (0, 0), n, mean, std, [X])
-        h = X
-        for i, d in enumerate(self.disc):
-            y = self._scr(f'Hd{i}', n, d.n_pad)
-            self._fwd(d, h, y, n)
-            h = y
-        HD = self._scr('HD', n, self.disc_head.n_pad, f32)
-        self._fwd(self.disc_head, h, HD, n)
-        enc = None
-        if self.has_enc:
-            if self.enc_sep:
-                h = X
-                for i, d in enumerate(self.enc_chain):
-                    y = self._scr(f'He{i}', n, d.n_pad)
-                    self._fwd(d, h, y, n)
-                    h = y
-                E = self._scr('E', n, self.enc_head.n_pad, f32)
-                self._fwd(self.enc_head, h, E, n)
-                enc = E
-            else:
-                enc = HD[:, self.disc_head.parts[1][2]:]
-        return HD, enc
 
     # ------------------------------------------------------------------ once-per-epoch rollout tail
     def prepare_epoch(self, exp):

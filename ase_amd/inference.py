@@ -4,19 +4,15 @@ learning/amp_network_builder.py:51-84 under /root/reference/ase).  Inputs are al
 observations, as in the reference."""
 import torch
 
-from .engine import UpdateEngine
-
-_INFER_CFG = {'learning_rate': 0.0, 'normalize_input': True, 'normalize_value': True, 'normalize_amp_input': True,
-              'amp_diversity_bonus': 0.0, 'disc_coef': 0.0, 'disc_weight_decay': 0.0, 'disc_logit_reg': 0.0,
-              'enc_weight_decay': 0.0, 'enc_coef': 0.0}
+from .forward import ForwardEngine
 
 
 class InferenceEngine:
     def __init__(self, net, engine=None, dtype=torch.bfloat16):
         if engine is None:
             from .backend import HipBackend
-            engine = UpdateEngine(net.kind, net, dict(_INFER_CFG), HipBackend(net.flat_params.device), minibatch=0,
-                                  amp_minibatch=0, dtype=dtype)
+            cfg = {'normalize_input': True, 'normalize_value': True, 'normalize_amp_input': True}
+            engine = ForwardEngine(net.kind, net, cfg, HipBackend(net.flat_params.device), dtype=dtype)
         self.eng = engine
 
     def refresh(self):

@@ -439,7 +439,7 @@ class CommonAgent:
 
     def _preproc_obs(self, obs_batch):
         """rl_games A2CBase._preproc_obs: uint8 -> /255, then the eval-mode observation normaliser.  The agents' own
-        rollout path fuses this into the first layer's input buffers (UpdateEngine._policy_nets); this stand-alone form
+        rollout path fuses this into the first layer's input buffers (ForwardEngine._policy_nets); this stand-alone form
         serves callers that feed the network-level API (model.a2c_network.eval_actor, learning/hrl_agent.py:231-236)."""
         if obs_batch.dtype == torch.uint8:
             obs_batch = obs_batch.float() / 255.0
@@ -456,7 +456,7 @@ class CommonAgent:
         """rl_games A2CBase.get_action_values(obs) / AMPAgent(obs, rand_action_probs) / ASEAgent(obs, ase_latents,
         rand_action_probs) (learning/amp_agent.py:139-169, learning/ase_agent.py:117-148): eval-mode model forward, sampled
         action, its neglogp, un-normalised value and - AMP / ASE - the eps-greedy substitution of mu for the rows whose
-        Bernoulli(rand_action_probs) draw is 0.  All of it on the device (UpdateEngine.policy_act)."""
+        Bernoulli(rand_action_probs) draw is 0.  All of it on the device (ForwardEngine.policy_act)."""
         z = probs = None
         if self.kind == 'ase':
             z = extra[0] if len(extra) > 0 else None

@@ -10,7 +10,7 @@ Same constructor ``Player(config)`` (the yaml ``params.config`` block + ``networ
 sub-block holds ``games_num / deterministic / print_stats``), same public methods (``restore``, ``run``, ``get_action``,
 ``env_reset``, ``env_step``, ``_preproc_obs``, ``_eval_disc``, ``_calc_amp_rewards`` ...).  What differs: the network is
 never called through autograd modules - observation normalisation, the MLPs, the Normal sample and (ASE) the latent draw
-are launches of libase_hip.so (``UpdateEngine.policy_act`` / ``amp_heads``).  Viewer / rendering hooks are out of scope
+are launches of libase_hip.so (``ForwardEngine.policy_act`` / ``amp_heads``).  Viewer / rendering hooks are out of scope
 (Isaac Gym): ``_post_step`` and ``_change_char_color`` are no-ops.
 """
 import copy
@@ -75,14 +75,11 @@ class CommonPlayer:
 
     def _engine_cfg(self):
         """Flags of the forward-only engine behind the network (ase_amd.inference.InferenceEngine)."""
-        from ..inference import _INFER_CFG
-        c = dict(_INFER_CFG)
-        c.update(normalize_input=self.normalize_input, normalize_value=self.config.get('normalize_value', False),
-                 normalize_amp_input=self.config.get('normalize_amp_input', True), seed=self.config.get('seed', 0))
-        return c
+        return dict(normalize_input=self.normalize_input, normalize_value=self.config.get('normalize_value', False),
+                    normalize_amp_input=self.config.get('normalize_amp_input', True), seed=self.config.get('seed', 0))
 
     def _build_net(self, config):
-        from ..engine import UpdateEngine
+        from ..forward import ForwardEngine
         from ..inference import InferenceEngine
         self.model = self.network.build(config)
         self.model.to(self.device)
@@ -96,7 +93,7 @@ class CommonPlayer:
         # the trainer's resolver: f16gp32 / f16gpx3 checkpoints play in f16, mixed_precision without a precision key = f16
         from ..cfg import resolve_precision
         self.precision, dtype = resolve_precision(self.config)
-        self.engine = UpdateEngine(net.kind, net, self._engine_cfg(), backend, minibatch=0, amp_minibatch=0, dtype=dtype)
+        self.engine = ForwardEngine(net.kind, net, self._engine_cfg(), backend, dtype=dtype)
         net.infer = InferenceEngine(net, self.engine)
         self.action_rng = torch.tensor([int(self.config.get('seed', 0)) ^ 0x91A7E5, 0], dtype=torch.int64, device=self.device)
 
