@@ -81,24 +81,6 @@ template <> __device__ __forceinline__ f16_t from_f32_plain<f16_t>(float x) { re
 __device__ __forceinline__ float floor_nan(float x, float lo) { return x < lo ? lo : x; }
 __device__ __forceinline__ float ceil_nan(float x, float hi) { return x > hi ? hi : x; }
 
-// ---- f32h_t shadows (ASE_F32H3): W * 2^e split into half hi / lo parts, packed [8 hi | 8 lo] per group of 8 consecutive elements of the
-// contracted dimension (written by ase_hip_refresh_shadow and ase_hip_apply_multi_v2, read by Mma<f32h_t>) -----------------------------
-// (saturating, like every other conversion into half storage: a weight beyond +-32 at the scale 2^11 must not become inf and then NaN
-//  in every product; once per weight and step, free.  The A operand's split stays a plain cast in the kernel's loop: its inputs are
-//  bounded by construction - observations clamped to +-5 at 2^12, see _gp_value)
-__device__ __forceinline__ void split_half(float v, float scale, f16_t& hi, f16_t& lo) {
-    const float s = __builtin_amdgcn_fmed3f(v * scale, -65504.f, 65504.f);
-    hi = (f16_t)s;
-    lo = (f16_t)(s - (float)hi);
-}
-__device__ __forceinline__ void store_split(char* row, int col, float v, float scale) {
-    f16_t hi, lo;
-    split_half(v, scale, hi, lo);
-    char* g = row + (col >> 3) * 32 + (col & 7) * 2;
-    *reinterpret_cast<f16_t*>(g) = hi;
-    *reinterpret_cast<f16_t*>(g + 16) = lo;
-}
-
 // ---- the two 16-bit storage types share every kernel: vector types and the matrix instruction by type -----------
 template <typename T> struct V16;
 template <> struct V16<bf16_t> { typedef bf16x8 x8; typedef bf16x4 x4; };

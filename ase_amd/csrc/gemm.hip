@@ -1,6 +1,6 @@
 // C entry points of the NT matrix-core kernels (gfx950 / CDNA4): argument checks, kernel choice, debug hooks.  The kernels
-// live in gemm_nt_kernels.h and are instantiated per storage type in gemm_nt_<type>.hip; the weight-gradient kernels and the
-// shadow refresh in gemm_tn.hip.
+// live in gemm_nt_kernels.h and are instantiated per storage type in gemm_nt_<type>.hip; the weight-gradient kernels in
+// gemm_tn.hip, the shadow refresh beside the optimizer in optim.hip.
 #include "gemm_nt.h"
 #include <math.h>
 

@@ -1,4 +1,4 @@
-// Weight-gradient ("TN") matrix-core kernels (gfx950 / CDNA4) and the shadow-weight refresh.
+// Weight-gradient ("TN") matrix-core kernels (gfx950 / CDNA4).
 //
 //   gemm_tn : G += alpha * Aᵀ·B   weight (+ bias) gradient
 //   TN kernels: gemm_tn_kernel (128 x 128, register-staged, transposed LDS reads, split over M, f32 atomics) and the phased
@@ -719,125 +719,7 @@ template <typename T> int launch_tn(TNParams p, hipStream_t stream) {
     return ASE_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// refresh_shadow: f32 master [n_real, k_real] -> dtype W_s [*, ldws] and transposed Wt_s [*, ldwts]
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void refresh_shadow_kernel(const float* __restrict__ W, int n_real, int k_real, T* __restrict__ Ws,
-                                      int64_t ldws, T* __restrict__ Wts, int64_t ldwts, int split_src, int gap) {
-    __shared__ float tile[32][33];
-    const int k0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = n0 + ty + 8 * i, k = k0 + tx;
-        float v = 0.f;
-        if (n < n_real && k < k_real) v = W[(int64_t)n * k_real + k];
-        tile[ty + 8 * i][tx] = v;
-        if (Ws && n < n_real && k < k_real) {
-            const int kd = (k < split_src) ? k : k + gap;
-            Ws[(int64_t)n * ldws + kd] = from_f32<T>(v);
-        }
-    }
-    __syncthreads();
-    if (Wts) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = k0 + ty + 8 * i, n = n0 + tx;
-            if (k < k_real && n < n_real) {
-                const int kd = (k < split_src) ? k : k + gap;
-                Wts[(int64_t)kd * ldwts + n] = from_f32<T>(tile[tx][ty + 8 * i]);
-            }
-        }
-    }
-}
-
-// f32h_t shadows (ASE_F32H3): W * 2^e split into half hi / lo parts, packed [8 hi | 8 lo] per group of 8 consecutive elements of
-// the contracted (contiguous) dimension - k for W_s, n for W_s^T; 4 bytes per element, leading dimensions in 4-byte units like the
-// f32 shadows they replace.  (See Mma<f32h_t> in gemm_nt_kernels.h.)
-// (store_split / split_half: common.h - ase_hip_apply_multi_v2 writes the same shadows from its own tiles)
-__global__ void refresh_shadow_split_kernel(const float* __restrict__ W, int n_real, int k_real, char* __restrict__ Ws, int64_t ldws,
-                                            char* __restrict__ Wts, int64_t ldwts, int split_src, int gap, float scale) {
-    __shared__ float tile[32][33];
-    const int k0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = n0 + ty + 8 * i, k = k0 + tx;
-        float v = 0.f;
-        if (n < n_real && k < k_real) v = W[(int64_t)n * k_real + k];
-        tile[ty + 8 * i][tx] = v;
-        if (Ws && n < n_real && k < k_real) store_split(Ws + (int64_t)n * ldws * 4, (k < split_src) ? k : k + gap, v, scale);
-    }
-    __syncthreads();
-    if (Wts) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = k0 + ty + 8 * i, n = n0 + tx;
-            if (k < k_real && n < n_real)
-                store_split(Wts + (int64_t)((k < split_src) ? k : k + gap) * ldwts * 4, n, tile[tx][ty + 8 * i], scale);
-        }
-    }
-}
-
-// All layers in one launch: desc[l] = {W, n_real, k_real, Ws, ldws, Wts, ldwts, split_src, gap, bias, bias_shadow, tiles_k}
-// (int64 each); blockIdx.y = layer, blockIdx.x = 32x32 tile (grid-stride), bias copied by the first workgroup.
-template <typename T>
-__global__ __launch_bounds__(256) void refresh_multi_kernel(const int64_t* __restrict__ desc) {
-    __shared__ float tile[32][33];
-    const int64_t* d = desc + 12 * blockIdx.y;
-    const float* W = reinterpret_cast<const float*>(d[0]);
-    const int n_real = (int)d[1], k_real = (int)d[2];
-    T* Ws = reinterpret_cast<T*>(d[3]);
-    const int64_t ldws = d[4];
-    T* Wts = reinterpret_cast<T*>(d[5]);
-    const int64_t ldwts = d[6];
-    const int split_src = (int)d[7], gap = (int)d[8];
-    const int tiles_k = (int)d[11];
-    const int tiles = tiles_k * ((n_real + 31) / 32);
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    if (blockIdx.x == 0 && d[9]) {
-        const float* b = reinterpret_cast<const float*>(d[9]);
-        float* bs = reinterpret_cast<float*>(d[10]);
-        for (int i = threadIdx.x; i < n_real; i += 256) bs[i] = b[i];
-    }
-    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
-        const int k0 = (t % tiles_k) * 32, n0 = (t / tiles_k) * 32;
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = n0 + ty + 8 * i, k = k0 + tx;
-            float v = 0.f;
-            if (n < n_real && k < k_real) {
-                v = W[(int64_t)n * k_real + k];
-                Ws[(int64_t)n * ldws + ((k < split_src) ? k : k + gap)] = from_f32<T>(v);
-            }
-            tile[ty + 8 * i][tx] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = k0 + ty + 8 * i, n = n0 + tx;
-            if (k < k_real && n < n_real)
-                Wts[(int64_t)((k < split_src) ? k : k + gap) * ldwts + n] = from_f32<T>(tile[tx][ty + 8 * i]);
-        }
-    }
-}
-
 }  // namespace
-
-extern "C" int ase_hip_refresh_shadow_multi(const int64_t* desc, int n_layers, int dtype, void* stream) {
-    ASE_CHECK_ARG(desc && n_layers > 0, "refresh_shadow_multi: null/empty operand");
-    const dim3 grid(256, n_layers);
-    const int rc = ase_dispatch_storage(dtype, [&](auto tag) {
-        typedef typename decltype(tag)::type T;
-        ASE_LAUNCH(refresh_multi_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, desc);
-        return ASE_OK;
-    });
-    ASE_CHECK_ARG(rc == ASE_OK, "refresh_shadow_multi: bad dtype %d", dtype);
-    ASE_CHECK_LAUNCH("refresh_shadow_multi");
-    return ASE_OK;
-}
 
 // The single-problem launch's kernel choice (ase_hip_gemm_tn and ase_hip_gemm_tn_kernel_id: written once).  The phased 256 x 256
 // kernel takes a 16-bit problem only when few M-splits fill the chip (its split reduction costs 256 KB of memory-side atomics
@@ -1038,31 +920,4 @@ extern "C" int ase_hip_gemm_tn_grouped(const int64_t* problems, const int32_t* w
                   "gemm_tn_grouped: a workspace needs the reduce table of the plan (and 16-byte alignment)");
     if (dtype == ASE_F16) return launch_tn8g<f16_t>(problems, work, n_work, red, n_red, workspace, alpha_dev, (hipStream_t)stream);
     return launch_tn8g<bf16_t>(problems, work, n_work, red, n_red, workspace, alpha_dev, (hipStream_t)stream);
-}
-
-extern "C" int ase_hip_refresh_shadow(const float* W, int n_real, int k_real, void* Ws, int64_t ldws, void* Wts,
-                                      int64_t ldwts, int split_src, int split_dst, int dtype, void* stream) {
-    ASE_CHECK_ARG(W && n_real > 0 && k_real > 0 && (Ws || Wts), "refresh_shadow: null/empty operand");
-    ASE_CHECK_ARG(split_src <= split_dst && split_src <= k_real, "refresh_shadow: bad split");
-    const dim3 grid((k_real + 31) / 32, (n_real + 31) / 32), block(256);
-    const int gap = split_dst - split_src;
-    if ((dtype & 0xFF) == ASE_F32H3) {           // packed half split of W * 2^eb (eb in bits 16-23, as in ase_hip_gemm_nt's dtype word)
-        const int eb = (dtype >> 16) & 0xFF;
-        ASE_CHECK_ARG(eb <= 24 && ((dtype >> 8) & 0xFF) == 0, "refresh_shadow: ASE_F32H3 takes the weight scale exponent 0..24 in bits 16-23");
-        ASE_CHECK_ARG((Ws == nullptr || (ldws % 8 == 0 && ((uintptr_t)Ws % 32) == 0)) && (Wts == nullptr || (ldwts % 8 == 0 && ((uintptr_t)Wts % 32) == 0)),
-                      "refresh_shadow: packed split shadows need 32-byte aligned rows (leading dimensions in whole groups of 8)");
-        ASE_LAUNCH(refresh_shadow_split_kernel, grid, block, 0, (hipStream_t)stream, W, n_real, k_real, (char*)Ws, ldws, (char*)Wts, ldwts,
-                   split_src, gap, ldexpf(1.f, eb));
-        ASE_CHECK_LAUNCH("refresh_shadow");
-        return ASE_OK;
-    }
-    const int rc = ase_dispatch_storage(dtype, [&](auto tag) {
-        typedef typename decltype(tag)::type T;
-        ASE_LAUNCH(refresh_shadow_kernel<T>, grid, block, 0, (hipStream_t)stream, W, n_real, k_real, (T*)Ws, ldws, (T*)Wts, ldwts,
-                   split_src, gap);
-        return ASE_OK;
-    });
-    ASE_CHECK_ARG(rc == ASE_OK, "refresh_shadow: bad dtype %d", dtype);
-    ASE_CHECK_LAUNCH("refresh_shadow");
-    return ASE_OK;
 }

@@ -1,5 +1,5 @@
-// Optimizer step (torch.optim.Adam semantics) and the weight-only gradient terms.
-#include "common.h"
+// Optimizer step (torch.optim.Adam semantics), the weight-only gradient terms and the shadow-weight refresh.
+#include "shadow.h"
 #include <type_traits>
 
 namespace {
@@ -66,23 +66,6 @@ __device__ __forceinline__ float adam_elem(float w, float gi, float& mi, float& 
 // odd-sized bias vectors: dword alignment is all the hardware asks of a global dwordx4)
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 
-template <typename T> __device__ __forceinline__ void store_shadow4(T* p, const float (&w)[4]);
-template <> __device__ __forceinline__ void store_shadow4<bf16_t>(bf16_t* p, const float (&w)[4]) {
-    bf16x4 v;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] = (bf16_t)w[c];
-    *reinterpret_cast<bf16x4*>(p) = v;
-}
-template <> __device__ __forceinline__ void store_shadow4<f16_t>(f16_t* p, const float (&w)[4]) {
-    f16x4 v;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] = from_f32<f16_t>(w[c]);
-    *reinterpret_cast<f16x4*>(p) = v;
-}
-template <> __device__ __forceinline__ void store_shadow4<float>(float* p, const float (&w)[4]) {
-    *reinterpret_cast<f32x4*>(p) = f32x4{w[0], w[1], w[2], w[3]};
-}
-
 // (8 waves per SIMD = 64 registers: the small kernels run in what the matrix kernels leave free; 62 without the second shadow pair)
 // SPLIT: the instantiation that may write the second shadow pair (desc2); the plain one is the kernel it always was
 template <typename T, bool SPLIT>
@@ -93,8 +76,14 @@ __global__ __launch_bounds__(256, SPLIT ? 8 : 1) void apply_multi_kernel(const i
     const int64_t* d = desc + 24 * blockIdx.y;
     // second shadow pair of the layer (desc2, nullable; a row of zeros: none): the packed half-split shadows of W * 2^eb
     // (ASE_F32H3, as ase_hip_refresh_shadow writes them) from the same tile - pitches in BYTES from here on
-    // (its fields are read where they are used, behind the optimizer arithmetic: held across it they cost 5 registers of 64)
+    // (its fields are read where they are used, behind the optimizer arithmetic: held across it they cost 5 registers of 64;
+    //  without SPLIT it is a constant pair of nulls and every store through it folds away)
     const int64_t* e3 = (SPLIT && desc2) ? desc2 + 8 * blockIdx.y : nullptr;
+    const auto pair3 = [&] {
+        if (!e3) return ShadowPair<f32h_t>{nullptr, 0, nullptr, 0, 0.f};
+        return ShadowPair<f32h_t>{reinterpret_cast<char*>(e3[0]), e3[1] * 4, reinterpret_cast<char*>(e3[2]), e3[3] * 4,
+                                  ldexpf(1.f, (int)e3[4])};
+    };
     float* W = reinterpret_cast<float*>(d[0]);
     const int n_real = (int)d[1], k_real = (int)d[2];
     T* Ws = reinterpret_cast<T*>(d[3]);
@@ -138,7 +127,7 @@ __global__ __launch_bounds__(256, SPLIT ? 8 : 1) void apply_multi_kernel(const i
     if (d[21]) {
         const int tk = (k_real + 127) / 128;
         const int tilesv = tk * ((n_real + 31) / 32);
-        const int vx = threadIdx.x & 31, vy = threadIdx.x >> 5;
+        const int vx = tx, vy = ty;
         for (int t = blockIdx.x; t < tilesv; t += gridDim.x) {
             const int k0 = (t % tk) * 128, n0 = (t / tk) * 32;
             __syncthreads();
@@ -174,7 +163,7 @@ __global__ __launch_bounds__(256, SPLIT ? 8 : 1) void apply_multi_kernel(const i
                         *reinterpret_cast<f4u*>(mW + o) = mv;
                         *reinterpret_cast<f4u*>(vW + o) = vv;
                     }
-                    store_shadow4<T>(Ws + (int64_t)n * ldws + ((k < split_src) ? k : k + gap), w);
+                    store_shadow4<T>(Ws + (int64_t)n * ldws + shadow_col(k, split_src, gap), w);
                 }
 #pragma unroll
                 for (int c = 0; c < 4; ++c) tile[vy + 8 * i][4 * vx + c] = w[c];
@@ -183,7 +172,7 @@ __global__ __launch_bounds__(256, SPLIT ? 8 : 1) void apply_multi_kernel(const i
             const int kk = threadIdx.x >> 1, half = threadIdx.x & 1;
             const int k = k0 + kk, nb = n0 + 16 * half;
             if (k < k_real && nb < n_real) {
-                T* dst = Wts + (int64_t)((k < split_src) ? k : k + gap) * ldwts + nb;
+                T* dst = Wts + (int64_t)shadow_col(k, split_src, gap) * ldwts + nb;
                 if (nb + 16 <= n_real) {
 #pragma unroll
                     for (int q = 0; q < 16; q += 4) {
@@ -194,32 +183,22 @@ __global__ __launch_bounds__(256, SPLIT ? 8 : 1) void apply_multi_kernel(const i
                 } else {
                     for (int q = 0; q < 16 && nb + q < n_real; ++q) dst[q] = from_f32<T>(tile[16 * half + q][kk]);
                 }
-                if (SPLIT && e3 && e3[2]) {
-                    const float sc3 = ldexpf(1.f, (int)e3[4]);
-                    char* row = reinterpret_cast<char*>(e3[2]) + (int64_t)((k < split_src) ? k : k + gap) * (e3[3] * 4);
+                if (const ShadowPair<f32h_t> s3 = pair3(); s3.Wts) {
+                    char* row = s3.Wts + (int64_t)shadow_col(k, split_src, gap) * s3.ldwts;
                     if (nb + 16 <= n_real) {             // 4 x (4 hi halves, 4 lo halves): half a group of 8 each
 #pragma unroll
                         for (int q = 0; q < 16; q += 4) {
-                            f16x4 h, l;
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) {
-                                f16_t hh, ll;
-                                split_half(tile[16 * half + q + c][kk], sc3, hh, ll);
-                                h[c] = hh; l[c] = ll;
-                            }
-                            char* g = row + ((nb + q) >> 3) * 32 + ((nb + q) & 7) * 2;
-                            *reinterpret_cast<f16x4*>(g) = h;
-                            *reinterpret_cast<f16x4*>(g + 16) = l;
+                            const float w4[4] = {tile[16 * half + q][kk], tile[16 * half + q + 1][kk], tile[16 * half + q + 2][kk],
+                                                 tile[16 * half + q + 3][kk]};
+                            store_split4(row, nb + q, w4, s3.scale);
                         }
                     } else {
-                        for (int q = 0; q < 16 && nb + q < n_real; ++q) store_split(row, nb + q, tile[16 * half + q][kk], sc3);
+                        for (int q = 0; q < 16 && nb + q < n_real; ++q) store_split(row, nb + q, tile[16 * half + q][kk], s3.scale);
                     }
                 }
             }
-            if (SPLIT && e3 && e3[0]) {       // W_s's second shadow from the tile too (not beside the optimizer's registers): 16 k of one row per thread
-                const float sc3 = ldexpf(1.f, (int)e3[4]);
-                char* Ws3 = reinterpret_cast<char*>(e3[0]);
-                const int64_t ld3 = e3[1] * 4;
+            // W_s's second shadow from the tile too (not beside the optimizer's registers): 16 k of one row per thread
+            if (const ShadowPair<f32h_t> s3 = pair3(); s3.Ws) {
                 const int rr = threadIdx.x >> 3, kc = (threadIdx.x & 7) * 16;
                 const int n = n0 + rr;
                 if (n < n_real) {
@@ -227,60 +206,36 @@ __global__ __launch_bounds__(256, SPLIT ? 8 : 1) void apply_multi_kernel(const i
                     for (int u = 0; u < 16; u += 4) {
                         const int k4 = k0 + kc + u;
                         if (k4 < k_real) {               // (k_real % 4 == 0; kd % 4 == 0: half a group of 8)
-                            const int kd = (k4 < split_src) ? k4 : k4 + gap;
-                            f16x4 h, l;
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) {
-                                f16_t hh, ll;
-                                split_half(tile[rr][kc + u + c], sc3, hh, ll);
-                                h[c] = hh; l[c] = ll;
-                            }
-                            char* g = Ws3 + (int64_t)n * ld3 + (kd >> 3) * 32 + (kd & 7) * 2;
-                            *reinterpret_cast<f16x4*>(g) = h;
-                            *reinterpret_cast<f16x4*>(g + 16) = l;
+                            const float w4[4] = {tile[rr][kc + u], tile[rr][kc + u + 1], tile[rr][kc + u + 2], tile[rr][kc + u + 3]};
+                            store_split4(s3.Ws + (int64_t)n * s3.ldws, shadow_col(k4, split_src, gap), w4, s3.scale);
                         }
                     }
                 }
             }
         }
-    } else
-    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
-        const int k0 = (t % tiles_k) * 32, n0 = (t / tiles_k) * 32;
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int n = n0 + ty + 8 * i, k = k0 + tx;
-            float w = 0.f;
-            if (n < n_real && k < k_real) {
-                const int64_t o = (int64_t)n * k_real + k;
-                w = W[o];
-                if (adam) {
-                    if (slot_a >= 0) w2[0] += (double)w * (double)w;
-                    float gi = gW[o];
-                    if (wd != 0.f) {
-                        gi = gi + wd * w;
-                        gW[o] = gi;                       // the exported gradient includes the weight-only terms
-                    }
-                    float mi = mW[o], vi = vW[o];
-                    w = adam_elem(w, gi, mi, vi, one_m_b1, b2, one_m_b2, eps, step_size, bc2_sqrt);
-                    W[o] = w; mW[o] = mi; vW[o] = vi;
+    } else {
+        // ---- scalar path: the shared 32 x 32 tile walk, the optimizer as its load
+        const auto step = [&](int n, int k) {
+            const int64_t o = (int64_t)n * k_real + k;
+            float w = W[o];
+            if (adam) {
+                if (slot_a >= 0) w2[0] += (double)w * (double)w;
+                float gi = gW[o];
+                if (wd != 0.f) {
+                    gi = gi + wd * w;
+                    gW[o] = gi;                       // the exported gradient includes the weight-only terms
                 }
-                Ws[(int64_t)n * ldws + ((k < split_src) ? k : k + gap)] = from_f32<T>(w);
-                if (SPLIT && e3 && e3[0])
-                    store_split(reinterpret_cast<char*>(e3[0]) + (int64_t)n * (e3[1] * 4), (k < split_src) ? k : k + gap, w, ldexpf(1.f, (int)e3[4]));
+                float mi = mW[o], vi = vW[o];
+                w = adam_elem(w, gi, mi, vi, one_m_b1, b2, one_m_b2, eps, step_size, bc2_sqrt);
+                W[o] = w; mW[o] = mi; vW[o] = vi;
             }
-            tile[ty + 8 * i][tx] = w;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = k0 + ty + 8 * i, n = n0 + tx;
-            if (k < k_real && n < n_real) {
-                Wts[(int64_t)((k < split_src) ? k : k + gap) * ldwts + n] = from_f32<T>(tile[tx][ty + 8 * i]);
-                if (SPLIT && e3 && e3[2])
-                    store_split(reinterpret_cast<char*>(e3[2]) + (int64_t)((k < split_src) ? k : k + gap) * (e3[3] * 4), n, tile[tx][ty + 8 * i],
-                                ldexpf(1.f, (int)e3[4]));
-            }
+            return w;
+        };
+        const ShadowPair<T> pair{Ws, ldws, Wts, ldwts};
+        for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+            const int k0 = (t % tiles_k) * 32, n0 = (t / tiles_k) * 32;
+            __syncthreads();
+            shadow_tile32(tile, n0, k0, n_real, k_real, split_src, gap, tx, ty, step, pair, pair3());
         }
     }
     if (adam && slot_a >= 0) {
@@ -290,6 +245,39 @@ __global__ __launch_bounds__(256, SPLIT ? 8 : 1) void apply_multi_kernel(const i
             atomic_add_f64(acc + slot_a, w2[0]);
             if (slot_b >= 0) atomic_add_f64(acc + slot_b, w2[0]);
         }
+    }
+}
+
+// ---- shadow refresh without an optimizer step: the same tile walk, a plain read as its load ---------------------------------------------
+// one layer, one tile per workgroup; T = f32h_t: the packed half split.  Either shadow may be absent.
+template <typename T>
+__global__ void refresh_shadow_kernel(const float* __restrict__ W, int n_real, int k_real, ShadowPair<T, true> pair, int split_src, int gap) {
+    __shared__ float tile[32][33];
+    shadow_tile32(tile, blockIdx.y * 32, blockIdx.x * 32, n_real, k_real, split_src, gap, threadIdx.x & 31, threadIdx.x >> 5,
+                  [&](int n, int k) { return W[(int64_t)n * k_real + k]; }, pair);
+}
+
+// All layers in one launch: desc[l] = fields 0..11 of the optimizer's table (int64 each); blockIdx.y = layer, blockIdx.x = 32 x 32
+// tile (grid-stride), bias copied by the first workgroup.
+template <typename T>
+__global__ __launch_bounds__(256) void refresh_multi_kernel(const int64_t* __restrict__ desc) {
+    __shared__ float tile[32][33];
+    const int64_t* d = desc + 12 * blockIdx.y;
+    const float* W = reinterpret_cast<const float*>(d[0]);
+    const int n_real = (int)d[1], k_real = (int)d[2];
+    const ShadowPair<T> pair{reinterpret_cast<T*>(d[3]), d[4], reinterpret_cast<T*>(d[5]), d[6]};
+    const int split_src = (int)d[7], gap = (int)d[8];
+    const int tiles_k = (int)d[11];
+    const int tiles = tiles_k * ((n_real + 31) / 32);
+    if (blockIdx.x == 0 && d[9]) {
+        const float* b = reinterpret_cast<const float*>(d[9]);
+        float* bs = reinterpret_cast<float*>(d[10]);
+        for (int i = threadIdx.x; i < n_real; i += 256) bs[i] = b[i];
+    }
+    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+        __syncthreads();
+        shadow_tile32(tile, (t / tiles_k) * 32, (t % tiles_k) * 32, n_real, k_real, split_src, gap, threadIdx.x & 31, threadIdx.x >> 5,
+                      [&](int n, int k) { return W[(int64_t)n * k_real + k]; }, pair);
     }
 }
 
@@ -373,4 +361,44 @@ extern "C" int ase_hip_apply_multi_v2(const int64_t* desc, int n_layers, const i
                                       int dtype, void* stream) {
     ASE_CHECK_ARG(desc2 != nullptr, "apply_multi_v2: null table of the second shadow pairs");
     return apply_multi_impl(desc, n_layers, desc2, opt_state, acc, dtype, stream);
+}
+
+extern "C" int ase_hip_refresh_shadow_multi(const int64_t* desc, int n_layers, int dtype, void* stream) {
+    ASE_CHECK_ARG(desc && n_layers > 0, "refresh_shadow_multi: null/empty operand");
+    const dim3 grid(256, n_layers);
+    const int rc = ase_dispatch_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        ASE_LAUNCH(refresh_multi_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, desc);
+        return ASE_OK;
+    });
+    ASE_CHECK_ARG(rc == ASE_OK, "refresh_shadow_multi: bad dtype %d", dtype);
+    ASE_CHECK_LAUNCH("refresh_shadow_multi");
+    return ASE_OK;
+}
+
+extern "C" int ase_hip_refresh_shadow(const float* W, int n_real, int k_real, void* Ws, int64_t ldws, void* Wts,
+                                      int64_t ldwts, int split_src, int split_dst, int dtype, void* stream) {
+    ASE_CHECK_ARG(W && n_real > 0 && k_real > 0 && (Ws || Wts), "refresh_shadow: null/empty operand");
+    ASE_CHECK_ARG(split_src <= split_dst && split_src <= k_real, "refresh_shadow: bad split");
+    const dim3 grid((k_real + 31) / 32, (n_real + 31) / 32), block(256);
+    const int gap = split_dst - split_src;
+    if ((dtype & 0xFF) == ASE_F32H3) {           // packed half split of W * 2^eb (eb in bits 16-23, as in ase_hip_gemm_nt's dtype word)
+        const int eb = (dtype >> 16) & 0xFF;
+        ASE_CHECK_ARG(eb <= 24 && ((dtype >> 8) & 0xFF) == 0, "refresh_shadow: ASE_F32H3 takes the weight scale exponent 0..24 in bits 16-23");
+        ASE_CHECK_ARG((Ws == nullptr || (ldws % 8 == 0 && ((uintptr_t)Ws % 32) == 0)) && (Wts == nullptr || (ldwts % 8 == 0 && ((uintptr_t)Wts % 32) == 0)),
+                      "refresh_shadow: packed split shadows need 32-byte aligned rows (leading dimensions in whole groups of 8)");
+        const ShadowPair<f32h_t, true> pair{(char*)Ws, ldws * 4, (char*)Wts, ldwts * 4, ldexpf(1.f, eb)};
+        ASE_LAUNCH(refresh_shadow_kernel<f32h_t>, grid, block, 0, (hipStream_t)stream, W, n_real, k_real, pair, split_src, gap);
+        ASE_CHECK_LAUNCH("refresh_shadow");
+        return ASE_OK;
+    }
+    const int rc = ase_dispatch_storage(dtype, [&](auto tag) {
+        typedef typename decltype(tag)::type T;
+        const ShadowPair<T, true> pair{(T*)Ws, ldws, (T*)Wts, ldwts};
+        ASE_LAUNCH(refresh_shadow_kernel<T>, grid, block, 0, (hipStream_t)stream, W, n_real, k_real, pair, split_src, gap);
+        return ASE_OK;
+    });
+    ASE_CHECK_ARG(rc == ASE_OK, "refresh_shadow: bad dtype %d", dtype);
+    ASE_CHECK_LAUNCH("refresh_shadow");
+    return ASE_OK;
 }

@@ -497,28 +497,25 @@ class UpdateEngine(ForwardEngine):
                 t[1].append(L.ACC_DISC_W2)
         base = self.params.data_ptr()
         rows, items = [], []
-        for d in self.layers:
-            for (name, nr, off), W, b, gW, gb in zip(d.parts, d.W, d.b, d.gW, d.gb):
-                ws, wts, bs = d.Ws[off:], d.Wts[:, off:], d.bs[off:off + nr]
-                ow, ob = (W.data_ptr() - base) // 4, (b.data_ptr() - base) // 4
-                mW, vW = self.adam_m[ow:ow + W.numel()], self.adam_v[ow:ow + W.numel()]
-                mb, vb = self.adam_m[ob:ob + nr], self.adam_v[ob:ob + nr]
-                coef, slots = terms.get(W.data_ptr(), [0.0, []])
-                assert len(slots) <= 2, slots
-                sa = slots[0] if len(slots) > 0 else -1
-                sb = slots[1] if len(slots) > 1 else -1
-                gap = d.split_dst - d.split_src
-                # 16-byte path of the kernel: rows in whole 4-element chunks on every side (the first layers' K = obs + z
-                # = 317 stays on the scalar path)
-                wide = int(self._apply_wide and d.K % 4 == 0 and ws.stride(0) % 4 == 0 and wts.stride(0) % 4 == 0
-                           and (d.split_src >= d.K or (d.split_src % 4 == 0 and gap % 4 == 0))
-                           and ws.data_ptr() % 16 == 0 and wts.data_ptr() % 16 == 0)
-                rows.append([W.data_ptr(), nr, d.K, ws.data_ptr(), ws.stride(0), wts.data_ptr(), wts.stride(0), d.split_src,
-                             gap, b.data_ptr(), bs.data_ptr(), (d.K + 31) // 32, gW.data_ptr(),
-                             mW.data_ptr(), vW.data_ptr(), gb.data_ptr(), mb.data_ptr(), vb.data_ptr(),
-                             struct.unpack('<i', struct.pack('<f', float(coef)))[0], sa, sb, wide, 0, 0])
-                items.append((W, ws, wts, d.split_src, d.split_dst, b, bs, gW.view(-1).view_as(W), mW.view_as(W), vW.view_as(W),
-                              gb, mb, vb, float(coef), sa, sb))
+        for d, j, row, item in self._shadow_rows():           # the refresh table's twelve fields, then the optimizer's twelve
+            W, ws, wts, _, _, b, bs = item
+            gW, gb, nr = d.gW[j], d.gb[j], b.numel()
+            ow, ob = (W.data_ptr() - base) // 4, (b.data_ptr() - base) // 4
+            mW, vW = self.adam_m[ow:ow + W.numel()], self.adam_v[ow:ow + W.numel()]
+            mb, vb = self.adam_m[ob:ob + nr], self.adam_v[ob:ob + nr]
+            coef, slots = terms.get(W.data_ptr(), [0.0, []])
+            assert len(slots) <= 2, slots
+            sa = slots[0] if len(slots) > 0 else -1
+            sb = slots[1] if len(slots) > 1 else -1
+            gap = d.split_dst - d.split_src
+            # 16-byte path of the kernel: rows in whole 4-element chunks on every side (the first layers' K = obs + z
+            # = 317 stays on the scalar path)
+            wide = int(self._apply_wide and d.K % 4 == 0 and ws.stride(0) % 4 == 0 and wts.stride(0) % 4 == 0
+                       and (d.split_src >= d.K or (d.split_src % 4 == 0 and gap % 4 == 0))
+                       and ws.data_ptr() % 16 == 0 and wts.data_ptr() % 16 == 0)
+            rows.append(row + [gW.data_ptr(), mW.data_ptr(), vW.data_ptr(), gb.data_ptr(), mb.data_ptr(), vb.data_ptr(),
+                               struct.unpack('<i', struct.pack('<f', float(coef)))[0], sa, sb, wide, 0, 0])
+            items.append(item + (gW.view(-1).view_as(W), mW.view_as(W), vW.view_as(W), gb, mb, vb, float(coef), sa, sb))
         n_pol = sum(len(d.parts) for d in self.style + self.actor + [self.mu_head] + self.critic + [self.value_head])
         if self.sigma_mode == 'vector':
             # the learned log-std vector: a bias-only row (no weight matrix: k_real = 0, no shadow tiles) whose "bias" is the

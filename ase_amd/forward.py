@@ -169,18 +169,22 @@ class ForwardEngine:
         self.val_state = torch.tensor([0.0, 1.0, 1.0], dtype=torch.float64, device=dev)
 
     # ------------------------------------------------------------------ shadows
+    def _shadow_rows(self):
+        """Per layer part (d, j): the twelve fields [W, n_real, k_real, Ws, ldws, Wts, ldwts, split_src, gap, bias, bias_shadow,
+        tiles_k] that open a row of the refresh table and of the optimizer's, and the tensors they point into."""
+        for d in self.layers:
+            for j, ((name, nr, off), W, b) in enumerate(zip(d.parts, d.W, d.b)):
+                ws, wts, bs = d.Ws[off:], d.Wts[:, off:], d.bs[off:off + nr]
+                yield d, j, [W.data_ptr(), nr, d.K, ws.data_ptr(), ws.stride(0), wts.data_ptr(), wts.stride(0), d.split_src,
+                             d.split_dst - d.split_src, b.data_ptr(), bs.data_ptr(), (d.K + 31) // 32], \
+                    (W, ws, wts, d.split_src, d.split_dst, b, bs)
+
     def refresh_shadows(self):
         """Master f32 weights -> compute-dtype shadows (W, W^T, padded bias) for every layer: one launch."""
         if self._refresh_desc is None:
-            rows, items = [], []
-            for d in self.layers:
-                for (name, nr, off), W, b in zip(d.parts, d.W, d.b):
-                    ws, wts, bs = d.Ws[off:], d.Wts[:, off:], d.bs[off:off + nr]
-                    rows.append([W.data_ptr(), nr, d.K, ws.data_ptr(), ws.stride(0), wts.data_ptr(), wts.stride(0),
-                                 d.split_src, d.split_dst - d.split_src, b.data_ptr(), bs.data_ptr(), (d.K + 31) // 32])
-                    items.append((W, ws, wts, d.split_src, d.split_dst, b, bs))
-            self._refresh_desc = torch.tensor(rows, dtype=torch.int64, device=self.dev)
-            self._refresh_items = items
+            parts = list(self._shadow_rows())
+            self._refresh_desc = torch.tensor([row for _, _, row, _ in parts], dtype=torch.int64, device=self.dev)
+            self._refresh_items = [item for _, _, _, item in parts]
         self.be.refresh_shadow_multi(self._refresh_desc, self._refresh_items, self.dtype)
 
     # ------------------------------------------------------------------ primitive layer ops

@@ -90,7 +90,7 @@ def _twin_factors(act, t):
 
 def half_split(x, e, saturate=True):
     """x (f32) -> (hi, lo) as the ASE_F32H3 kernels form them: sx = x * 2^e, hi = half(sx), lo = half(sx - hi), both returned as f64
-    values.  saturate: the SHADOWS' split (csrc/common.h split_half) clamps to +-65504; the A operand's split in the kernel's loop
+    values.  saturate: the SHADOWS' split (csrc/shadow.h split_half) clamps to +-65504; the A operand's split in the kernel's loop
     (csrc/gemm_nt_kernels.h split_f16) is a plain cast: beyond half's range hi is inf and the product NaN (include/ase_hip.h:
     "overflow turns the output into NaN")."""
     sx = x.float() * (2.0 ** e)

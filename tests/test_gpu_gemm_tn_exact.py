@@ -4,7 +4,9 @@ it (f32 atomics), and the shadow refresh kernels that produce these kernels' B o
 tests/ref_gemm_tn.py, NOT the emulator (tests/test_gemm_ref.py runs the same lists through the emulator on the CPU).
 
 The operands are integers (tests/ref_gemm_tn.py states and asserts the conditions), so the split-M partial sums are exact in any
-order and G / gbias are compared bit for bit - there is no tolerance in this file, the atomic paths included.  Every
+order and G / gbias are compared bit for bit - there is no tolerance in this file, the atomic paths included.  (The refresh kernels
+live beside the optimizer in csrc/optim.hip, on the tile routine of csrc/shadow.h; their half-split form is held to the packer of
+tests/ref_split_pack.py.)  Every
 single-problem case asserts ase_hip_gemm_tn_kernel_id first; G and gbias are windows of longer sentinel buffers that must come
 back intact around them; the operands' pitch columns and the rows after M hold NaN, and in the `poison` variants so do the pad
 columns the header names (no NaN may reach G or gbias)."""
@@ -13,6 +15,7 @@ import torch
 
 from ase_amd import lib as L
 from tests import ref_gemm_tn as T
+from tests import ref_split_pack as S
 
 pytestmark = pytest.mark.gpu
 
@@ -170,4 +173,31 @@ def test_refresh_shadow_equals_torch_conversion(backends, dt, n, k, ss, sd):
     want_bs[:n] = b.cpu()
     assert torch.equal(_bits(bs.cpu()), _bits(want_bs))
     TOTALS['elements'] += 4 * (want_ws.numel() + want_wts.numel())
+    TOTALS['cases'] += 1
+
+
+@pytest.mark.parametrize('e', [0, 11, 24])
+@pytest.mark.parametrize('n,k,ss,sd', [(1, 1, 1, 1), (33, 65, 65, 65), (48, 53, 37, 64)])
+def test_refresh_shadow_half_split_equals_reference_packer(backends, n, k, ss, sd, e):
+    """The packed half-split pair (ASE_F32H3, W * 2^e) against the torch packer of tests/ref_split_pack.py as int32 words: saturated
+    elements, -0.0, zero and subnormal lo parts among them (the case asserts it), into sentinel-filled buffers whose leading
+    dimensions are larger than needed (whole groups of 8, 32-byte aligned base) - pad rows, pad columns, gap columns and the
+    uncovered positions of a partly covered group come back untouched.  W_s only, W_s^T only, both."""
+    be = backends['bf16']
+    dev = be.device
+    W = S.split_case(n, k, e, 100 * n + k + e)
+    kp = k + (sd - ss)
+    shape_ws, shape_wts = (n + 3, (kp + 7) // 8 * 8 + 8), (kp + 2, (n + 7) // 8 * 8 + 16)
+    want_ws, want_wts = S.expected_pair(W, e, ss, sd, shape_ws, shape_wts, SHADOW_SENTINEL)
+    Wd = W.to(dev)
+    for do_ws, do_wts in [(True, False), (False, True), (True, True)]:
+        Ws = torch.full(shape_ws, SHADOW_SENTINEL, device=dev)
+        Wts = torch.full(shape_wts, SHADOW_SENTINEL, device=dev)
+        assert Ws.data_ptr() % 32 == 0 and Wts.data_ptr() % 32 == 0
+        be.refresh_shadow(Wd, Ws if do_ws else None, Wts if do_wts else None, ss, sd, x3_exp=e)
+        for name, got, want, done in (('Ws', Ws.cpu(), want_ws, do_ws), ('Wts', Wts.cpu(), want_wts, do_wts)):
+            want = want if done else _bits(torch.full_like(got, SHADOW_SENTINEL))
+            bad = int((_bits(got) != want).sum())
+            assert bad == 0, (name, do_ws, do_wts, 'words not bitwise equal', bad, 'of', got.numel())
+    TOTALS['elements'] += 3 * (want_ws.numel() + want_wts.numel())
     TOTALS['cases'] += 1

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from ase_amd import lib as L
+from tests import ref_split_pack as S
 from tests.test_gp_fuse_emu import assert_same_step, run_steps
 
 pytestmark = pytest.mark.gpu
@@ -156,8 +157,8 @@ def _apply_case(n, k, split_src, gap, wide):
     gW, mW, vW = (torch.randn(n, k, generator=g) * 1e-3).to(dev), torch.zeros(n, k, device=dev), torch.zeros(n, k, device=dev)
     gb, mb, vb, bs = (torch.zeros(n, device=dev) for _ in range(4))
     ws, wts = torch.zeros(n, kp, dtype=torch.float16, device=dev), torch.zeros(kp, npad, dtype=torch.float16, device=dev)
-    Ws3, Wts3, R3, Rt3 = (torch.zeros(n, kp, device=dev), torch.zeros(kp, npad, device=dev), torch.zeros(n, kp, device=dev),
-                          torch.zeros(kp, npad, device=dev))
+    Ws3, Wts3, R3, Rt3 = (torch.full((n, kp), S.SENTINEL, device=dev), torch.full((kp, npad), S.SENTINEL, device=dev),
+                          torch.full((n, kp), S.SENTINEL, device=dev), torch.full((kp, npad), S.SENTINEL, device=dev))
     row = [W.data_ptr(), n, k, ws.data_ptr(), ws.stride(0), wts.data_ptr(), wts.stride(0), split_src, gap, b.data_ptr(),
            bs.data_ptr(), (k + 31) // 32, gW.data_ptr(), mW.data_ptr(), vW.data_ptr(), gb.data_ptr(), mb.data_ptr(), vb.data_ptr(),
            struct.unpack('<i', struct.pack('<f', 0.0))[0], -1, -1, int(wide), 0, 0]
@@ -180,13 +181,17 @@ def _apply_case(n, k, split_src, gap, wide):
                                                     (64, 256, 256, 0, 1)])                       # more than one tile along k and n
 def test_apply_multi_writes_the_half_split_shadows(n, k, split_src, gap, wide):
     """The second shadow pair out of the optimizer launch is byte-equal to ase_hip_refresh_shadow(x3_exp = 11) of the updated
-    masters (same split function), Ws and its transpose, padding untouched; the 16-bit shadow is still the rounded new weight."""
+    masters (same split function), Ws and its transpose, padding untouched; the 16-bit shadow is still the rounded new weight.
+    Both launches walk their tiles through csrc/shadow.h, so both pairs are also held to the torch packer of
+    tests/ref_split_pack.py (sentinel-filled buffers: pad and gap positions included)."""
     W0, W, ws, ref16, got, ref = _apply_case(n, k, split_src, gap, wide)
     assert float((W - W0).abs().min()) > 0                                     # every weight moved (Adam's first step)
     assert torch.equal(ws.view(torch.int16), ref16.view(torch.int16))
-    for a, r in zip(got, ref):
+    want = S.expected_pair(W.cpu(), 11, split_src, split_src + gap, tuple(got[0].shape), tuple(got[1].shape))
+    for a, r, w in zip(got, ref, want):
         assert float(r.abs().max()) > 0
         assert torch.equal(a.view(torch.int32), r.view(torch.int32))
+        assert torch.equal(a.view(torch.int32).cpu(), w) and torch.equal(r.view(torch.int32).cpu(), w)
 
 
 def test_normalize_multi_f32_twin(be):
