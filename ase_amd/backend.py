@@ -551,6 +551,47 @@ class HipBackend:
                                                _ptr(body_ang_vel), n, int(local_root_obs), int(root_height_obs), float(env_dt),
                                                _ptr(hist), S, self._stream()), "amp_reset_due")
 
+    # ------------------------------------------------------------------ demo fetch (N11)
+    def amp_demo_fetch(self, clips, out, ring_rows, head, n, num_steps, truncate_time, dt, local_root_obs, root_height_obs,
+                       motion_ids=None, motion_times0=None, rng_state=None, clip_cdf=None, advance=True, draws_out=None,
+                       head_dev=None):
+        """HumanoidAMP.fetch_amp_obs_demo + build_amp_obs_demo and the store into the demo ring in one launch (env/tasks/
+        humanoid_amp.py:63-105; operands and the draw table: see ase_hip_amp_demo_fetch).  clips: the dict of motion_state.
+        out: f32 [ring_rows, >= num_steps * F] with unit column stride (any row stride); sample i goes to row (head + i) %
+        ring_rows.  Either motion_ids (int32 [n]) and motion_times0 (f32 [n]) are passed in, or rng_state (int64 [2] = seed |
+        offset, advanced by one unless advance is false) and clip_cdf (uint32 bits in an int32 [n_clips] tensor) draw them on
+        the device.  draws_out: None or (int32 [n], f32 [n]) receiving every sample's clip and time.  head_dev: None or an int32
+        [1] device tensor added to head when the launch runs."""
+        B, D = clips['gts'].shape[1], int(clips['dof_offsets'][-1])
+        J, K = len(clips['dof_offsets']) - 1, len(clips['key_body_ids'])
+        n, S, F = int(n), int(num_steps), 13 + 6 * J + D + 3 * K
+        n_clips = clips['lengths'].numel()
+        ia = lambda xs: (C.c_int32 * len(xs))(*[int(x) for x in xs])
+        assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1, "out: f32 [ring_rows, >= n_steps * F] rows"
+        assert out.shape[0] >= ring_rows and out.shape[1] >= S * F and out.stride(0) >= S * F, "out: ring_rows rows of n_steps * F columns"
+        for k in ('gts', 'grs', 'lrs', 'grvs', 'gravs', 'dvs', 'lengths', 'dt'):
+            assert clips[k].dtype == torch.float32 and clips[k].is_contiguous()
+        for k in ('num_frames', 'length_starts'):
+            assert clips[k].dtype == torch.int32 and clips[k].is_contiguous() and clips[k].numel() == n_clips
+        assert clips['dt'].numel() == n_clips and len(clips['dof_body_ids']) == J
+        for t, dtype in ((motion_ids, torch.int32), (motion_times0, torch.float32)):
+            assert t is None or (t.dtype == dtype and t.is_contiguous() and t.shape == (n,)), "draws: int32 / f32 [n]"
+        assert rng_state is None or (rng_state.dtype == torch.int64 and rng_state.numel() == 2 and rng_state.is_contiguous())
+        assert clip_cdf is None or (clip_cdf.dtype == torch.int32 and clip_cdf.is_contiguous() and clip_cdf.shape == (n_clips,)), \
+            "clip_cdf: int32 [n_clips]"
+        ids_out, times_out = (None, None) if draws_out is None else draws_out
+        for t, dtype in ((ids_out, torch.int32), (times_out, torch.float32)):
+            assert t is None or (t.dtype == dtype and t.is_contiguous() and t.shape == (n,)), "draws_out: int32 / f32 [n]"
+        assert head_dev is None or (head_dev.dtype == torch.int32 and head_dev.numel() == 1)
+        L.check(self.lib.ase_hip_amp_demo_fetch(_ptr(clips['gts']), _ptr(clips['grs']), _ptr(clips['lrs']), _ptr(clips['grvs']),
+                                                _ptr(clips['gravs']), _ptr(clips['dvs']), B, _ptr(clips['lengths']),
+                                                _ptr(clips['num_frames']), _ptr(clips['dt']), _ptr(clips['length_starts']), n_clips,
+                                                ia(clips['dof_body_ids']), ia(clips['dof_offsets']), J, ia(clips['key_body_ids']), K,
+                                                _ptr(motion_ids), _ptr(motion_times0), _ptr(rng_state), _ptr(clip_cdf), int(advance),
+                                                _ptr(ids_out), _ptr(times_out), n, S, float(truncate_time), float(dt),
+                                                int(local_root_obs), int(root_height_obs), _ptr(out), out.stride(0), int(ring_rows),
+                                                int(head), _ptr(head_dev), self._stream()), "amp_demo_fetch")
+
     # ------------------------------------------------------------------ normaliser / gather
     def rms_moments(self, src, D, idx, remap, M, state, sums):
         L.check(self.lib.ase_hip_rms_moments(_ptr(src), _ld(src), D, _ptr(idx), remap[0], remap[1], M, _ptr(state),

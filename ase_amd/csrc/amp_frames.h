@@ -1,7 +1,7 @@
 // The per-sample device functions of the AMP observation side - whole, and in the parts a kernel may spread over lanes -
-// shared by amp_obs.hip (whole batches) and amp_reset.hip (the reset rows of an environment): the motion-clip sampler (utils/motion_lib.py:122-172,263-272,296-325;
+// shared by amp_obs.hip (whole batches), amp_reset.hip (the reset rows of an environment) and amp_demo.hip (the demo fetch): the motion-clip sampler (utils/motion_lib.py:122-172,263-272,296-325;
 // utils/torch_utils.py:7-28,94-118) and one frame of the discriminator observation (env/tasks/humanoid_amp.py:280-316,
-// env/tasks/humanoid.py:523-552).  Both files compile with -ffp-contract=off: every expression rounds operation by operation.
+// env/tasks/humanoid.py:523-552).  All three compile with -ffp-contract=off: every expression rounds operation by operation.
 #pragma once
 #include "common.h"
 #include "quat.h"
@@ -60,14 +60,17 @@ __device__ __forceinline__ void motion_root(const MotionClips& a, const FrameBle
         root_ang_vel[c] = a.gravs[fb.f0 * 3 + c];
     }
 }
-// world position of key body k
-__device__ __forceinline__ void motion_key(const MotionClips& a, const FrameBlend& fb, int k, float* out) {
+// world position of body b (amp_demo.hip keeps a key-body table longer than kMaxJoints)
+__device__ __forceinline__ void motion_body(const MotionClips& a, const FrameBlend& fb, int b, float* out) {
     const float blend = fb.blend;
     const float* p0 = a.gts + fb.f0 * a.B * 3;
     const float* p1 = a.gts + fb.f1 * a.B * 3;
-    const int b = a.key_body[k];
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[c] = (1.f - blend) * p0[b * 3 + c] + blend * p1[b * 3 + c];
+}
+// world position of key body k
+__device__ __forceinline__ void motion_key(const MotionClips& a, const FrameBlend& fb, int k, float* out) {
+    motion_body(a, fb, a.key_body[k], out);
 }
 // dof positions of joint j from its local rotation; dof d sits at dp[d * dof_stride]
 __device__ __forceinline__ void motion_joint(const MotionClips& a, const FrameBlend& fb, int j, float* dp, int64_t dof_stride) {

@@ -969,6 +969,12 @@ class AMPAgent(CommonAgent):
         self._disc_reward_scale = config['disc_reward_scale']
         self._normalize_amp_input = config.get('normalize_amp_input', True)
         self._amp_replay_keep_prob = config['amp_replay_keep_prob']
+        # opt-in: the environment writes demo observations straight into the demo ring, drawn on the device (one launch, no
+        # staging tensor, no ring_store) - other values than the torch generator's, hence not the default
+        self._device_demo_fetch = bool(config.get('device_demo_fetch', False))
+        if self._device_demo_fetch:
+            env = getattr(self.vec_env, 'env', self.vec_env)
+            assert hasattr(env, 'fetch_amp_obs_demo_into'), "device_demo_fetch needs an environment with fetch_amp_obs_demo_into"
 
     def _build_net_config(self):
         c = super()._build_net_config()
@@ -1042,14 +1048,23 @@ class AMPAgent(CommonAgent):
         env = getattr(self.vec_env, 'env', self.vec_env)          # the reference reaches through vec_env.env
         return env.fetch_amp_obs_demo(n).to(self.ppo_device)
 
+    def _store_amp_obs_demo(self):
+        """One batch of demo observations into the demo ring."""
+        if self._device_demo_fetch:
+            env = getattr(self.vec_env, 'env', self.vec_env)
+            self._amp_obs_demo_buffer.store_with(env.fetch_amp_obs_demo_into, self._amp_batch_size,
+                                                 self._amp_observation_space.shape[0])
+        else:
+            self._amp_obs_demo_buffer.store(self._fetch_amp_obs_demo(self._amp_batch_size))
+
     def _init_amp_demo_buf(self):
         size = self._amp_obs_demo_buffer.get_buffer_size()
         for _ in range(int(np.ceil(size / self._amp_batch_size))):
-            self._amp_obs_demo_buffer.store(self._fetch_amp_obs_demo(self._amp_batch_size))
+            self._store_amp_obs_demo()
         self._demo_ready = True
 
     def _update_amp_demos(self):
-        self._amp_obs_demo_buffer.store(self._fetch_amp_obs_demo(self._amp_batch_size))
+        self._store_amp_obs_demo()
 
     def _store_replay_amp_obs(self, amp_obs_exp):
         buf = self._amp_replay_buffer

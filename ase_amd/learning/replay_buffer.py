@@ -49,6 +49,19 @@ class ReplayBuffer:
         self._head = (self._head + n) % self._buffer_size
         self._total_count += n
 
+    def store_with(self, produce, n, width):
+        """Append n rows that ``produce(data, ring_rows, head, n)`` writes in place, rows ``(head + i) % ring_rows`` of the
+        [ring_rows, width] storage: a producer kernel stores into the ring itself, without a staging tensor or ``ring_store``."""
+        n = int(n)
+        if n == 0:
+            return
+        assert n <= self._buffer_size
+        self._ensure(int(width))
+        assert self._data.shape[1] == int(width)
+        produce(self._data, self._buffer_size, self._head, n)
+        self._head = (self._head + n) % self._buffer_size
+        self._total_count += n
+
     def sample_indices(self, n):
         size = self._buffer_size
         idx = torch.arange(self._sample_head, self._sample_head + n, device=self._device) % size

@@ -97,6 +97,8 @@ SIGNATURES = {
                           _p, _p, _p, _p, _i, _i, _i, _f, _p, _i, _p],
     "ase_hip_amp_reset_due": [_p] * 6 + [_i] + [_p] * 6 + [_i, _p, _i] + [_p, _i] + [_p, _p, _p, _i] + [_i, _d, _i, _d, _d, _i]
                              + [_p, _i] + [_p] * 4 + [_p] * 5 + [_p, _i64, _p, _p, _i64, _i] + [_p] * 4 + [_i, _i, _i, _f, _p, _i, _p],
+    "ase_hip_amp_demo_fetch": [_p] * 6 + [_i] + [_p] * 4 + [_i, _p, _p, _i, _p, _i] + [_p] * 4 + [_i, _p, _p] + [_i, _i, _f, _f, _i, _i]
+                              + [_p, _i64, _i, _i, _p, _p],
     "ase_hip_clip_frames": [_p] * 6 + [_i] + [_p] * 4 + [_i, _i, _p, _p, _i] + [_p] * 7,
     "ase_hip_gemm_nt_kernel_id": [_i, _i, _i, _i],
     "ase_hip_gemm_tn_kernel_id": [_i, _i, _i, _i, _i, _i64, _i64, _i],

@@ -12,6 +12,8 @@ does, stored f32.  ``from_reference`` takes a loaded reference ``MotionLib`` ins
 Sampling: everything per sample - frame blend, slerp of the root and every local rotation, exponential-map dof positions,
 key-body interpolation, then the 140-float observation frame (root height, tangent-normal root rotation, local velocities,
 dof observations, key bodies) - runs in two HIP kernels (``ase_hip_motion_state``, ``ase_hip_build_amp_obs``).
+``AmpObsDemoSource.fetch_into`` is the whole demo fetch - draws, sampler, frames and the store into the demo ring - as one
+launch (``ase_hip_amp_demo_fetch``, N11).
 
 There is no host fallback for either.  Not here: FBX / MJCF import, retargeting, clips that store global rotations.
 """
@@ -122,7 +124,7 @@ def read_motion_files(motion_file, dof_body_ids, dof_offsets, key_body_ids):
 
 
 def clip_cdf(weights):
-    """The table of the device-side weighted clip choice (``ase_hip_amp_reset_due``): ``cdf[m] = floor(2^24 cumsum(w)[m] /
+    """The table of the device-side weighted clip choice (``ase_hip_amp_reset_due``, ``ase_hip_amp_demo_fetch``): ``cdf[m] = floor(2^24 cumsum(w)[m] /
     sum(w) + 0.5)`` taken in f64, the last entry ``2^24``; a 24-bit draw ``v`` picks the first clip with ``v < cdf[m]``, so clip
     m has probability ``(cdf[m] - cdf[m - 1]) / 2^24`` exactly and a clip of weight zero is never drawn.  -> int32 [n_clips]
     (the uint32 the kernel reads: no entry exceeds 2^24).  A positive weight whose interval comes out empty is refused."""
@@ -225,7 +227,7 @@ class AmpObsDemoSource:
     """``HumanoidAMP.fetch_amp_obs_demo`` (env/tasks/humanoid_amp.py:63-84): ``num_samples`` demo observations of
     ``num_amp_obs_steps`` frames each, newest frame first, frame k taken ``k * dt`` before the sampled time."""
 
-    def __init__(self, motion_lib, backend, num_amp_obs_steps=10, dt=1.0 / 30.0, local_root_obs=True, root_height_obs=True):
+    def __init__(self, motion_lib, backend, num_amp_obs_steps=10, dt=1.0 / 30.0, local_root_obs=True, root_height_obs=True, seed=0):
         self._motion_lib, self.be = motion_lib, backend
         self._num_amp_obs_steps, self.dt = int(num_amp_obs_steps), float(dt)
         self._local_root_obs, self._root_height_obs = bool(local_root_obs), bool(root_height_obs)
@@ -233,9 +235,31 @@ class AmpObsDemoSource:
         n_joints = len(c['dof_offsets']) - 1
         self._num_amp_obs_per_step = 13 + 6 * n_joints + c['dof_offsets'][-1] + 3 * len(c['key_body_ids'])   # humanoid_amp.py:107-118
         self._amp_obs_demo_buf = None
+        # the Philox stream {seed, offset} of the device-side fetch (fetch_into); a call moves the offset on by one
+        self.rng_state = torch.tensor([int(seed), 0], dtype=torch.int64, device=motion_lib._device)
 
     def get_num_amp_obs(self):
         return self._num_amp_obs_steps * self._num_amp_obs_per_step
+
+    def fetch_into(self, out, ring_rows, head, n, *, motion_ids=None, motion_times0=None, advance=True, draws_out=None, head_dev=None):
+        """``fetch_amp_obs_demo(n)`` written straight into rows ``(head + i) % ring_rows`` of ``out`` [ring_rows, >= steps *
+        per_step] by ONE launch (``ase_hip_amp_demo_fetch``): no intermediate tensor, no staging buffer.  Without ``motion_ids`` /
+        ``motion_times0`` the clips and times are drawn on the device, from ``clip_cdf`` and this source's ``rng_state`` (the
+        draw table: include/ase_hip.h) - NOT the values a torch generator gives, which is why ``fetch_amp_obs_demo`` stays as it
+        is.  With them (int32 / f32 [n]) the rows are bitwise ``build_amp_obs_demo(motion_ids, motion_times0)``."""
+        ml = self._motion_lib
+        truncate_time = self.dt * (self._num_amp_obs_steps - 1)
+        drawn = motion_ids is None and motion_times0 is None
+        self.be.amp_demo_fetch(ml.clips, out, ring_rows, head, n, self._num_amp_obs_steps, truncate_time, self.dt,
+                               self._local_root_obs, self._root_height_obs, motion_ids=motion_ids, motion_times0=motion_times0,
+                               rng_state=self.rng_state if drawn else None, clip_cdf=ml.clip_cdf if drawn else None,
+                               advance=advance, draws_out=draws_out, head_dev=head_dev)
+
+    def fetch_amp_obs_demo_device(self, num_samples):
+        """``fetch_amp_obs_demo`` with the draws on the device -> a fresh [num_samples, steps * per_step] tensor."""
+        out = torch.empty(num_samples, self.get_num_amp_obs(), dtype=torch.float32, device=self._motion_lib._device)
+        self.fetch_into(out, num_samples, 0, num_samples)
+        return out
 
     def fetch_amp_obs_demo(self, num_samples):
         ml = self._motion_lib

@@ -64,6 +64,13 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
                                                       reset_buf != 0: due test, draws (Philox stream {seed, offset}), apply and
                                                       _reset_env_tensors in one launch (humanoid_amp.py:132-201,
                                                       humanoid_amp_getup.py:78-114, humanoid.py:165-167)
+  amp_demo_fetch(out, ring_rows, head, n, num_steps, truncate_time, dt, motion_ids, motion_times0, rng_state, clip_cdf,
+                 motion_ids_out, motion_times0_out, clip tensors ..., dof_body_ids, dof_offsets, key_body_ids, local_root_obs,
+                 root_height_obs, advance=True, head_dev=None) -> ()
+                                                      (out, rng_state and the draw outputs written in place) the demo fetch:
+                                                      draws (passed in, or the Philox stream {seed, offset}), motion sampler,
+                                                      frames and the store into the demo ring in one launch
+                                                      (env/tasks/humanoid_amp.py:63-105)
   clip_frames(rotation, root_translation, root_velocity, root_angular_velocity, local_translation, clip_first, clip_num_frames,
               clip_fps, frame_clip, parent_indices, dof_body_ids, dof_offsets) -> (gts, grs, lrs, grvs, gravs, dvs)
                                                       the clip loader: forward kinematics and joint velocities of every frame of
@@ -743,6 +750,34 @@ def amp_reset_due(root_states: torch.Tensor, dof_pos: torch.Tensor, dof_vel: tor
                              reset_buf, terminate_buf, recovery_counter, plan, root_states, dof_pos, dof_vel,
                              _f32c(body_pos, 'body_pos'), _f32c(body_rot, 'body_rot'), _f32c(body_vel, 'body_vel'),
                              _f32c(body_ang_vel, 'body_ang_vel'), local_root_obs, root_height_obs, env_dt, hist, advance)
+
+
+@torch.library.custom_op('ase_hip::amp_demo_fetch', mutates_args=('out', 'rng_state', 'motion_ids_out', 'motion_times0_out'),
+                         device_types='cuda')
+def amp_demo_fetch(out: torch.Tensor, ring_rows: int, head: int, n: int, num_steps: int, truncate_time: float, dt: float,
+                   motion_ids: torch.Tensor | None, motion_times0: torch.Tensor | None, rng_state: torch.Tensor | None,
+                   clip_cdf: torch.Tensor | None, motion_ids_out: torch.Tensor | None, motion_times0_out: torch.Tensor | None,
+                   gts: torch.Tensor, grs: torch.Tensor, lrs: torch.Tensor, grvs: torch.Tensor, gravs: torch.Tensor,
+                   dvs: torch.Tensor, lengths: torch.Tensor, num_frames: torch.Tensor, clip_dt: torch.Tensor,
+                   length_starts: torch.Tensor, dof_body_ids: list[int], dof_offsets: list[int], key_body_ids: list[int],
+                   local_root_obs: bool, root_height_obs: bool, advance: bool = True, head_dev: torch.Tensor | None = None) -> None:
+    """The demo fetch in one launch (operands and the draw table: see ase_hip_amp_demo_fetch): n demo observations of num_steps
+    frames go to rows (head + i) % ring_rows of out [ring_rows, >= num_steps F].  Either motion_ids / motion_times0 are passed
+    in or rng_state / clip_cdf draw them on the device; motion_ids_out / motion_times0_out come both or none."""
+    given, drawn = (motion_ids, motion_times0), (rng_state, clip_cdf)
+    has_given, has_drawn = all(t is not None for t in given), all(t is not None for t in drawn)
+    _check(has_given or all(t is None for t in given), 'amp_demo_fetch: motion_ids and motion_times0 come together')
+    _check(has_drawn or all(t is None for t in drawn), 'amp_demo_fetch: rng_state and clip_cdf come together')
+    _check(has_given != has_drawn, 'amp_demo_fetch: either motion_ids / motion_times0 or rng_state / clip_cdf')
+    _check((motion_ids_out is None) == (motion_times0_out is None), 'amp_demo_fetch: the draw outputs come both or none')
+    _check(out.dim() == 2 and out.dtype == torch.float32 and out.is_cuda and out.stride(1) == 1, 'amp_demo_fetch: out is an f32 '
+           'device tensor [ring_rows, >= num_steps F] with unit column stride')
+    clips = dict(gts=gts, grs=grs, lrs=lrs, grvs=grvs, gravs=gravs, dvs=dvs, lengths=lengths, num_frames=num_frames, dt=clip_dt,
+                 length_starts=length_starts, dof_body_ids=dof_body_ids, dof_offsets=dof_offsets, key_body_ids=key_body_ids)
+    _backend().amp_demo_fetch(clips, out, ring_rows, head, n, num_steps, truncate_time, dt, local_root_obs, root_height_obs,
+                              motion_ids=motion_ids, motion_times0=motion_times0, rng_state=rng_state, clip_cdf=clip_cdf,
+                              advance=advance, draws_out=None if motion_ids_out is None else (motion_ids_out, motion_times0_out),
+                              head_dev=head_dev)
 
 
 @torch.library.custom_op('ase_hip::clip_frames', mutates_args=(), device_types='cuda')

@@ -181,6 +181,12 @@ class SyntheticVecEnv:
             return self.demo_source.fetch_amp_obs_demo(n)
         return self.amp_fs.draw(n, self.gen, mean=0.3).to(self.device)
 
+    def fetch_amp_obs_demo_into(self, data, ring_rows, head, n):
+        """n demo observations written straight into rows (head + i) % ring_rows of the ring ``data`` by the demo source's one
+        launch, drawn on the device (``AmpObsDemoSource.fetch_into``; the agents' ``device_demo_fetch``)."""
+        assert self.demo_source is not None, "fetch_amp_obs_demo_into needs a demo_source"
+        self.demo_source.fetch_into(data, ring_rows, head, n)
+
     def reset(self, env_ids=None):
         if env_ids is None:
             ids = torch.arange(self.num_envs)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew, ase_hip_amp_reset_due and ase_hip_gemm_tn_kernel_id were added WITHOUT a new version
+/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch and ase_hip_gemm_tn_kernel_id were added WITHOUT a new version
  *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
  *  load time) */
 #define ASE_HIP_ABI_VERSION 9
@@ -810,6 +810,44 @@ int ase_hip_amp_reset_due(const float* gts, const float* grs, const float* lrs, 
                           const float* body_pos, const float* body_rot, const float* body_vel, const float* body_ang_vel,
                           int n_envs, int local_root_obs, int root_height_obs, float env_dt, float* hist, int n_steps,
                           void* stream);
+
+/* The demo fetch (an addition to ABI 9, nothing else changed): n demo observations of n_steps frames each,
+ * drawn, sampled, built and stored into the demo ring by ONE launch over the (sample i, slot k) items, no intermediate tensor.
+ * Clip tensors, HOST index arrays and the frame layout F = 13 + 6 n_joints + D + 3 n_key as in ase_hip_motion_state /
+ * ase_hip_build_amp_obs; lengths / num_frames / dt / length_starts have n_clips entries.  Up to 78 key bodies (F <= 255).
+ * Where sample i's clip m and time t0 come from - exactly one pair is non-NULL:
+ *   motion_ids (DEVICE int32 [n]), motion_times0 (f32 [n]): passed in, read when the launch runs.  A motion_ids[i] outside
+ *             [0, n_clips) leaves sample i's row unwritten and is never dereferenced.
+ *   rng_state (u64[2] = {seed, offset} on the device, as in ase_hip_amp_reset_due), cdf (DEVICE uint32 [n_clips], the table of
+ *             ase_hip_amp_reset_due): draw j of sample i comes from element 2 i + j of the stream ("uniform": the 24-bit uniform
+ *             (c[2] >> 8) * 2^-24 of the element, f32):
+ *               j = 0  v = c[2] >> 8  the 24-bit integer behind the uniform: m is the first clip with v < cdf[m]
+ *               j = 1  uniform u      t0 = u * (lengths[m] - truncate_time) + truncate_time, three f32 operations each rounded
+ *                                     on its own (MotionLib.sample_time(truncate_time) + truncate_time; a clip shorter than
+ *                                     truncate_time gives t0 in (length, truncate_time], as the reference does)
+ *             advance != 0: the offset moves on by one behind the launch (a call is one stream position).
+ * motion_ids_out / motion_times0_out (nullable, both or none; int32 / f32 [n]) receive every sample's (m, t0), in both modes.
+ * Slot k of sample i is the frame of clip m at the f32 time t0 + (-step_dt) * (float)k (product and sum rounded on their own),
+ * used UNCLAMPED as ase_hip_amp_reset does: what build_amp_obs_demo's motion_times0.unsqueeze(-1) + (-dt * arange(n_steps)),
+ * ase_hip_motion_state and ase_hip_build_amp_obs compute, bit for bit - the same device functions.
+ * Sample i goes to row (head + i) % ring_rows of out (f32 [ring_rows, ld_out], ld_out >= n_steps * F), slot k at columns
+ * [k F, (k + 1) F); columns behind n_steps * F and all other rows are not written.  ring_rows = n, head = 0: a plain
+ * [n, n_steps F] output.  head_dev (nullable, DEVICE int32 [1]): read when the launch runs and added to head, so that a
+ * recorded launch follows a ring head kept on the device; a value outside [0, ring_rows) leaves every row unwritten.
+ * Refused: a NULL operand of the mode; both modes or neither; half an export; n < 1; n_steps outside [1, 64]; n > ring_rows;
+ * head outside [0, ring_rows); ld_out < n_steps * F; n_joints outside [1, 32]; a joint of other than 1 or 3 dofs;
+ * dof_offsets[0] != 0; key / dof body ids outside [0, n_bodies); F > 255; n_clips < 1; a tile beyond 64 KB (n_steps > 32 of a
+ * wide frame).
+ * Replaces: HumanoidAMP.fetch_amp_obs_demo / build_amp_obs_demo (env/tasks/humanoid_amp.py:63-105), MotionLib.sample_motions /
+ *   sample_time (utils/motion_lib.py:100-119) and the store into the demo ring (learning/amp_agent.py:498-533). */
+int ase_hip_amp_demo_fetch(const float* gts, const float* grs, const float* lrs, const float* grvs, const float* gravs,
+                           const float* dvs, int n_bodies, const float* lengths, const int32_t* num_frames, const float* dt,
+                           const int32_t* length_starts, int n_clips, const int32_t* dof_body_ids, const int32_t* dof_offsets,
+                           int n_joints, const int32_t* key_body_ids, int n_key, const int32_t* motion_ids,
+                           const float* motion_times0, uint64_t* rng_state, const uint32_t* cdf, int advance,
+                           int32_t* motion_ids_out, float* motion_times0_out, int n, int n_steps, float truncate_time,
+                           float step_dt, int local_root_obs, int root_height_obs, float* out, int64_t ld_out, int ring_rows,
+                           int head, const int32_t* head_dev, void* stream);
 
 /* Motion-clip loader: the frame arrays of ase_hip_motion_state / ase_hip_amp_reset from the raw contents of
  * SkeletonMotion clip files, every frame of every clip in ONE launch.  Inputs (DEVICE, all clips concatenated along the

@@ -394,6 +394,19 @@ def main():
             us = timeit(lambda: src.fetch_amp_obs_demo(ns), n=100)
             print(json.dumps({'measurement': 'fetch_amp_obs_demo (sample motions + times, motion state, 10-frame observations)',
                               'samples': ns, 'us_per_call': round(us, 1), 'out_bytes': ns * 1400 * 4}), flush=True)
+        # one demo-ring refill of config 2 (512 samples x 10 frames; the ring here has 8192 rows, its size does not enter), both
+        # ways in this process: the host-driven chain (torch draws, two launches, staging tensor, ring_store) and the one launch
+        # that draws on the device and stores into the ring itself (N11).  Seven repeats of 100 calls each: median and spread.
+        # Calls are issued back to back and timed between two events, as every figure above: the larger of host and GPU time.
+        from ase_amd.learning.replay_buffer import ReplayBuffer
+        ring_a, ring_b = ReplayBuffer(8192, 'cuda:0', be), ReplayBuffer(8192, 'cuda:0', be)
+        ways = (('demo-ring refill, host-driven chain (fetch_amp_obs_demo + ring_store)', lambda: ring_a.store(src.fetch_amp_obs_demo(512))),
+                ('demo-ring refill, one launch (amp_demo_fetch into the ring)', lambda: ring_b.store_with(src.fetch_into, 512, 1400)))
+        for name, fn in ways:
+            reps = sorted(timeit(fn, n=100) for _ in range(7))
+            print(json.dumps({'measurement': name, 'samples': 512, 'frames': 10, 'us_per_call_median': round(reps[3], 1),
+                              'us_per_call_min': round(reps[0], 1), 'us_per_call_max': round(reps[-1], 1), 'repeats': 7,
+                              'calls_per_repeat': 100}), flush=True)
 
 
 if __name__ == '__main__':
