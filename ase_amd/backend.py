@@ -592,6 +592,92 @@ class HipBackend:
                                                 int(local_root_obs), int(root_height_obs), _ptr(out), out.stride(0), int(ring_rows),
                                                 int(head), _ptr(head_dev), self._stream()), "amp_demo_fetch")
 
+    # ------------------------------------------------------------------ one environment step into the experience (N12)
+    _KINDS = {torch.uint8: L.KIND_U8, torch.bool: L.KIND_U8, torch.int32: L.KIND_I32, torch.int64: L.KIND_I64,
+              torch.float32: L.KIND_F32}
+
+    def _rollout_store_table(self, n, n_slots, fields):
+        """The device field table of rollout_store, kept per field set (addresses and pitches; the slot is no part of it).
+        A new set is uploaded from pinned memory without waiting for the copy.  A table is never dropped: a launch program that
+        recorded a call holds its address (768 bytes at most per set).  Only addresses on this backend's device enter it."""
+        rows = []
+        for src, dst in fields:
+            assert self._here(src) and self._here(dst), \
+                f"fields: tensors on {self.device} (the table holds raw addresses the kernel dereferences)"
+            assert src.dtype == torch.float32 and dst.dtype == torch.float32, "fields: f32"
+            src = src.view(n, -1) if src.dim() != 2 else src
+            D = src.shape[1]
+            assert src.shape[0] == n and D >= 1 and (D == 1 or src.stride(1) == 1) and src.stride(0) >= D, "field source: [n_envs, D] rows"
+            dst = dst.view(dst.shape[0], n, -1) if dst.dim() != 3 else dst
+            assert dst.shape == (n_slots, n, D) and (D == 1 or dst.stride(2) == 1) and dst.stride(1) >= D and \
+                dst.stride(0) >= n * dst.stride(1), "field destination: [n_slots, n_envs, D] rows"
+            rows.append((src.data_ptr(), src.stride(0), D, dst.data_ptr(), dst.stride(1), dst.stride(0)))
+        key = tuple(rows)
+        tabs = self.__dict__.setdefault('_rs_tables', {})
+        hit = tabs.get(key)
+        if hit is None:
+            hit = tabs[key] = torch.tensor(rows, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+        return hit
+
+    def rollout_store(self, dones, slot=0, n_slots=None, fields=(), rewards=None, shift=0.0, scale=1.0, rewards_out=None,
+                      dones_out=None, next_values=None, terminate=None, next_values_out=None, cur_rewards=None,
+                      cur_lengths=None, meter=None, max_size=0, workspace=None, done_ids_out=None, slot_dev=None):
+        """What play_steps does behind env_step, for experience slot `slot`, in one entry (learning/common_agent.py:267-293;
+        operands: see ase_hip_rollout_store).  dones [n_envs] uint8 / bool / int32 / int64 / f32.  fields: (source [n_envs, D],
+        destination [n_slots, n_envs, D]) pairs of f32 tensors with unit column stride, at most 16.  rewards f32 [n_envs];
+        rewards_out / next_values_out f32 and dones_out uint8 are [n_slots, n_envs(, 1)] buffers, next_values f32 [n_envs] with
+        terminate typed like dones.  cur_rewards / cur_lengths f32 [n_envs] are updated in place and come with meter (f64 [4] =
+        reward mean, length mean, current size, episodes seen) and max_size; workspace (f64, lib.rollout_store_ws(n_envs)) is
+        the backend's own when None, one per size and stream.  Every tensor lives on the backend's device.  done_ids_out int32 [n_envs].  slot_dev: None or an int32 [1] device tensor read when the
+        launch runs, in place of slot.  Recordable in a launch program."""
+        n = dones.numel()
+        vec = lambda t, dt, who: None if t is None else self._rs_vec(t, n, dt, who)
+        dones, terminate = vec(dones, None, 'dones'), vec(terminate, None, 'terminate')
+        rewards, next_values = vec(rewards, torch.float32, 'rewards'), vec(next_values, torch.float32, 'next_values')
+        cur_rewards, cur_lengths = vec(cur_rewards, torch.float32, 'cur_rewards'), vec(cur_lengths, torch.float32, 'cur_lengths')
+        done_ids_out = vec(done_ids_out, torch.int32, 'done_ids_out')
+        slotted = [(rewards_out, torch.float32), (dones_out, torch.uint8), (next_values_out, torch.float32)]
+        for t, dt in slotted:
+            if t is not None:
+                assert self._here(t), f"slotted output: a tensor on {self.device}"
+                assert t.dtype == dt and t.dim() >= 2 and t[0].numel() == n and t.shape[1] == n and t.stride(1) == 1, \
+                    "slotted output: [n_slots, n_envs(, 1)], unit stride over the environments"
+                assert n_slots is None or n_slots == t.shape[0], "outputs disagree on n_slots"
+                n_slots = t.shape[0]
+        if n_slots is None:
+            n_slots = fields[0][1].shape[0] if fields else 1
+        table = self._rollout_store_table(n, n_slots, fields) if fields else None
+        assert meter is None or (meter.dtype == torch.float64 and meter.numel() == 4 and meter.is_contiguous() and
+                                 self._here(meter)), "meter: f64 [4] on the device"
+        if meter is not None and workspace is None:
+            # private to a call until it completes: calls of one stream are ordered, so the backend keeps one per stream
+            ws, key = self.__dict__.setdefault('_rs_ws', {}), (n, torch.cuda.current_stream(self.device).cuda_stream)
+            workspace = ws.get(key)
+            if workspace is None:
+                workspace = ws[key] = torch.zeros(L.rollout_store_ws(n), dtype=torch.float64, device=self.device)
+        assert workspace is None or (workspace.dtype == torch.float64 and workspace.is_contiguous() and
+                                     self._here(workspace)), "workspace: f64 on the device"
+        assert slot_dev is None or (slot_dev.dtype == torch.int32 and slot_dev.numel() == 1 and self._here(slot_dev))
+        kind = lambda t: 0 if t is None else self._KINDS[t.dtype]
+        L.check(self.lib.ase_hip_rollout_store(_ptr(table), len(fields), _ptr(rewards), float(shift), float(scale),
+                                               _ptr(rewards_out), _ld(rewards_out), _ptr(dones), kind(dones), _ptr(dones_out),
+                                               _ld(dones_out), _ptr(next_values), _ptr(terminate), kind(terminate),
+                                               _ptr(next_values_out), _ld(next_values_out), _ptr(cur_rewards), _ptr(cur_lengths),
+                                               _ptr(meter), int(max_size), _ptr(workspace),
+                                               0 if workspace is None else workspace.numel(), _ptr(done_ids_out), n, int(slot),
+                                               _ptr(slot_dev), int(n_slots), self._stream()), "rollout_store")
+
+    def _here(self, t):
+        """Whether a tensor lives on this backend's GPU (a device given without an index is the current one)."""
+        return t.is_cuda and t.device.index == (torch.cuda.current_device() if self.device.index is None else self.device.index)
+
+    def _rs_vec(self, t, n, dtype, who):
+        cls = type(self)
+        assert self._here(t), f"{who}: a tensor on {self.device}, not {t.device}"
+        assert t.numel() == n and t.is_contiguous() and (t.dtype == dtype if dtype is not None else t.dtype in cls._KINDS), \
+            f"{who}: contiguous [n_envs] of {dtype or 'uint8 / bool / int32 / int64 / float32'}"
+        return t
+
     # ------------------------------------------------------------------ normaliser / gather
     def rms_moments(self, src, D, idx, remap, M, state, sums):
         L.check(self.lib.ase_hip_rms_moments(_ptr(src), _ld(src), D, _ptr(idx), remap[0], remap[1], M, _ptr(state),

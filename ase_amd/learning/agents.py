@@ -60,6 +60,46 @@ class AverageMeter:
         return self.mean.squeeze(0).cpu().numpy()
 
 
+class DeviceMeterWords:
+    """The four words ase_hip_rollout_store keeps on the device (f64 [4] = reward mean, length mean, current size, episodes
+    seen) and ONE host copy of them, fetched when somebody asks and dropped when the rollout loop has written again."""
+
+    def __init__(self, words):
+        self.words, self._host = words, None
+
+    def read(self):
+        if self._host is None:
+            self._host = self.words.cpu()
+        return self._host
+
+    def written(self):
+        self._host = None
+
+
+class DeviceMeter:
+    """One of the two means of the device meter behind AverageMeter's interface.  current_size and get_mean() of both views
+    share one read of the four words per rollout (DeviceMeterWords): train() asks three times per epoch and waits for the device
+    once.  The two means share current_size, as the two AverageMeters of the rollout loop always hold the same one; clear() of
+    either empties both."""
+
+    def __init__(self, shared, index, max_size):
+        self.shared, self.index, self.max_size = shared, index, max_size
+
+    @property
+    def current_size(self):
+        return int(self.shared.read()[2])
+
+    def get_mean(self):
+        return self.shared.read()[self.index].to(torch.float32).numpy()
+
+    def clear(self):
+        self.shared.words[:3].zero_()
+        self.shared.written()
+
+    def update(self, values):
+        raise RuntimeError("a DeviceMeter is updated by rollout_store, on the device")
+
+
 class _NullObserver:
     """rl_games AlgoObserver interface (config['features']['observer']); the default does nothing."""
 
@@ -157,6 +197,11 @@ class CommonAgent:
         rs = config.get('reward_shaper', {}) or {}
         self._reward_scale, self._reward_shift = float(rs.get('scale_value', 1.0)), float(rs.get('shift_value', 0.0))
         self.algo_observer = (config.get('features', {}) or {}).get('observer', None) or _NullObserver()
+        # opt-in: everything play_steps does behind env_step as ONE rollout_store per step, the done rows reset by the
+        # environment from a device mask - no nonzero, no host round trip in the step (_play_steps_device)
+        self._device_rollout = bool(config.get('device_rollout', False))
+        if self._device_rollout:
+            self._check_device_rollout()
         self.writer = config.get('writer', None) or ScalarLog()
         self.is_tensor_obses = True
         self._load_config_params(config)
@@ -218,11 +263,26 @@ class CommonAgent:
                                        dtype=torch.int64, device=self.ppo_device)       # Philox stream of the rollout's actions
         self.game_rewards = AverageMeter(self.value_size, self.games_to_track)
         self.game_lengths = AverageMeter(1, self.games_to_track)
+        if self._device_rollout:
+            assert hasattr(self.backend, 'rollout_store'), "device_rollout needs a backend with rollout_store"
+            self._meter_words = torch.zeros(4, dtype=torch.float64, device=self.ppo_device)
+            self._meter_host = DeviceMeterWords(self._meter_words)
+            self.game_rewards = DeviceMeter(self._meter_host, 0, self.games_to_track)
+            self.game_lengths = DeviceMeter(self._meter_host, 1, self.games_to_track)
         self.obs = None
         self.init_tensors()
         self.algo_observer.after_init(self)
         if self.world_size > 1:
             self._sync_initial_state()
+
+    def _check_device_rollout(self):
+        """What config['device_rollout'] needs, refused at construction."""
+        env = getattr(self.vec_env, 'env', self.vec_env)
+        assert getattr(env, 'resets_done_on_device', False) or getattr(self.vec_env, 'resets_done_on_device', False), \
+            "device_rollout needs an environment that declares resets_done_on_device = True and provides reset_done(mask)"
+        assert self.num_agents == 1 and self.value_size == 1, "device_rollout: num_agents == 1 and value_size == 1"
+        assert type(self.algo_observer) is _NullObserver or getattr(self.algo_observer, 'accepts_done_ids', False), \
+            "device_rollout: process_infos receives the device id list (e / -1), the observer must declare accepts_done_ids = True"
 
     def _randperm(self, n):
         return torch.randperm(n, device=self.ppo_device, generator=self._gen).to(torch.int32)
@@ -307,6 +367,9 @@ class CommonAgent:
         self.current_rewards = torch.zeros(N, self.value_size, dtype=torch.float32, device=dev)   # rl_games A2CBase.init_tensors
         self.current_lengths = torch.zeros(N, dtype=torch.float32, device=dev)
         self.dones = torch.ones(N, dtype=torch.uint8, device=dev)
+        if self._device_rollout:
+            self._done_ids = torch.full((N,), -1, dtype=torch.int32, device=dev)      # rollout_store's list: e where done, else -1
+            self._no_dones = torch.zeros(N, dtype=torch.uint8, device=dev)
 
     # ------------------------------------------------------------------ mode switches / stats
     def set_eval(self):
@@ -516,6 +579,8 @@ class CommonAgent:
                 if k in self.experience:
                     self.experience[k].copy_(v.to(self.ppo_device))
             return self._play_steps_tail()
+        if self._device_rollout:
+            return self._play_steps_device()
         E = self.experience
         done_indices = []
         if self.obs is None:
@@ -546,6 +611,47 @@ class CommonAgent:
             self.current_rewards = self.current_rewards * not_dones.unsqueeze(1)
             self.current_lengths = self.current_lengths * not_dones
             done_indices = done_indices[:, 0]
+        return self._play_steps_tail()
+
+    def _reset_done(self, done_mask):
+        """env_reset(done_indices) of the device loop: the environment resets the rows whose mask element is set."""
+        return self.obs_to_tensors(self.vec_env.reset_done(done_mask))
+
+    def _rollout_fields(self, n, res_dict, infos):
+        """Per-step experience fields beyond CommonAgent's as (source, destination) rows of rollout_store's table - what
+        _rollout_extras copies on the host path."""
+        return []
+
+    def _play_steps_device(self):
+        """play_steps with config['device_rollout']: per step the done rows' reset from the previous step's done mask, the obses
+        copy (an environment may hand out its own buffer and overwrite it in step), _before_act, _act, env_step, _next_values
+        and ONE rollout_store for the rest - the stores, the shaped reward, the masked next value, the episode accumulators, both
+        meters and the id list of the next reset.  The host never learns which rows are done."""
+        E, be = self.experience, self.backend
+        if self.obs is None:
+            self.obs = self.env_reset()
+        done_mask = self._no_dones                     # the reference's first env_reset([]) resets nothing
+        self._done_ids.fill_(-1)
+        for n in range(self.horizon_length):
+            self.obs = self._reset_done(done_mask)
+            E['obses'][n].copy_(self.obs['obs'])
+            self._rollout_step = n
+            self._before_act()
+            res = self._act()
+            self.obs, rewards, self.dones, infos = self.env_step(res['actions'])
+            next_values = self._next_values()
+            fields = [(res[k], E[k]) for k in ('actions', 'neglogpacs', 'values', 'mus', 'sigmas')]
+            fields.append((self.obs['obs'], E['next_obses']))
+            fields += self._rollout_fields(n, res, infos)
+            be.rollout_store(self.dones, slot=n, fields=fields, rewards=rewards, shift=self._reward_shift,
+                             scale=self._reward_scale, rewards_out=E['rewards'], dones_out=E['dones'],
+                             next_values=next_values, terminate=infos['terminate'].to(self.ppo_device),
+                             next_values_out=E['next_values'], cur_rewards=self.current_rewards,
+                             cur_lengths=self.current_lengths, meter=self._meter_words, max_size=self.games_to_track,
+                             done_ids_out=self._done_ids)
+            self.algo_observer.process_infos(infos, self._done_ids)
+            done_mask = self.dones
+        self._meter_host.written()
         return self._play_steps_tail()
 
     def _experience_kwargs(self):
@@ -1014,6 +1120,10 @@ class AMPAgent(CommonAgent):
         self.experience['amp_obs'][n].copy_(infos['amp_obs'])
         self.experience['rand_action_mask'][n].copy_(res_dict['rand_action_mask'])
 
+    def _rollout_fields(self, n, res_dict, infos):
+        E = self.experience
+        return [(infos['amp_obs'].to(self.ppo_device), E['amp_obs']), (res_dict['rand_action_mask'], E['rand_action_mask'])]
+
     def _record_train_batch_info(self, batch_dict, train_info):
         super()._record_train_batch_info(batch_dict, train_info)
         train_info['disc_rewards'] = batch_dict['disc_rewards']
@@ -1160,6 +1270,7 @@ class ASEAgent(AMPAgent):
         self._enc_reward_w = config['enc_reward_w']
         # opt-in: latent renewals as launches of backend.latent_renew (csrc/latent_renew.hip) instead of the host path below
         self._device_latents = bool(config.get('device_latents', False))
+        assert self._device_latents or not config.get('device_rollout', False), "device_rollout needs device_latents: True (ASE)"
 
     def _build_net_config(self):
         c = super()._build_net_config()
@@ -1199,6 +1310,17 @@ class ASEAgent(AMPAgent):
                 return obs
             self._reset_latents(env_ids)
             self._reset_latent_step_count(env_ids)
+        return obs
+
+    def _reset_done(self, done_mask):
+        """+ env_reset's latent part on the full-length id list of the previous step's store (e where done, else -1: skipped).
+        The stream position moves on iff a row was done, as env_reset's launch moves it iff it has ids - decided on the device."""
+        obs = super()._reset_done(done_mask)
+        rng = self.engine.rng_state
+        self.backend.latent_renew(self._ase_latents, env_ids=self._done_ids, rng_state=rng, advance=False,
+                                  reset_steps=self._latent_reset_steps, steps_add=False, steps_low=int(self._latent_steps_min),
+                                  steps_high=int(self._latent_steps_max))
+        rng[1:2] += (self._done_ids.max() >= 0).to(rng.dtype)
         return obs
 
     def _rand_steps(self, n):
@@ -1244,6 +1366,13 @@ class ASEAgent(AMPAgent):
             self._latents_slot = -1
             return
         self.experience['ase_latents'][n].copy_(self._ase_latents)
+
+    def _rollout_fields(self, n, res_dict, infos):
+        fields = super()._rollout_fields(n, res_dict, infos)
+        if self._latents_slot == n:                   # _update_latents' launch wrote the slot
+            self._latents_slot = -1
+            return fields
+        return fields + [(self._ase_latents, self.experience['ase_latents'])]
 
     def _record_train_batch_info(self, batch_dict, train_info):
         super()._record_train_batch_info(batch_dict, train_info)
@@ -1386,6 +1515,9 @@ class HRLAgent(CommonAgent):
 
     def _rollout_extras(self, n, res_dict, infos):
         self.experience['disc_rewards'][n].copy_(infos['disc_rewards'].view(-1, 1))
+
+    def _rollout_fields(self, n, res_dict, infos):
+        return [(infos['disc_rewards'].to(self.ppo_device).view(-1, 1), self.experience['disc_rewards'])]
 
     def _get_mean_rewards(self):
         return super()._get_mean_rewards() * self._llc_steps

@@ -22,6 +22,8 @@ TASK_OBS_COLS = (5, 2, 3, 15)                                       # columns as
 TASK_RESET_DRAWS = (3, 2, 3, 4)                                     # uniforms per row ase_hip_task_reset takes per kind
 RESET_FRAME, RESET_TABLE, RESET_MOTION = range(3)                   # ASE_RESET_*: the kinds of a row of ase_hip_amp_reset
 RESET_HAS_TABLE, RESET_HAS_MOTION = 1, 2                            # ASE_RESET_HAS_*: the host mask of kinds that may occur
+KIND_U8, KIND_I32, KIND_I64, KIND_F32 = range(4)                    # ASE_KIND_*: the flag vectors of ase_hip_rollout_store
+ROLLOUT_STORE_MAX_FIELDS, ROLLOUT_STORE_ROWS = 16, 8                # ASE_ROLLOUT_STORE_*
 INIT_DEFAULT, INIT_START, INIT_RANDOM, INIT_HYBRID = range(4)       # ASE_INIT_*: the state initialisation of ase_hip_amp_reset_due
 
 # accumulator slots (ASE_ACC_*)
@@ -99,6 +101,8 @@ SIGNATURES = {
                              + [_p, _i] + [_p] * 4 + [_p] * 5 + [_p, _i64, _p, _p, _i64, _i] + [_p] * 4 + [_i, _i, _i, _f, _p, _i, _p],
     "ase_hip_amp_demo_fetch": [_p] * 6 + [_i] + [_p] * 4 + [_i, _p, _p, _i, _p, _i] + [_p] * 4 + [_i, _p, _p] + [_i, _i, _f, _f, _i, _i]
                               + [_p, _i64, _i, _i, _p, _p],
+    "ase_hip_rollout_store": [_p, _i, _p, _f, _f, _p, _i64, _p, _i, _p, _i64, _p, _p, _i, _p, _i64, _p, _p, _p, _i, _p, _i64, _p,
+                              _i, _i, _p, _i, _p],
     "ase_hip_clip_frames": [_p] * 6 + [_i] + [_p] * 4 + [_i, _i, _p, _p, _i] + [_p] * 7,
     "ase_hip_gemm_nt_kernel_id": [_i, _i, _i, _i],
     "ase_hip_gemm_tn_kernel_id": [_i, _i, _i, _i, _i, _i64, _i64, _i],
@@ -122,6 +126,11 @@ SIGNATURES = {
 
 class AseHipError(RuntimeError):
     pass
+
+
+def rollout_store_ws(n_envs):
+    """ASE_ROLLOUT_STORE_WS: doubles of ase_hip_rollout_store's workspace."""
+    return 3 * ((int(n_envs) + ROLLOUT_STORE_ROWS - 1) // ROLLOUT_STORE_ROWS)
 
 
 def load():

@@ -71,6 +71,12 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
                                                       draws (passed in, or the Philox stream {seed, offset}), motion sampler,
                                                       frames and the store into the demo ring in one launch
                                                       (env/tasks/humanoid_amp.py:63-105)
+  rollout_store(dones, slot, n_slots, srcs, dsts, rewards, shift, scale, rewards_out, dones_out, next_values, terminate,
+                next_values_out, cur_rewards, cur_lengths, meter, max_size, done_ids_out, slot_dev=None) -> ()
+                                                      (dsts, the three slotted outputs, the accumulators, the meter and the id
+                                                      list written in place) one environment step into experience slot `slot`:
+                                                      what play_steps does behind env_step, without dones.nonzero
+                                                      (learning/common_agent.py:267-293)
   clip_frames(rotation, root_translation, root_velocity, root_angular_velocity, local_translation, clip_first, clip_num_frames,
               clip_fps, frame_clip, parent_indices, dof_body_ids, dof_offsets) -> (gts, grs, lrs, grvs, gravs, dvs)
                                                       the clip loader: forward kinematics and joint velocities of every frame of
@@ -778,6 +784,35 @@ def amp_demo_fetch(out: torch.Tensor, ring_rows: int, head: int, n: int, num_ste
                               motion_ids=motion_ids, motion_times0=motion_times0, rng_state=rng_state, clip_cdf=clip_cdf,
                               advance=advance, draws_out=None if motion_ids_out is None else (motion_ids_out, motion_times0_out),
                               head_dev=head_dev)
+
+
+@torch.library.custom_op('ase_hip::rollout_store', mutates_args=('dsts', 'rewards_out', 'dones_out', 'next_values_out', 'cur_rewards',
+                                                             'cur_lengths', 'meter', 'done_ids_out'), device_types='cuda')
+def rollout_store(dones: torch.Tensor, slot: int, n_slots: int, srcs: list[torch.Tensor], dsts: list[torch.Tensor],
+                  rewards: torch.Tensor | None, shift: float, scale: float, rewards_out: torch.Tensor | None,
+                  dones_out: torch.Tensor | None, next_values: torch.Tensor | None, terminate: torch.Tensor | None,
+                  next_values_out: torch.Tensor | None, cur_rewards: torch.Tensor | None, cur_lengths: torch.Tensor | None,
+                  meter: torch.Tensor | None, max_size: int, done_ids_out: torch.Tensor | None,
+                  slot_dev: torch.Tensor | None = None) -> None:
+    """One environment step stored into experience slot `slot` (operands: see ase_hip_rollout_store): srcs[i] [n_envs, D_i] is
+    copied to dsts[i][slot] ([n_slots, n_envs, D_i]), the shaped reward, the done flags and the masked next value go to their
+    slotted buffers, the episode accumulators are advanced in place, the two meters (meter f64 [4]) take the done rows and
+    done_ids_out receives e / -1.  Every tensor is passed by position, None where a group is left out."""
+    _check(len(srcs) == len(dsts) and len(srcs) <= L.ROLLOUT_STORE_MAX_FIELDS, 'rollout_store: as many sources as destinations, at most 16')
+    kinds = (torch.uint8, torch.bool, torch.int32, torch.int64, torch.float32)
+    _check(dones.dtype in kinds and (terminate is None or terminate.dtype in kinds),
+           'rollout_store: dones / terminate must be uint8, bool, int32, int64 or float32')
+    _check((cur_rewards is None) == (cur_lengths is None) == (meter is None), 'rollout_store: the accumulators and the meter come together')
+    _backend().rollout_store(dones, slot=slot, n_slots=n_slots, fields=list(zip(srcs, dsts)), rewards=rewards, shift=shift,
+                             scale=scale, rewards_out=rewards_out, dones_out=dones_out, next_values=next_values,
+                             terminate=terminate, next_values_out=next_values_out, cur_rewards=cur_rewards,
+                             cur_lengths=cur_lengths, meter=meter, max_size=max_size, done_ids_out=done_ids_out, slot_dev=slot_dev)
+
+
+@rollout_store.register_fake
+def _(dones, slot, n_slots, srcs, dsts, rewards, shift, scale, rewards_out, dones_out, next_values, terminate, next_values_out,
+      cur_rewards, cur_lengths, meter, max_size, done_ids_out, slot_dev=None):
+    return None
 
 
 @torch.library.custom_op('ase_hip::clip_frames', mutates_args=(), device_types='cuda')

@@ -197,6 +197,17 @@ class SyntheticVecEnv:
             self.progress_buf[ids.to(self.device)] = 0
         return self._obs.clone()          # a bare tensor, as RLGPUEnv.reset without global observations (ase/run.py:115-133)
 
+    resets_done_on_device = True      # reset_done(mask): what the agents' device_rollout asks of an environment
+
+    def reset_done(self, mask):
+        """reset() of the rows whose mask element is set, without the host learning which: a full-length draw, selected by
+        torch.where.  (Another use of the generator than reset(env_ids): the two are different streams.)"""
+        m = torch.as_tensor(mask).to(self.device).view(-1) != 0
+        fresh = self.obs_fs.draw(self.num_envs, self.gen).to(self.device)
+        self._obs = torch.where(m.unsqueeze(1), fresh, self._obs)
+        self.progress_buf.copy_(torch.where(m, torch.zeros_like(self.progress_buf), self.progress_buf))
+        return self._obs.clone()
+
     def step(self, actions):
         n = self.num_envs
         self.last_actions = actions

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch and ase_hip_gemm_tn_kernel_id were added WITHOUT a new version
+/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id and ase_hip_rollout_store were added WITHOUT a new version
  *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
  *  load time) */
 #define ASE_HIP_ABI_VERSION 9
@@ -505,6 +505,63 @@ int ase_hip_sample_actions(const float* mu, int64_t ld_mu, const float* logstd, 
 int ase_hip_sample_latents(float* z, int rows, int dim, uint64_t* rng_state, int64_t row_offset, int advance,
                            void* z2 /* nullable: a second copy [rows, ld_z2] in z2_dtype (the GEMM input buffer) */,
                            int64_t ld_z2, int z2_dtype, void* stream);
+
+/* One environment step stored into experience slot n (an addition to ABI 9, nothing else changed): everything
+ * play_steps does behind env_step, over n_envs rows, without dones.nonzero() and without a host round trip.  n = slot, or -
+ * slot_dev non-NULL (DEVICE int32 [1]) - the word read when the launch runs, IN PLACE of slot (ase_hip_amp_demo_fetch's
+ * head_dev idea: a recorded launch follows a slot kept on the device); a word outside [0, n_slots) makes the whole call write
+ * nothing: no experience, no accumulators, no meter, no ids.  Every part but dones is optional, each group given whole or
+ * left out whole (NULL):
+ *   row copies   fields: DEVICE int64[n_fields][6] = {src, ld_src, D, dst_base, ld_dst, slot_stride}, all f32, pitches in
+ *                elements (ase_hip_gather_multi's table with a slot stride in place of the dtype), n_fields 0 .. 16, D >= 1,
+ *                ld >= D: dst_base[n * slot_stride + e * ld_dst + j] = src[e * ld_src + j] for j < D, bitwise.  Columns
+ *                [D, ld_dst) and other slots are not touched.  A field moves 16 bytes per lane when D % 4 == 0, ld_src % 4
+ *                == 0, ld_dst % 4 == 0, slot_stride % 4 == 0 and src and dst_base are 16-byte aligned, 4 bytes otherwise -
+ *                chosen per field inside the kernel.  The table's content cannot be checked on the host.
+ *   rewards      rewards_out[n * rewards_ss + e] = (rewards[e] + shift) * scale, two f32 operations each rounded on its own
+ *                (rl_games DefaultRewardsShaper).  rewards f32 [n_envs] is also what the accumulators add: it is required by
+ *                either, and refused when neither rewards_out nor the accumulators are given.
+ *   dones_out    dones_out[n * dones_ss + e] = (uint8)(dones[e] != 0).  dones [n_envs] has the type dones_kind names:
+ *                ASE_KIND_U8, ASE_KIND_I32, ASE_KIND_I64 (Isaac Gym's reset_buf) or ASE_KIND_F32 (HRLAgent.env_step); its
+ *                values are expected to be 0 or 1, as in the reference.  d = (float)dones[e] below.
+ *   next values  next_values_out[n * next_values_ss + e] = next_values[e] * (1.0f - (float)terminate[e]); terminate
+ *                [n_envs] of terminate_kind (the same four codes).
+ *   accumulators cur_rewards, cur_lengths f32 [n_envs], in place: r = cur_rewards[e] + rewards[e] (the RAW reward),
+ *                l = cur_lengths[e] + 1.0f; a row with dones[e] != 0 enters this call's meter sums with (r, l); then
+ *                cur_rewards[e] = r * (1.0f - d), cur_lengths[e] = l * (1.0f - d).
+ *                meter: DEVICE f64[4] = {reward_mean, length_mean, current_size, episodes_seen}, max_size = games_to_track.
+ *                With k done rows in this call: k == 0 leaves the four words bitwise unchanged; otherwise, in f64, for each
+ *                of the two means new = sum / k, size = min(k, max_size), old = min(max_size - size, current_size),
+ *                mean = (mean * old + new * size) / (old + size); then current_size = old + size, episodes_seen += k - rl_games
+ *                AverageMeter.update word for word.
+ *                workspace: DEVICE f64[workspace_doubles], workspace_doubles >= ASE_ROLLOUT_STORE_WS(n_envs), private to
+ *                the call until it completes; its content on entry does not matter.  NO floating-point atomics and no
+ *                ticket: every block of ASE_ROLLOUT_STORE_ROWS rows stores its partial {sum r, sum l, k} (rows in order) to
+ *                its own three words, and a SECOND one-wave kernel of the same call (ase_hip_adv_norm's and
+ *                ase_hip_ppo_head's precedent: a kernel boundary instead of a fence) folds them - lane i the blocks i,
+ *                i + 64, ... in order, then a butterfly over the lanes - and updates the meter.  Only the order of the f64
+ *                sum differs from a sequential sum; two calls on equal inputs give bitwise-equal meters.
+ *   id list      done_ids_out int32 [n_envs]: done_ids_out[e] = e for a done row, -1 otherwise, every element written - the
+ *                list ase_hip_task_reset, ase_hip_latent_renew and a plan of ase_hip_amp_reset accept (ids outside
+ *                [0, n_envs) are skipped), so the next step's resets need no nonzero.
+ * The three outputs with a slot stride need rewards_ss / dones_ss / next_values_ss >= n_envs.
+ * Refused, on the host, before any launch: NULL dones; a partial group (accumulators; next values; rewards_out without
+ * rewards; rewards without a consumer; accumulators without rewards); n_envs <= 0; n_fields outside [0, 16] or fields NULL with
+ * n_fields > 0; a kind code outside the four; a slot stride below n_envs; max_size <= 0 with a meter; a workspace below
+ * ASE_ROLLOUT_STORE_WS(n_envs); n_slots <= 0 or slot outside [0, n_slots) (checked also when slot_dev is given).
+ * Replaces: learning/common_agent.py:267-293 (the stores behind env_step, rewards_shaper, terminated / next_vals,
+ *   current_rewards / current_lengths, dones.nonzero, game_rewards.update / game_lengths.update, not_dones), with
+ *   learning/amp_agent.py:93-122, learning/ase_agent.py:66-100 and learning/hrl_agent.py:124-151 for the extra fields. */
+enum { ASE_KIND_U8 = 0, ASE_KIND_I32 = 1, ASE_KIND_I64 = 2, ASE_KIND_F32 = 3 };
+#define ASE_ROLLOUT_STORE_MAX_FIELDS 16
+#define ASE_ROLLOUT_STORE_ROWS 8
+#define ASE_ROLLOUT_STORE_WS(n_envs) (3 * (((n_envs) + ASE_ROLLOUT_STORE_ROWS - 1) / ASE_ROLLOUT_STORE_ROWS))
+int ase_hip_rollout_store(const int64_t* fields, int n_fields, const float* rewards, float shift, float scale,
+                          float* rewards_out, int64_t rewards_ss, const void* dones, int dones_kind, uint8_t* dones_out,
+                          int64_t dones_ss, const float* next_values, const void* terminate, int terminate_kind,
+                          float* next_values_out, int64_t next_values_ss, float* cur_rewards, float* cur_lengths,
+                          double* meter, int max_size, double* workspace, int64_t workspace_doubles, int32_t* done_ids_out,
+                          int n_envs, int slot, const int32_t* slot_dev, int n_slots, void* stream);
 
 /* The whole optimizer step of every dense layer in ONE launch: weight-only gradient terms (g += c * w: discriminator
  * weight decay / logit regulariser / encoder weight decay), their reported sums of squares (pre-update weights, into

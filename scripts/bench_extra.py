@@ -16,6 +16,9 @@ rollout-time inference path.  One JSON line per measurement on stdout.
           environments under a launch program, next to the same functions as plain torch ops on the device (reported, not gated)
   amp-reset: the fused HumanoidAMP reset launch (motion-state rows, 10 history slots) for 64 and 4096 of 4096 environments under a
           launch program, next to the same result composed from the sampler and the frame builder (reported, not gated)
+  rollout-store: what play_steps does behind env_step for one step of config 2 (4096 envs, obs 253, actions 31, amp 1400, latents
+          64, dones at 1/300): the host block (some thirty torch launches and dones.nonzero's round trip) next to the one
+          rollout_store call, eager and replayed from a launch program (reported, not gated)
   infer : get_action_values (eval-mode normalisation + actor + critic forward + sample) on 4096 observations
 """
 import argparse
@@ -249,6 +252,93 @@ def amp_reset_case():
                           'device': torch.cuda.get_device_name(0)}), flush=True)
 
 
+def rollout_store_case():
+    """One environment step's stores of config 2, three ways on the same tensors.  Calls are issued back to back and timed
+    between two events - the larger of host and GPU time; the host block waits for the device in every call (nonzero).  Seven
+    repeats of 100 calls each: median and spread."""
+    from ase_amd.backend import HipBackend
+    from ase_amd.learning.agents import AverageMeter
+    be = HipBackend('cuda:0')
+    g = torch.Generator().manual_seed(0)
+    N, H, OBS, ACT, AMP, Z = 4096, 32, 253, 31, 1400, 64
+    dev = 'cuda:0'
+    rnd = lambda *shape: torch.randn(*shape, generator=g).to(dev)
+    E = {'actions': (ACT,), 'neglogpacs': (), 'values': (1,), 'mus': (ACT,), 'sigmas': (ACT,), 'next_obses': (OBS,), 'rewards': (1,),
+         'next_values': (1,), 'amp_obs': (AMP,), 'rand_action_mask': (), 'ase_latents': (Z,)}
+    E = {k: torch.zeros(H, N, *shp, device=dev) for k, shp in E.items()}
+    E['dones'] = torch.zeros(H, N, dtype=torch.uint8, device=dev)
+    res = {'actions': rnd(N, ACT), 'neglogpacs': rnd(N), 'values': rnd(N, 1), 'mus': rnd(N, ACT), 'sigmas': rnd(N, ACT),
+           'rand_action_mask': torch.ones(N, device=dev)}
+    obs, amp_obs, latents, next_values = rnd(N, OBS), rnd(N, AMP), rnd(N, Z), rnd(N, 1)
+    rewards = torch.ones(N, 1, device=dev)
+    dones_b = torch.rand(N, generator=g) < 1.0 / 300
+    dones = dones_b.to(torch.uint8).to(dev)
+    terminate = (dones_b & (torch.rand(N, generator=g) < 0.5)).to(dev)
+    shift, scale, n = 0.0, 1.0, 5
+
+    class Host:          # CommonAgent.play_steps' statements behind env_step, with the ASE agent's _rollout_extras
+        current_rewards = torch.zeros(N, 1, device=dev)
+        current_lengths = torch.zeros(N, device=dev)
+        game_rewards, game_lengths = AverageMeter(1, 100), AverageMeter(1, 100)
+
+    def host_block(a=Host):
+        for k in ('actions', 'neglogpacs', 'values', 'mus', 'sigmas'):
+            E[k][n].copy_(res[k].view(E[k][n].shape))
+        E['rewards'][n].copy_((rewards + shift) * scale)
+        E['next_obses'][n].copy_(obs)
+        E['dones'][n].copy_(dones)
+        E['amp_obs'][n].copy_(amp_obs)
+        E['rand_action_mask'][n].copy_(res['rand_action_mask'])
+        E['ase_latents'][n].copy_(latents)
+        terminated = terminate.float().unsqueeze(-1)
+        E['next_values'][n].copy_(next_values * (1.0 - terminated))
+        a.current_rewards += rewards
+        a.current_lengths += 1
+        all_done_indices = dones.nonzero(as_tuple=False)
+        done_indices = all_done_indices[::1]
+        a.game_rewards.update(a.current_rewards[done_indices])
+        a.game_lengths.update(a.current_lengths[done_indices])
+        not_dones = 1.0 - dones.float()
+        a.current_rewards = a.current_rewards * not_dones.unsqueeze(1)
+        a.current_lengths = a.current_lengths * not_dones
+        done_indices = done_indices[:, 0]
+
+    cur_r, cur_l = torch.zeros(N, 1, device=dev), torch.zeros(N, device=dev)
+    meter, ids = torch.zeros(4, dtype=torch.float64, device=dev), torch.zeros(N, dtype=torch.int32, device=dev)
+    fields = [(res[k], E[k]) for k in ('actions', 'neglogpacs', 'values', 'mus', 'sigmas')] + \
+        [(obs, E['next_obses']), (amp_obs, E['amp_obs']), (res['rand_action_mask'], E['rand_action_mask']), (latents, E['ase_latents'])]
+
+    def one_call():
+        be.rollout_store(dones, slot=n, fields=fields, rewards=rewards, shift=shift, scale=scale, rewards_out=E['rewards'],
+                         dones_out=E['dones'], next_values=next_values, terminate=terminate, next_values_out=E['next_values'],
+                         cur_rewards=cur_r, cur_lengths=cur_l, meter=meter, max_size=100, done_ids_out=ids)
+    prog = be.prog_create()
+    be.prog_begin(prog)
+    one_call()
+    be.prog_end(prog)
+
+    def timeit(fn, calls=100):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(calls):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / calls * 1e3
+    byt = sum(2 * 4 * N * int(s.shape[1] if s.dim() > 1 else 1) for s, _ in fields) + N * (4 * 4 + 4 * 4 + 3)
+    for name, fn in (('rollout step stores, host block (play_steps behind env_step, with dones.nonzero)', host_block),
+                     ('rollout step stores, one rollout_store call', one_call),
+                     ('rollout step stores, one rollout_store call replayed from a launch program', lambda: be.prog_launch(prog))):
+        reps = sorted(timeit(fn) for _ in range(7))
+        print(json.dumps({'measurement': name, 'envs': N, 'done_rows': int(dones_b.sum()), 'bytes': byt,
+                          'us_per_call_median': round(reps[3], 1), 'us_per_call_min': round(reps[0], 1),
+                          'us_per_call_max': round(reps[-1], 1), 'repeats': 7, 'calls_per_repeat': 100}), flush=True)
+    be.prog_destroy(prog)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--updates', type=int, default=4)
@@ -343,6 +433,8 @@ def main():
         env_tensors_case()
     if not args.only or 'amp-reset' in args.only.split(','):
         amp_reset_case()
+    if not args.only or 'rollout-store' in args.only.split(','):
+        rollout_store_case()
     if not args.only or 'ampobs' in args.only.split(','):
         # N2: observation production for 4096 envs (one frame + history push) and 5120 demo samples (512 x 10 steps)
         from ase_amd.backend import HipBackend
