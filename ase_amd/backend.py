@@ -678,6 +678,61 @@ class HipBackend:
             f"{who}: contiguous [n_envs] of {dtype or 'uint8 / bool / int32 / int64 / float32'}"
         return t
 
+    # ------------------------------------------------------------------ the HRL inner loop's glue (N13)
+    def _hrl_rows(self, t, n, cols, dtype, who):
+        """[n, >= cols] rows of `dtype` with unit column stride on this GPU: the kernels dereference raw addresses at t's pitch."""
+        assert self._here(t), f"{who}: a tensor on {self.device}, not {t.device}"
+        assert t.dim() == 2 and t.shape[0] == n and t.shape[1] >= cols and t.stride(1) == 1 and t.stride(0) >= cols and \
+            (t.dtype == dtype if dtype is not None else t.dtype in (torch.float32, torch.bfloat16, torch.float16)), \
+            f"{who}: [{n}, >= {cols}] rows of {dtype or 'f32 / bf16 / f16'}, unit column stride"
+        return t
+
+    def hrl_latent(self, actions, z=None, z2=None, dim=None):
+        """z = normalize(clamp(actions, -1, 1)) per row (ase_hip_hrl_latent): actions f32 [n, >= dim]; z f32 [n, >= dim] and / or
+        z2 [n, >= dim] in f32 / bf16 / f16 (the style chain's input buffer: columns [0, dim) only), each read or written at its
+        own pitch.  dim defaults to actions' width.  Recordable in a launch program."""
+        n = actions.shape[0]
+        dim = actions.shape[1] if dim is None else int(dim)
+        f32 = torch.float32
+        actions = self._hrl_rows(actions, n, dim, f32, 'actions')
+        z = None if z is None else self._hrl_rows(z, n, dim, f32, 'z')
+        z2 = None if z2 is None else self._hrl_rows(z2, n, dim, None, 'z2')
+        assert z is not None or z2 is not None, "hrl_latent: z or z2"
+        L.check(self.lib.ase_hip_hrl_latent(_ptr(actions), _ld(actions), _ptr(z), _ld(z), _ptr(z2), _ld(z2),
+                                            0 if z2 is None else _code(z2.dtype), n, dim, self._stream()), "hrl_latent")
+
+    def hrl_llc_action(self, mu, low, high, out, act, clip=True):
+        """The padded head output mu f32 [n, >= act] -> out f32 [n, >= act]: clamp(mu, -1, 1) * ((high - low) / 2) +
+        ((high + low) / 2) with clip, a strided copy without (ase_hip_hrl_llc_action).  low / high f32 [act], contiguous."""
+        n, act, f32 = mu.shape[0], int(act), torch.float32
+        mu, out = self._hrl_rows(mu, n, act, f32, 'mu'), self._hrl_rows(out, n, act, f32, 'out')
+        for t, who in ((low, 'low'), (high, 'high')):
+            assert (t is None and not clip) or (self._here(t) and t.dtype == f32 and t.numel() == act and t.is_contiguous()), \
+                f"{who}: contiguous f32 [{act}] on {self.device}"
+        L.check(self.lib.ase_hip_hrl_llc_action(_ptr(mu), _ld(mu), _ptr(low), _ptr(high), _ptr(out), _ld(out), n, act, int(bool(clip)),
+                                                self._stream()), "hrl_llc_action")
+
+    def hrl_accum(self, rewards, dones, acc, first, last, llc_steps, terminate=None, logit=None, disc_scale=1.0, rewards_out=None,
+                  disc_out=None, dones_out=None, terminate_out=None):
+        """One inner step folded into acc f32 [4, n] (task-reward sum, discriminator-reward sum, done count, terminate count) and,
+        with last, the finals (ase_hip_hrl_accum): rewards f32 [n]; dones / terminate [n] uint8 / bool / int32 / int64 / f32;
+        logit f32 [n, ld] whose column 0 is the discriminator logit, read at its pitch; the four outputs f32 with n elements.
+        Every tensor lives on the backend's device.  Recordable in a launch program."""
+        n, f32 = dones.numel(), torch.float32
+        vec = lambda t, dt, who: None if t is None else self._rs_vec(t, n, dt, who)
+        rewards, dones, terminate = vec(rewards, f32, 'rewards'), vec(dones, None, 'dones'), vec(terminate, None, 'terminate')
+        outs = [vec(t, f32, who) for t, who in ((rewards_out, 'rewards_out'), (disc_out, 'disc_out'), (dones_out, 'dones_out'),
+                                                 (terminate_out, 'terminate_out'))]
+        assert self._here(acc) and acc.dtype == f32 and acc.dim() == 2 and acc.shape == (4, n) and acc.stride(1) == 1 and \
+            acc.stride(0) >= n, f"acc: f32 [4, {n}] rows on {self.device}"
+        if logit is not None:
+            assert self._here(logit) and logit.dtype == f32 and logit.dim() == 2 and logit.shape[0] == n and logit.stride(0) >= 1, \
+                f"logit: f32 [{n}, ld] on {self.device}"
+        kind = lambda t: 0 if t is None else self._KINDS[t.dtype]
+        L.check(self.lib.ase_hip_hrl_accum(_ptr(rewards), _ptr(dones), kind(dones), _ptr(terminate), kind(terminate), _ptr(logit),
+                                           _ld(logit), float(disc_scale), _ptr(acc), _ld(acc), int(bool(first)), int(bool(last)),
+                                           int(llc_steps), *[_ptr(t) for t in outs], n, self._stream()), "hrl_accum")
+
     # ------------------------------------------------------------------ normaliser / gather
     def rms_moments(self, src, D, idx, remap, M, state, sums):
         L.check(self.lib.ase_hip_rms_moments(_ptr(src), _ld(src), D, _ptr(idx), remap[0], remap[1], M, _ptr(state),

@@ -81,6 +81,24 @@ template <> __device__ __forceinline__ f16_t from_f32_plain<f16_t>(float x) { re
 __device__ __forceinline__ float floor_nan(float x, float lo) { return x < lo ? lo : x; }
 __device__ __forceinline__ float ceil_nan(float x, float hi) { return x > hi ? hi : x; }
 
+// the AMP style reward of one discriminator logit: -log(max(1 - sigmoid(l), 1e-4)) * scale (learning/amp_agent.py:570-577),
+// every f32 operation rounded on its own - ase_hip_disc_reward and ase_hip_hrl_accum call this one function
+__device__ __forceinline__ float disc_reward_of(float l, float scale) {
+    const float prob = 1.f / (1.f + expf(-l));
+    return -logf(floor_nan(1.f - prob, 0.0001f)) * scale;
+}
+
+// a flag vector of one of the four kinds (ASE_KIND_*): its value as a float and whether it is set
+__device__ __forceinline__ float flag_value(const void* p, int kind, int e, bool& set) {
+    switch (kind) {
+        case ASE_KIND_U8: { const uint8_t v = ((const uint8_t*)p)[e]; set = v != 0; return (float)v; }
+        case ASE_KIND_I32: { const int32_t v = ((const int32_t*)p)[e]; set = v != 0; return (float)v; }
+        case ASE_KIND_I64: { const int64_t v = ((const int64_t*)p)[e]; set = v != 0; return (float)v; }
+        default: { const float v = ((const float*)p)[e]; set = v != 0.f; return v; }
+    }
+}
+inline bool kind_ok(int kind) { return kind == ASE_KIND_U8 || kind == ASE_KIND_I32 || kind == ASE_KIND_I64 || kind == ASE_KIND_F32; }
+
 // ---- the two 16-bit storage types share every kernel: vector types and the matrix instruction by type -----------
 template <typename T> struct V16;
 template <> struct V16<bf16_t> { typedef bf16x8 x8; typedef bf16x4 x4; };

@@ -6,9 +6,7 @@ namespace {
 __global__ __launch_bounds__(256) void disc_reward_kernel(const float* __restrict__ logit, int64_t ld_l,
                                                           float* __restrict__ r, int64_t n, float scale) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float l = logit[i * ld_l];
-        const float prob = 1.f / (1.f + expf(-l));
-        r[i] = -logf(floor_keep_nan(1.f - prob, 0.0001f)) * scale;
+        r[i] = disc_reward_of(logit[i * ld_l], scale);
     }
 }
 

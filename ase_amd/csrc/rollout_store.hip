@@ -33,16 +33,6 @@ struct RolloutStoreArgs {
     int n_fields, dones_kind, terminate_kind, max_size, n_envs, slot, n_slots;
 };
 
-// a flag vector of one of the four kinds: its value as a float and whether it is set
-__device__ __forceinline__ float flag_value(const void* p, int kind, int e, bool& set) {
-    switch (kind) {
-        case ASE_KIND_U8: { const uint8_t v = ((const uint8_t*)p)[e]; set = v != 0; return (float)v; }
-        case ASE_KIND_I32: { const int32_t v = ((const int32_t*)p)[e]; set = v != 0; return (float)v; }
-        case ASE_KIND_I64: { const int64_t v = ((const int64_t*)p)[e]; set = v != 0; return (float)v; }
-        default: { const float v = ((const float*)p)[e]; set = v != 0.f; return v; }
-    }
-}
-
 // the slot a launch writes: the device word when there is one (read when the launch runs), -1 when it names no slot
 __device__ __forceinline__ int store_slot(const int32_t* slot_dev, int slot, int n_slots) {
     if (!slot_dev) return slot;
@@ -145,8 +135,6 @@ __global__ __launch_bounds__(64) void rollout_meter_kernel(const double* __restr
     meter[2] = size_sum;
     meter[3] += k;
 }
-
-inline bool kind_ok(int kind) { return kind == ASE_KIND_U8 || kind == ASE_KIND_I32 || kind == ASE_KIND_I64 || kind == ASE_KIND_F32; }
 
 }  // namespace
 

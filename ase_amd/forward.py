@@ -74,6 +74,7 @@ class ForwardEngine:
         # beside mu in one head group: mu columns [0, act), log-std columns [64, 64 + act))
         self.sigma_mode = getattr(net, 'sigma_mode', 'frozen')
         self._scratch = {}
+        self._frozen = {}            # eval statistics kept while the engine is frozen: frozen_stats / drop_frozen_stats
         self._refresh_desc = None
         self._build_layers()
         self._bind_params()
@@ -240,6 +241,41 @@ class ForwardEngine:
         self.be.rms_finalize(state, D, None, 0, 0, mean, std)
         return mean[0], std[0]
 
+    def frozen_stats(self, which):
+        """Eval mean / std of the 'obs' or 'amp' normaliser, computed ONCE and kept while the engine is frozen (a low-level
+        controller's statistics never change): the per-call rms_finalize of _eval_stats, hoisted.  Whoever writes the running
+        statistics - set_stats_weights, restore, set_train - calls drop_frozen_stats.  Without input normalisation: 0 / 1."""
+        hit = self._frozen.get(which)
+        if hit is None:
+            state, D, key = ((self.obs_state, self.obs, 'normalize_input') if which == 'obs' else
+                             (self.amp_state, self.amp, 'normalize_amp_input'))
+            mean = torch.zeros(1, D, dtype=torch.float32, device=self.dev)
+            std = torch.ones(1, D, dtype=torch.float32, device=self.dev)
+            if self.cfg.get(key, True):
+                self.be.rms_finalize(state, D, None, 0, 0, mean, std)
+            hit = self._frozen[which] = (mean[0], std[0])
+        return hit
+
+    def drop_frozen_stats(self):
+        self._frozen.clear()
+
+    def style_input(self, n):
+        """The style chain's input buffer [n, P(z)] in the compute dtype: what hrl_latent's z2 writes for policy_mu_frozen."""
+        return self._scr('Zs', n, P(self.z))
+
+    def policy_mu_frozen(self, obs):
+        """The mu-only pass of a frozen ASE controller (learning/hrl_agent.py:231-237): obs is a [n, >= obs] VIEW read at its own
+        pitch (no copy), normalised with frozen_stats into the actor input only; the style input is taken as already written
+        (style_input); then the style chain, the actor chain and the mu head, one launch per dense layer.  Returns the padded
+        head output f32 [n, P(act)], persistent scratch.  No critic input, no gather, no rms_finalize."""
+        assert self.kind == 'ase' and self.style, "policy_mu_frozen: an ASE controller"
+        n, a0 = obs.shape[0], self.actor[0]
+        Xa = self._scr('Xa', n, a0.k_pad)
+        mean, std = self.frozen_stats('obs')
+        self.be.rms_normalize(obs, self.obs, None, (0, 0), n, mean, std, [Xa])
+        self._fwd_scr('Hs', self.style[:-1], self.style[-1], self.style_input(n), n, Xa[:, a0.split_dst:])
+        return self._fwd_scr('Ha', self.actor, self.mu_head, Xa, n, 'MU')
+
     def _policy_nets(self, obs, z, normalize, want_mu, want_value):
         """Eval-mode observation normalisation + actor / critic forward on raw observations [n, obs].  Returns the padded
         head outputs (MU f32 [n, P(act)] before any tanh, V f32 [n, 64]); every buffer is persistent scratch."""
@@ -321,20 +357,24 @@ class ForwardEngine:
             res['rand_action_mask'] = o['rand_action_mask'].view(-1)
         return res
 
-    def amp_heads(self, amp_obs, normalize=True):
+    def amp_heads(self, amp_obs, normalize=True, frozen=False, want_enc=True):
         """Eval-mode discriminator logits [n,1] (+ un-normalised encoder output [n,z]) on raw amp obs
-        (learning/amp_agent.py:547-549, learning/ase_agent.py:480-482)."""
+        (learning/amp_agent.py:547-549, learning/ase_agent.py:480-482).  frozen: the statistics of frozen_stats, no rms_finalize.
+        want_enc False: a separate encoder chain is not run (the HRL inner loop reads the logit alone)."""
         be, n = self.be, amp_obs.shape[0]
         f32 = torch.float32
         X = self._scr('Xd', n, self.disc[0].k_pad)
-        if normalize and self.cfg.get('normalize_amp_input', True):
+        if frozen:
+            assert normalize, "amp_heads: frozen statistics are the normalised pass"
+            mean, std = self.frozen_stats('amp')
+        elif normalize and self.cfg.get('normalize_amp_input', True):
             mean, std = self._eval_stats(self.amp_state, self.amp, 'amp')
         else:
             mean, std = self._scr('one_am', 1, self.amp, f32)[0].zero_(), self._scr('one_as', 1, self.amp, f32)[0].fill_(1.0)
         be.rms_normalize(amp_obs, self.amp, None, (0, 0), n, mean, std, [X])
         HD = self._fwd_scr('Hd', self.disc, self.disc_head, X, n, 'HD')
         enc = None
-        if self.has_enc:
+        if self.has_enc and want_enc:
             if self.enc_sep:
                 enc = self._fwd_scr('He', self.enc_chain, self.enc_head, X, n, 'E')
             else:

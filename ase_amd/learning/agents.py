@@ -377,6 +377,7 @@ class CommonAgent:
 
     def set_train(self):
         self._train_mode = True
+        self.engine.drop_frozen_stats()
 
     @staticmethod
     def _rms_to_state_dict(vec):
@@ -399,6 +400,7 @@ class CommonAgent:
         return state
 
     def set_stats_weights(self, weights):
+        self.engine.drop_frozen_stats()
         if self.normalize_input:
             self._rms_from_state_dict(self.engine.obs_state, weights['running_mean_std'])
         if self.normalize_value:
@@ -481,6 +483,7 @@ class CommonAgent:
 
     def restore(self, fn):
         self.set_full_state_weights(torch.load(fn, map_location=self.ppo_device, weights_only=False))
+        self.engine.drop_frozen_stats()
 
     def update_epoch(self):
         self.epoch_num += 1
@@ -1429,6 +1432,12 @@ class HRLAgent(CommonAgent):
         llc_checkpoint = config['llc_checkpoint']
         assert llc_checkpoint != ""                                           # learning/hrl_agent.py:40
         self._build_llc(self._llc_params, llc_checkpoint)
+        # opt-in: the glue of the inner loop as three launches - hrl_latent once per high-level step, hrl_llc_action and
+        # hrl_accum once per inner step - around a mu-only LLC pass with frozen statistics (_env_step_device)
+        self._device_llc_step = bool(config.get('device_llc_step', False))
+        if self._device_llc_step:
+            self._check_device_llc_step()
+            self._init_llc_step_buffers()
 
     def _load_config_params(self, config):
         super()._load_config_params(config)
@@ -1491,7 +1500,59 @@ class HRLAgent(CommonAgent):
     def preprocess_actions(self, actions):
         return torch.clamp(actions, -1.0, 1.0)                                # hrl_agent.py:90-94
 
+    def _check_device_llc_step(self):
+        """What config['device_llc_step'] needs, refused at construction."""
+        llc = self._llc_agent
+        assert not (llc.engine.mu_tanh or getattr(llc.model.a2c_network, 'mu_tanh', False)), \
+            "device_llc_step: an LLC with mu_tanh is not supported (hrl_llc_action has no tanh)"
+        assert 1 <= self._latent_dim <= 128, f"device_llc_step: latent_dim {self._latent_dim} outside [1, 128]"
+        assert llc.actions_low.numel() <= 128, f"device_llc_step: environment action width {llc.actions_low.numel()} above 128"
+        env = getattr(self.vec_env, 'env', self.vec_env)
+        assert not (getattr(env, 'returns_numpy', False) or getattr(self.vec_env, 'returns_numpy', False)), \
+            "device_llc_step takes tensors only: the environment returns numpy"
+        assert all(hasattr(self.backend, k) for k in ('hrl_latent', 'hrl_llc_action', 'hrl_accum')), \
+            "device_llc_step needs a backend with hrl_latent / hrl_llc_action / hrl_accum"
+
+    def _init_llc_step_buffers(self):
+        N, dev, f32 = self.num_actors * self.num_agents, self.ppo_device, torch.float32
+        self._llc_acc = torch.zeros(4, N, dtype=f32, device=dev)          # task-reward sum, disc-reward sum, done / terminate counts
+        out = self._llc_out = torch.zeros(4, N, dtype=f32, device=dev)    # the finals env_step returns, overwritten by the next step
+        self._llc_finals = (out[0].view(N, 1) if self.value_size == 1 else out[0], out[1].view(N, 1), out[2], out[3])
+        self._llc_actions = torch.zeros(N, self._llc_agent.actions_low.numel(), dtype=f32, device=dev)
+        for which in ('obs', 'amp'):              # the LLC's eval statistics, once: no rms_finalize inside the loop
+            self._llc_agent.engine.frozen_stats(which)
+
+    @staticmethod
+    def _llc_tensor(t, dev, who):
+        assert torch.is_tensor(t), f"device_llc_step takes tensors only: the environment returned {type(t).__name__} for {who}"
+        return t.to(dev)
+
+    def _env_step_device(self, actions):
+        """env_step with config['device_llc_step'] (hrl_agent.py:45-82,231-240): z once, then per inner step the mu-only LLC pass,
+        hrl_llc_action, vec_env.step, the discriminator forward and hrl_accum on the padded logit column."""
+        be, llc, dev, T = self.backend, self._llc_agent, self.ppo_device, self._llc_steps
+        e = llc.engine
+        obs, n = self.obs['obs'], actions.shape[0]
+        be.hrl_latent(actions, z2=e.style_input(n), dim=self._latent_dim)
+        rewards, disc_rewards, dones, terminate = self._llc_finals
+        for t in range(T):
+            MU = e.policy_mu_frozen(self._extract_llc_obs(obs))
+            be.hrl_llc_action(MU, llc.actions_low, llc.actions_high, self._llc_actions, e.act, clip=llc.clip_actions)
+            obs, curr_rewards, curr_dones, infos = self.vec_env.step(self._llc_actions)
+            obs = self._llc_tensor(obs['obs'] if isinstance(obs, dict) else obs, dev, 'obs')
+            amp_obs = self._llc_tensor(infos['amp_obs'], dev, 'amp_obs')
+            HD, _ = e.amp_heads(amp_obs.view(-1, amp_obs.shape[-1]), frozen=True, want_enc=False)
+            be.hrl_accum(self._llc_tensor(curr_rewards, dev, 'rewards').view(-1), self._llc_tensor(curr_dones, dev, 'dones'),
+                         self._llc_acc, t == 0, t == T - 1, T, terminate=self._llc_tensor(infos['terminate'], dev, 'terminate'),
+                         logit=HD, disc_scale=llc._disc_reward_scale, rewards_out=rewards, disc_out=disc_rewards,
+                         dones_out=dones, terminate_out=terminate)
+        infos['terminate'] = terminate
+        infos['disc_rewards'] = disc_rewards
+        return self.obs_to_tensors(obs), rewards, dones, infos
+
     def env_step(self, actions):
+        if self._device_llc_step:
+            return self._env_step_device(actions)
         actions = self.preprocess_actions(actions)
         obs = self.obs['obs']
         rewards = disc_rewards = done_count = terminate_count = 0.0

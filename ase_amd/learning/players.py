@@ -117,6 +117,7 @@ class CommonPlayer:
         if self.config.get('normalize_value', False) and 'reward_mean_std' in ck:
             self._set_rms(self.engine.val_state, ck['reward_mean_std'])
         self.engine.refresh_shadows()
+        self.engine.drop_frozen_stats()
         return ck
 
     # ------------------------------------------------------------------ acting
@@ -224,6 +225,7 @@ class AMPPlayerContinuous(CommonPlayer):
         ck = super().restore(fn)
         if self._normalize_amp_input:
             self._set_rms(self.engine.amp_state, ck['amp_input_mean_std'])
+        self.engine.drop_frozen_stats()
         return ck
 
     def _build_net_config(self):
@@ -355,6 +357,15 @@ class HRLPlayer(CommonPlayer):
         llc_checkpoint = config['llc_checkpoint']
         assert llc_checkpoint != ""                                          # learning/hrl_players.py:30
         self._build_llc(self._llc_params, llc_checkpoint)
+        self._device_llc_step = bool(config.get('device_llc_step', False))   # opt-in: the inner loop's glue as three launches
+        if self._device_llc_step:
+            self._check_device_llc_step()
+            n, f32 = self.env.task.num_envs, torch.float32
+            self._llc_acc = torch.zeros(4, n, dtype=f32, device=self.device)
+            self._llc_out = torch.zeros(3, n, dtype=f32, device=self.device)
+            self._llc_actions = torch.zeros(n, self.actions_low.numel(), dtype=f32, device=self.device)
+            for which in ('obs', 'amp'):          # the LLC's eval statistics, once: no rms_finalize inside the loop
+                self._llc_agent.engine.frozen_stats(which)
 
     def _setup_action_space(self):
         super()._setup_action_space()
@@ -369,7 +380,44 @@ class HRLPlayer(CommonPlayer):
         action = self.get_action(obs_dict, self.is_determenistic)
         return self.env_step(self.env, obs_dict, action)
 
+    def _check_device_llc_step(self):
+        """What config['device_llc_step'] needs, refused at construction."""
+        llc = self._llc_agent
+        assert not (llc.engine.mu_tanh or getattr(llc.model.a2c_network, 'mu_tanh', False)), \
+            "device_llc_step: an LLC with mu_tanh is not supported (hrl_llc_action has no tanh)"
+        assert 1 <= self._latent_dim <= 128, f"device_llc_step: latent_dim {self._latent_dim} outside [1, 128]"
+        assert self.actions_low.numel() <= 128, f"device_llc_step: environment action width {self.actions_low.numel()} above 128"
+        assert not getattr(self.env, 'returns_numpy', False), "device_llc_step takes tensors only: the environment returns numpy"
+        assert all(hasattr(self.backend, k) for k in ('hrl_latent', 'hrl_llc_action', 'hrl_accum')), \
+            "device_llc_step needs a backend with hrl_latent / hrl_llc_action / hrl_accum"
+
+    def _env_step_device(self, env, obs_dict, action):
+        """env_step with config['device_llc_step']: HRLAgent._env_step_device without the terminate count."""
+        be, llc, dev, T = self.backend, self._llc_agent, self.device, self._llc_steps
+        e = llc.engine
+        obs, n = obs_dict['obs'], action.shape[0]
+
+        def tensor(t, who):
+            assert torch.is_tensor(t), f"device_llc_step takes tensors only: the environment returned {type(t).__name__} for {who}"
+            return t.to(dev)
+        be.hrl_latent(action, z2=e.style_input(n), dim=self._latent_dim)
+        out = self._llc_out
+        for t in range(T):
+            MU = e.policy_mu_frozen(self._extract_llc_obs(obs))
+            be.hrl_llc_action(MU, self.actions_low, self.actions_high, self._llc_actions, e.act, clip=True)
+            obs, curr_rewards, curr_dones, infos = env.step(self._llc_actions)
+            obs = tensor(obs['obs'] if isinstance(obs, dict) else obs, 'obs')
+            amp_obs = tensor(infos['amp_obs'], 'amp_obs')
+            HD, _ = e.amp_heads(amp_obs.view(-1, amp_obs.shape[-1]), frozen=True, want_enc=False)
+            curr_rewards = tensor(curr_rewards, 'rewards')
+            be.hrl_accum(curr_rewards.view(-1), tensor(curr_dones, 'dones'), self._llc_acc, t == 0, t == T - 1, T, logit=HD,
+                         disc_scale=llc._disc_reward_scale, rewards_out=out[0], disc_out=out[1], dones_out=out[2])
+        infos['disc_rewards'] = out[1].view(n, 1)
+        return self.obs_to_torch(obs), out[0].view(curr_rewards.shape), out[2], infos
+
     def env_step(self, env, obs_dict, action):
+        if self._device_llc_step:
+            return self._env_step_device(env, obs_dict, action)
         obs = obs_dict['obs']
         rewards = done_count = disc_rewards = 0.0
         for t in range(self._llc_steps):

@@ -103,6 +103,9 @@ SIGNATURES = {
                               + [_p, _i64, _i, _i, _p, _p],
     "ase_hip_rollout_store": [_p, _i, _p, _f, _f, _p, _i64, _p, _i, _p, _i64, _p, _p, _i, _p, _i64, _p, _p, _p, _i, _p, _i64, _p,
                               _i, _i, _p, _i, _p],
+    "ase_hip_hrl_latent": [_p, _i64, _p, _i64, _p, _i64, _i, _i, _i, _p],
+    "ase_hip_hrl_llc_action": [_p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p],
+    "ase_hip_hrl_accum": [_p, _p, _i, _p, _i, _p, _i64, _f, _p, _i64, _i, _i, _i, _p, _p, _p, _p, _i, _p],
     "ase_hip_clip_frames": [_p] * 6 + [_i] + [_p] * 4 + [_i, _i, _p, _p, _i] + [_p] * 7,
     "ase_hip_gemm_nt_kernel_id": [_i, _i, _i, _i],
     "ase_hip_gemm_tn_kernel_id": [_i, _i, _i, _i, _i, _i64, _i64, _i],

@@ -77,6 +77,14 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
                                                       list written in place) one environment step into experience slot `slot`:
                                                       what play_steps does behind env_step, without dones.nonzero
                                                       (learning/common_agent.py:267-293)
+  hrl_latent(actions) -> z                            F.normalize(torch.clamp(actions, -1, 1), dim=-1): the latent a high-level
+                                                      action selects, once per high-level step (learning/hrl_agent.py:89-93,235)
+  hrl_llc_action(mu, low, high, act, clip) -> a       the LLC's padded head output -> the environment's action: clamp and
+                                                      rl_games rescale_actions (ASEAgent.preprocess_actions, hrl_agent.py:238)
+  hrl_accum(rewards, dones, terminate, logit, disc_scale, acc, first, last, llc_steps, rewards_out, disc_out, dones_out,
+            terminate_out) -> ()                      (acc and, with last, the four outputs written in place) one inner step's
+                                                      task reward, discriminator reward and done / terminate counts folded into
+                                                      the running sums; the means and masks at the end (hrl_agent.py:57-73)
   clip_frames(rotation, root_translation, root_velocity, root_angular_velocity, local_translation, clip_first, clip_num_frames,
               clip_fps, frame_clip, parent_indices, dof_body_ids, dof_offsets) -> (gts, grs, lrs, grvs, gravs, dvs)
                                                       the clip loader: forward kinematics and joint velocities of every frame of
@@ -812,6 +820,54 @@ def rollout_store(dones: torch.Tensor, slot: int, n_slots: int, srcs: list[torch
 @rollout_store.register_fake
 def _(dones, slot, n_slots, srcs, dsts, rewards, shift, scale, rewards_out, dones_out, next_values, terminate, next_values_out,
       cur_rewards, cur_lengths, meter, max_size, done_ids_out, slot_dev=None):
+    return None
+
+
+@torch.library.custom_op('ase_hip::hrl_latent', mutates_args=(), device_types='cuda')
+def hrl_latent(actions: torch.Tensor) -> torch.Tensor:
+    _check(actions.dim() == 2 and actions.dtype == torch.float32 and 1 <= actions.shape[1] <= 128 and actions.stride(1) == 1,
+           'hrl_latent: actions f32 [n, 1 <= d <= 128], unit column stride')
+    z = torch.empty(actions.shape, dtype=torch.float32, device=actions.device)
+    _backend().hrl_latent(actions, z=z)
+    return z
+
+
+@hrl_latent.register_fake
+def _(actions):
+    return actions.new_empty(actions.shape)
+
+
+@torch.library.custom_op('ase_hip::hrl_llc_action', mutates_args=(), device_types='cuda')
+def hrl_llc_action(mu: torch.Tensor, low: torch.Tensor, high: torch.Tensor, act: int, clip: bool) -> torch.Tensor:
+    _check(mu.dim() == 2 and mu.dtype == torch.float32 and 1 <= act <= 128 and mu.shape[1] >= act and mu.stride(1) == 1,
+           'hrl_llc_action: mu f32 [n, >= act], 1 <= act <= 128, unit column stride')
+    out = torch.empty(mu.shape[0], act, dtype=torch.float32, device=mu.device)
+    _backend().hrl_llc_action(mu, low.float().contiguous(), high.float().contiguous(), out, act, clip)
+    return out
+
+
+@hrl_llc_action.register_fake
+def _(mu, low, high, act, clip):
+    return mu.new_empty(mu.shape[0], act)
+
+
+@torch.library.custom_op('ase_hip::hrl_accum', mutates_args=('acc', 'rewards_out', 'disc_out', 'dones_out', 'terminate_out'),
+                         device_types='cuda')
+def hrl_accum(rewards: torch.Tensor, dones: torch.Tensor, terminate: torch.Tensor | None, logit: torch.Tensor | None,
+              disc_scale: float, acc: torch.Tensor, first: bool, last: bool, llc_steps: int, rewards_out: torch.Tensor | None,
+              disc_out: torch.Tensor | None, dones_out: torch.Tensor | None, terminate_out: torch.Tensor | None) -> None:
+    """One inner step of HRLAgent.env_step folded into acc f32 [4, n] (operands: see ase_hip_hrl_accum); with last the means and
+    masks go to the four f32 outputs.  Every tensor is passed by position, None where a group is left out."""
+    kinds = (torch.uint8, torch.bool, torch.int32, torch.int64, torch.float32)
+    _check(dones.dtype in kinds and (terminate is None or terminate.dtype in kinds),
+           'hrl_accum: dones / terminate must be uint8, bool, int32, int64 or float32')
+    _check(llc_steps >= 1, 'hrl_accum: llc_steps >= 1')
+    _backend().hrl_accum(rewards, dones, acc, first, last, llc_steps, terminate=terminate, logit=logit, disc_scale=disc_scale,
+                         rewards_out=rewards_out, disc_out=disc_out, dones_out=dones_out, terminate_out=terminate_out)
+
+
+@hrl_accum.register_fake
+def _(rewards, dones, terminate, logit, disc_scale, acc, first, last, llc_steps, rewards_out, disc_out, dones_out, terminate_out):
     return None
 
 

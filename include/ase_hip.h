@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id and ase_hip_rollout_store were added WITHOUT a new version
+/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id, ase_hip_rollout_store and ase_hip_hrl_latent / ase_hip_hrl_llc_action / ase_hip_hrl_accum were added WITHOUT a new version
  *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
  *  load time) */
 #define ASE_HIP_ABI_VERSION 9
@@ -562,6 +562,55 @@ int ase_hip_rollout_store(const int64_t* fields, int n_fields, const float* rewa
                           float* next_values_out, int64_t next_values_ss, float* cur_rewards, float* cur_lengths,
                           double* meter, int max_size, double* workspace, int64_t workspace_doubles, int32_t* done_ids_out,
                           int n_envs, int slot, const int32_t* slot_dev, int n_slots, void* stream);
+
+/* The glue of the HRL agent's inner loop (additions to ABI 9, nothing else changed): one high-level step wraps
+ * llc_steps simulator steps around the frozen low-level controller (learning/hrl_agent.py:45-82).  Three entries, each ONE
+ * launch on a grid that depends on n alone, no atomics, no intermediate tensor, recordable in a launch program.  Every f32
+ * operation named below is rounded on its own (no a * b + c contraction).
+ *
+ * ase_hip_hrl_latent, once per high-level step: z[e, :] = normalize(clamp(actions[e, :], -1, 1)) - the high-level
+ *   preprocess_actions and F.normalize (learning/hrl_agent.py:89-93,235).  actions f32 [n, ld_a], dim in [1, 128], one wave
+ *   per row.  The clamp is torch.clamp's: a NaN stays NaN, -0.0 stays -0.0.  The normalisation is ase_hip_normalize_rows'
+ *   arithmetic (x / max(sqrt(sum x^2), 1e-12), the sum in the wave's butterfly order), so z is bitwise
+ *   ase_hip_normalize_rows(torch.clamp(actions, -1, 1)).  z f32 [n, ld_z], nullable.  z2 (nullable): a second copy in
+ *   z2_dtype (ASE_F32 / ASE_BF16 / ASE_F16; the 16-bit types rounded to nearest even, f16 saturating as ase_hip_gather_rows
+ *   stores it) at pitch ld_z2 - the style chain's input buffer; columns [0, dim) only, the pad columns are not touched.
+ *   Refused: NULL actions; neither z nor z2; dim outside [1, 128]; a pitch below dim; a z2_dtype outside the three; n < 1.
+ *
+ * ase_hip_hrl_llc_action, once per inner step: the padded f32 head output mu [n, ld_mu] -> the action the environment gets,
+ *   out f32 [n, ld_out] (ASEAgent.preprocess_actions through learning/hrl_agent.py:238; rl_games rescale_actions), one lane per
+ *   element, act in [1, 128].  clip != 0:
+ *     out[e, j] = clamp(mu[e, j], -1, 1) * ((high[j] - low[j]) / 2) + ((high[j] + low[j]) / 2)
+ *   in that order - the two bound terms, the multiply, then the add; the clamp keeps a NaN.  clip == 0: out[e, j] = mu[e, j],
+ *   a strided copy; low / high may be NULL.  mu is read at its own pitch: no gather runs in front.
+ *   Refused: NULL mu / out; clip without low / high; act outside [1, 128]; a pitch below act; n < 1.
+ *
+ * ase_hip_hrl_accum, once per inner step, one lane per environment (learning/hrl_agent.py:57-73).  acc: f32 [4, n] at row pitch
+ *   acc_stride >= n = {task-reward sum, discriminator-reward sum, done count, terminate count}.  Each row does
+ *     acc[k, e] = (first ? 0.0f : acc[k, e]) + x_k[e]
+ *   (first != 0: the accumulator's content on entry does not matter and is not read; the 0.0f + turns a first -0.0 into +0.0,
+ *   as the reference's 0.0 + tensor does) with x_0 = rewards[e]; x_1 = -log(max(1 - sigmoid(l), 1e-4)) * disc_scale of
+ *   l = logit[e * ld_l], the device function of ase_hip_disc_reward; x_2, x_3 = the float values of dones[e] / terminate[e],
+ *   typed by dones_kind / terminate_kind (ASE_KIND_*, as in ase_hip_rollout_store).  last != 0: the call also writes the finals,
+ *     rewards_out[e] = acc[0, e] / (float)llc_steps, disc_out[e] = acc[1, e] / (float)llc_steps
+ *   - an IEEE DIVISION, correctly rounded, NOT a multiplication by the rounded reciprocal (the two differ for llc_steps 3 and
+ *   5) - and dones_out[e] = acc[2, e] > 0 ? 1.0f : 0.0f, terminate_out[e] likewise from acc[3, e] (f32; a NaN count gives 0,
+ *   as the reference's (count > 0) mask).  last == 0 leaves the four outputs untouched, and they may be NULL.
+ *   Optional groups: {terminate, terminate_out} (a player has no terminate: row 3 is not touched), {logit, disc_out} (row 1 is
+ *   not touched).
+ *   Refused: NULL rewards / dones / acc; a kind code outside the four; terminate_out without terminate or disc_out without logit;
+ *   last with terminate but no terminate_out, or with logit but no disc_out; ld_l < 1 with a logit; llc_steps < 1; last without
+ *   rewards_out / dones_out; acc_stride < n; n < 1.
+ * Replaces, per inner step: F.normalize and the high-level clamp (hoisted to once per high-level step), the LLC's clamp and
+ *   rescale_actions, _calc_disc_reward's reward expression, the four running sums, the two divisions and the two masks. */
+int ase_hip_hrl_latent(const float* actions, int64_t ld_a, float* z, int64_t ld_z, void* z2, int64_t ld_z2, int z2_dtype,
+                       int n, int dim, void* stream);
+int ase_hip_hrl_llc_action(const float* mu, int64_t ld_mu, const float* low, const float* high, float* out, int64_t ld_out,
+                           int n, int act, int clip, void* stream);
+int ase_hip_hrl_accum(const float* rewards, const void* dones, int dones_kind, const void* terminate, int terminate_kind,
+                      const float* logit, int64_t ld_l, float disc_scale, float* acc, int64_t acc_stride, int first, int last,
+                      int llc_steps, float* rewards_out, float* disc_out, float* dones_out, float* terminate_out, int n,
+                      void* stream);
 
 /* The whole optimizer step of every dense layer in ONE launch: weight-only gradient terms (g += c * w: discriminator
  * weight decay / logit regulariser / encoder weight decay), their reported sums of squares (pre-update weights, into

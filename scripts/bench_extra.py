@@ -19,6 +19,10 @@ rollout-time inference path.  One JSON line per measurement on stdout.
   rollout-store: what play_steps does behind env_step for one step of config 2 (4096 envs, obs 253, actions 31, amp 1400, latents
           64, dones at 1/300): the host block (some thirty torch launches and dones.nonzero's round trip) next to the one
           rollout_store call, eager and replayed from a launch program (reported, not gated)
+  hrl-step: the glue of one high-level HRL step around the frozen controller's dense layers at config 4's size (4096 envs,
+          llc_steps 5, obs 253 + 5 task, actions 31, amp 1400, latents 64) - the default path's per-statement launches next to
+          hrl_latent once and rms_normalize / hrl_llc_action / rms_normalize / hrl_accum per inner step, eager and replayed from a
+          launch program; the dense layers and the environment are left out of both (reported, not gated)
   infer : get_action_values (eval-mode normalisation + actor + critic forward + sample) on 4096 observations
 """
 import argparse
@@ -339,6 +343,95 @@ def rollout_store_case():
     be.prog_destroy(prog)
 
 
+def hrl_step_case():
+    """The glue of one high-level step of config 4 (HRLAgent.env_step around the LLC's dense layers and vec_env.step), both ways on
+    the same tensors: the default path's statements (ForwardEngine.policy_forward / amp_heads / _calc_disc_rewards and the torch
+    lines of env_step, dense layers left out) and the device_llc_step sequence.  Steps are issued back to back and timed between
+    two events - the larger of host and GPU time.  Seven repeats of 100 high-level steps each: median and spread."""
+    from ase_amd.backend import HipBackend
+    from ase_amd.forward import P
+    from ase_amd.learning.agents import rescale_actions
+    be = HipBackend('cuda:0')
+    g = torch.Generator().manual_seed(0)
+    N, T, OBS, TASK, ACT, AMP, Z = 4096, 5, 253, 5, 31, 1400, 64
+    dev, bf16, f32 = 'cuda:0', torch.bfloat16, torch.float32
+    rnd = lambda *shape: torch.randn(*shape, generator=g).to(dev)
+    obs, amp_obs, actions = rnd(N, OBS + TASK), rnd(N, AMP), rnd(N, Z) * 1.5
+    MU, HD = rnd(N, P(ACT)), rnd(N, 64)                          # the padded head outputs the dense layers leave behind
+    low, high = -torch.rand(ACT, generator=g).to(dev) - 0.5, torch.rand(ACT, generator=g).to(dev) + 0.5
+    rewards = torch.ones(N, device=dev)
+    dones = (torch.rand(N, generator=g) < 1.0 / 300).to(torch.uint8).to(dev)
+    terminate = (torch.rand(N, generator=g) < 1.0 / 600).to(dev)
+    obs_state = torch.cat([rnd(OBS).double(), torch.rand(OBS, generator=g).double().to(dev) + 0.5, torch.ones(1, dtype=torch.float64, device=dev)])
+    amp_state = torch.cat([rnd(AMP).double(), torch.rand(AMP, generator=g).double().to(dev) + 0.5, torch.ones(1, dtype=torch.float64, device=dev)])
+    kpad = P(OBS) + P(Z)
+    Xa, Xc, Zs, Xd = (torch.zeros(N, c, dtype=bf16, device=dev) for c in (kpad, kpad, P(Z), P(AMP)))
+    z, mu = torch.zeros(N, Z, device=dev), torch.zeros(N, ACT, device=dev)
+    om, os_, am, as_ = (torch.zeros(1, c, device=dev) for c in (OBS, OBS, AMP, AMP))
+    scale = 2.0
+
+    def default_path():
+        a = torch.clamp(actions, -1.0, 1.0)
+        r = dr = dc = tc = 0.0
+        for t in range(T):
+            llc_obs = obs[..., :OBS].contiguous()
+            be.normalize_rows(a, z, N, Z)
+            be.rms_finalize(obs_state, OBS, None, 0, 0, om, os_)
+            be.rms_normalize(llc_obs, OBS, None, (0, 0), N, om[0], os_[0], [Xa, Xc])
+            be.gather_rows(z, Z, None, (0, 0), N, Xc[:, P(OBS):])
+            be.gather_rows(z, Z, None, (0, 0), N, Zs)
+            be.gather_rows(MU, ACT, None, (0, 0), N, mu)
+            rescale_actions(low, high, torch.clamp(mu, -1.0, 1.0))
+            be.rms_finalize(amp_state, AMP, None, 0, 0, am, as_)
+            be.rms_normalize(amp_obs, AMP, None, (0, 0), N, am[0], as_[0], [Xd])
+            d = torch.empty(N, 1, dtype=f32, device=dev)
+            be.disc_reward(HD, d, N, scale)
+            r = r + rewards
+            dc = dc + dones.float()
+            tc = tc + terminate.float()
+            dr = dr + d
+        r, dr = r / T, dr / T
+        return r, dr, (dc > 0).to(dc.dtype), (tc > 0).to(tc.dtype)
+
+    acc, outs, env_actions = torch.zeros(4, N, device=dev), torch.zeros(4, N, device=dev), torch.zeros(N, ACT, device=dev)
+    be.rms_finalize(obs_state, OBS, None, 0, 0, om, os_)        # the frozen statistics, once
+    be.rms_finalize(amp_state, AMP, None, 0, 0, am, as_)
+
+    def key_path():
+        be.hrl_latent(actions, z2=Zs, dim=Z)
+        for t in range(T):
+            be.rms_normalize(obs[:, :OBS], OBS, None, (0, 0), N, om[0], os_[0], [Xa])
+            be.hrl_llc_action(MU, low, high, env_actions, ACT)
+            be.rms_normalize(amp_obs, AMP, None, (0, 0), N, am[0], as_[0], [Xd])
+            be.hrl_accum(rewards, dones, acc, t == 0, t == T - 1, T, terminate=terminate, logit=HD, disc_scale=scale,
+                         rewards_out=outs[0], disc_out=outs[1], dones_out=outs[2], terminate_out=outs[3])
+    prog = be.prog_create()
+    be.prog_begin(prog)
+    key_path()
+    be.prog_end(prog)
+    entries = be.prog_size(prog)
+
+    def timeit(fn, calls=100):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(calls):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / calls * 1e3
+    for name, fn, launches in (('hrl step glue, default path (per-statement launches, eager)', default_path, None),
+                               ('hrl step glue, device_llc_step (eager)', key_path, entries),
+                               ('hrl step glue, device_llc_step replayed from a launch program', lambda: be.prog_launch(prog), entries)):
+        reps = sorted(timeit(fn) for _ in range(7))
+        print(json.dumps({'measurement': name, 'envs': N, 'llc_steps': T, 'launches_per_step': launches,
+                          'us_per_step_median': round(reps[3], 1), 'us_per_step_min': round(reps[0], 1),
+                          'us_per_step_max': round(reps[-1], 1), 'repeats': 7, 'steps_per_repeat': 100}), flush=True)
+    be.prog_destroy(prog)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--updates', type=int, default=4)
@@ -435,6 +528,8 @@ def main():
         amp_reset_case()
     if not args.only or 'rollout-store' in args.only.split(','):
         rollout_store_case()
+    if not args.only or 'hrl-step' in args.only.split(','):
+        hrl_step_case()
     if not args.only or 'ampobs' in args.only.split(','):
         # N2: observation production for 4096 envs (one frame + history push) and 5120 demo samples (512 x 10 steps)
         from ase_amd.backend import HipBackend
