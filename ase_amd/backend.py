@@ -733,6 +733,116 @@ class HipBackend:
                                            _ld(logit), float(disc_scale), _ptr(acc), _ld(acc), int(bool(first)), int(bool(last)),
                                            int(llc_steps), *[_ptr(t) for t in outs], n, self._stream()), "hrl_accum")
 
+    # ------------------------------------------------------------------ one environment step, one launch per side (N14)
+    def _state_view(self, t, shape, who):
+        """A state operand the step kernels read in place: f32 on this GPU, the last dimension dense, any environment / element
+        stride that covers the elements (a contiguous tensor or a window of the simulator's packed tensor) -> (pointer,
+        environment stride, element stride); a 2-d operand -> (pointer, row stride)."""
+        assert self._here(t), f"{who}: a tensor on {self.device}, not {t.device}"
+        assert t.dtype == torch.float32 and tuple(t.shape) == tuple(shape), f"{who}: f32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}"
+        assert t.dim() == 2 or t.stride(2) == 1, f"{who}: the last dimension is dense"
+        return _ptr(t), int(t.stride(0)), int(t.stride(1))      # (whether the strides cover the elements: the entry's own check)
+
+    def _state_rows(self, t, n, cols, who):
+        """[n, cols] rows with unit column stride at any row stride >= cols (an actor window of a packed tensor)."""
+        if t is None:
+            return None, 0
+        assert self._here(t) and t.dtype == torch.float32 and tuple(t.shape) == (n, cols) and t.stride(1) == 1 and t.stride(0) >= cols, \
+            f"{who}: f32 [{n}, {cols}] rows on {self.device}, unit column stride"
+        return _ptr(t), int(t.stride(0))
+
+    def _dense(self, t, numel, dtype, who):
+        if t is None:
+            return None
+        assert self._here(t) and t.dtype == dtype and t.numel() == numel and t.is_contiguous(), \
+            f"{who}: contiguous {dtype} of {numel} elements on {self.device}"
+        return _ptr(t)
+
+    def _id_array(self, ids):
+        """The host-side id list of a body mask, built once per distinct list and kept."""
+        if ids is None:
+            return None, 0
+        key = tuple(int(x) for x in ids)
+        cache = self.__dict__.setdefault('_id_arrays', {})
+        if key not in cache:
+            cache[key] = (C.c_int32 * len(key))(*key)
+        return cache[key], len(key)
+
+    def env_pre_step(self, actions_in, actions, targets, clip_actions=1.0, pd_offset=None, pd_scale=None, motor_efforts=None,
+                     power_scale=1.0, root_states=None, prev_root_pos=None, recovery_counter=None):
+        """The pre_physics_step chain in one launch (ase_hip_env_pre_step): actions = clamp(actions_in, +-clip_actions) (actions_in
+        f32 [n, D] at its own pitch, e.g. a view of the agent's buffer); targets = pd_offset + pd_scale * actions with pd_offset /
+        pd_scale, else actions * motor_efforts * power_scale; prev_root_pos [n, 3] = root_states[:, 0:3] when given;
+        recovery_counter int32 [n] = max(recovery_counter - 1, 0) when given.  Recordable in a launch program."""
+        n, D = actions_in.shape
+        f32 = torch.float32
+        for t, who in ((actions_in, 'actions_in'), (actions, 'actions'), (targets, 'targets')):
+            self._hrl_rows(t, n, D, f32, who)
+        pd = pd_offset is not None
+        assert pd == (pd_scale is not None) and pd != (motor_efforts is not None), "env_pre_step: pd_offset + pd_scale, or motor_efforts"
+        rs, rs_stride = self._state_rows(root_states, n, 13, 'root_states')
+        L.check(self.lib.ase_hip_env_pre_step(_ptr(actions_in), _ld(actions_in), float(clip_actions), _ptr(actions), _ld(actions),
+                                              _ptr(targets), _ld(targets), int(pd), self._dense(pd_offset, D, f32, 'pd_offset'),
+                                              self._dense(pd_scale, D, f32, 'pd_scale'), self._dense(motor_efforts, D, f32, 'motor_efforts'),
+                                              float(power_scale), rs if prev_root_pos is not None else None, rs_stride,
+                                              self._dense(prev_root_pos, 3 * n, f32, 'prev_root_pos'),
+                                              self._dense(recovery_counter, n, torch.int32, 'recovery_counter'), n, D, self._stream()),
+                "env_pre_step")
+
+    def env_post_step(self, body_pos, body_rot, body_vel, body_ang_vel, contact_forces, progress_buf, obs, reward, reset, terminated,
+                      termination_heights, contact_body_ids, max_episode_length, enable_early_termination, local_root_obs,
+                      root_height_obs, col_offset=0, clip_obs=float('inf'), task_kind=None, enable_task_obs=True, task_col_offset=None,
+                      root_states=None, prev_root_pos=None, tar_a=None, tar_b=None, tar_speed=None, tar_states=None, reach_body_id=0,
+                      dt=0.0, tar_contact_forces=None, strike_body_ids=None, recovery_counter=None, hist=None, dof_pos=None,
+                      dof_vel=None, dof_offsets=None, key_body_ids=None):
+        """Humanoid.post_physics_step + HumanoidAMP.post_physics_step in one launch (ase_hip_env_post_step) on state read in place:
+        body_pos / _vel / _ang_vel [n, B, 3], body_rot [n, B, 4], contact_forces [n, B, 3] and dof_pos / dof_vel [n, D] at any
+        strides that cover them (windows of the simulator's packed tensors); root_states / tar_states [n, 13] and
+        tar_contact_forces [n, 3] at any row stride.  progress_buf += 1; the humanoid columns at col_offset of obs and the task's
+        at task_col_offset (default: right behind), clamped to +-clip_obs; reward (the task's, or 1); reset / terminated with
+        the recovery mask when recovery_counter is given; hist [n, S, F] shifted and its slot 0 rebuilt when given.  Task operands
+        as task_obs / task_reward take them (tar_speed: tensor [n] for heading, python float for location).  Recordable."""
+        n, B = body_pos.shape[0], body_pos.shape[1]
+        f32, i64 = torch.float32, torch.int64
+        views = [self._state_view(t, (n, B, w), who) for t, w, who in ((body_pos, 3, 'body_pos'), (body_rot, 4, 'body_rot'),
+                                                                       (body_vel, 3, 'body_vel'), (body_ang_vel, 3, 'body_ang_vel'),
+                                                                       (contact_forces, 3, 'contact_forces'))]
+        D = 0
+        if hist is not None:
+            assert self._here(hist) and hist.dtype == f32 and hist.dim() == 3 and hist.shape[0] == n and hist.is_contiguous(), \
+                f"hist: contiguous f32 [{n}, S, F] on {self.device}"
+            D = int(dof_offsets[-1])
+            views += [self._state_view(t, (n, D), who) for t, who in ((dof_pos, 'dof_pos'), (dof_vel, 'dof_vel'))]
+            assert hist.shape[2] == 13 + 6 * (len(dof_offsets) - 1) + D + 3 * len(key_body_ids), "hist: the frame width of the character"
+        else:
+            views += [(None, 0, 0), (None, 0, 0)]
+        self._hrl_rows(obs, n, 1, f32, 'obs')
+        kind = -1 if task_kind is None else int(task_kind)
+        task_obs = bool(enable_task_obs) and kind >= 0
+        if task_col_offset is None:
+            task_col_offset = int(col_offset) + 15 * B - 2
+        assert obs.shape[1] >= max(int(col_offset) + 15 * B - 2, int(task_col_offset) + L.TASK_OBS_COLS[kind] if task_obs else 0), \
+            "obs: the columns do not fit its width"
+        speed_t = tar_speed if torch.is_tensor(tar_speed) else None
+        rs, rs_stride = self._state_rows(root_states, n, 13, 'root_states')
+        ts, ts_stride = self._state_rows(tar_states, n, 13, 'tar_states')
+        tc, tc_stride = self._state_rows(tar_contact_forces, n, 3, 'tar_contact_forces')
+        wa = 3 if kind == L.TASK_REACH else 2
+        offs, n_off = self._id_array(dof_offsets if hist is not None else None)
+        keys, n_key = self._id_array(key_body_ids if hist is not None else None)
+        contact, n_contact = self._id_array(contact_body_ids)
+        strike, n_strike = self._id_array(strike_body_ids)
+        L.check(self.lib.ase_hip_env_post_step(
+            *[x for v in views for x in v], n, B, D, int(local_root_obs), int(root_height_obs), _ptr(obs), _ld(obs), int(col_offset),
+            float(clip_obs), kind, int(task_obs), int(task_col_offset), rs, rs_stride, self._dense(prev_root_pos, 3 * n, f32, 'prev_root_pos'),
+            self._dense(tar_a, wa * n, f32, 'tar_a'), self._dense(tar_b, 2 * n, f32, 'tar_b'), self._dense(speed_t, n, f32, 'tar_speed'),
+            0.0 if speed_t is not None or tar_speed is None else float(tar_speed), ts, ts_stride, int(reach_body_id), float(dt),
+            self._dense(reward, n, f32, 'reward'), self._dense(progress_buf, n, i64, 'progress_buf'),
+            self._dense(termination_heights, B, f32, 'termination_heights'), contact, n_contact, tc, tc_stride, strike, n_strike,
+            float(max_episode_length), int(enable_early_termination), self._dense(recovery_counter, n, torch.int32, 'recovery_counter'),
+            self._dense(reset, n, i64, 'reset'), self._dense(terminated, n, i64, 'terminated'), _ptr(hist),
+            0 if hist is None else hist.shape[1], offs, max(n_off - 1, 0), keys, n_key, self._stream()), "env_post_step")
+
     # ------------------------------------------------------------------ normaliser / gather
     def rms_moments(self, src, D, idx, remap, M, state, sums):
         L.check(self.lib.ase_hip_rms_moments(_ptr(src), _ld(src), D, _ptr(idx), remap[0], remap[1], M, _ptr(state),

@@ -85,6 +85,13 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
             terminate_out) -> ()                      (acc and, with last, the four outputs written in place) one inner step's
                                                       task reward, discriminator reward and done / terminate counts folded into
                                                       the running sums; the means and masks at the end (hrl_agent.py:57-73)
+  env_pre_step(actions_in, actions, targets, clip_actions, pd_offset, pd_scale, motor_efforts, power_scale, root_states,
+               prev_root_pos, recovery_counter) -> () (actions, targets, prev_root_pos, recovery_counter written in place) the
+                                                      pre_physics_step chain: action clamp and copy, PD targets or forces, the
+                                                      previous root position, the recovery counter (humanoid.py:361-366,479-481)
+  env_post_step(body_pos, ..., key_body_ids) -> ()    (progress_buf, obs, reward, reset, terminated, hist written in place)
+                                                      Humanoid.post_physics_step + HumanoidAMP.post_physics_step on state read
+                                                      in place at its own strides (humanoid.py:368-383, humanoid_amp.py:50-59)
   clip_frames(rotation, root_translation, root_velocity, root_angular_velocity, local_translation, clip_first, clip_num_frames,
               clip_fps, frame_clip, parent_indices, dof_body_ids, dof_offsets) -> (gts, grs, lrs, grvs, gravs, dvs)
                                                       the clip loader: forward kinematics and joint velocities of every frame of
@@ -868,6 +875,63 @@ def hrl_accum(rewards: torch.Tensor, dones: torch.Tensor, terminate: torch.Tenso
 
 @hrl_accum.register_fake
 def _(rewards, dones, terminate, logit, disc_scale, acc, first, last, llc_steps, rewards_out, disc_out, dones_out, terminate_out):
+    return None
+
+
+@torch.library.custom_op('ase_hip::env_pre_step', mutates_args=('actions', 'targets', 'prev_root_pos', 'recovery_counter'),
+                         device_types='cuda')
+def env_pre_step(actions_in: torch.Tensor, actions: torch.Tensor, targets: torch.Tensor, clip_actions: float,
+                 pd_offset: torch.Tensor | None, pd_scale: torch.Tensor | None, motor_efforts: torch.Tensor | None, power_scale: float,
+                 root_states: torch.Tensor | None, prev_root_pos: torch.Tensor | None, recovery_counter: torch.Tensor | None) -> None:
+    """The pre_physics_step chain in one launch (operands: see ase_hip_env_pre_step).  Every tensor is passed by position, None
+    where a group is left out; actions, targets, prev_root_pos and recovery_counter are written in place."""
+    _check(actions_in.dim() == 2 and actions_in.dtype == torch.float32, 'env_pre_step: actions_in f32 [n, D]')
+    _check((pd_offset is None) == (pd_scale is None) and (pd_offset is None) != (motor_efforts is None),
+           'env_pre_step: pd_offset AND pd_scale, or motor_efforts')
+    _backend().env_pre_step(actions_in, actions, targets, clip_actions, pd_offset, pd_scale, motor_efforts, power_scale, root_states,
+                            prev_root_pos, recovery_counter)
+
+
+@env_pre_step.register_fake
+def _(actions_in, actions, targets, clip_actions, pd_offset, pd_scale, motor_efforts, power_scale, root_states, prev_root_pos,
+      recovery_counter):
+    return None
+
+
+@torch.library.custom_op('ase_hip::env_post_step', mutates_args=('progress_buf', 'obs', 'reward', 'reset', 'terminated', 'hist'),
+                         device_types='cuda')
+def env_post_step(body_pos: torch.Tensor, body_rot: torch.Tensor, body_vel: torch.Tensor, body_ang_vel: torch.Tensor,
+                  contact_forces: torch.Tensor, progress_buf: torch.Tensor, obs: torch.Tensor, reward: torch.Tensor,
+                  reset: torch.Tensor, terminated: torch.Tensor, termination_heights: torch.Tensor, contact_body_ids: list[int],
+                  max_episode_length: float, enable_early_termination: bool, local_root_obs: bool, root_height_obs: bool,
+                  col_offset: int, clip_obs: float, kind: str | None, enable_task_obs: bool, root_states: torch.Tensor | None,
+                  prev_root_pos: torch.Tensor | None, tar_a: torch.Tensor | None, tar_b: torch.Tensor | None,
+                  tar_speed: torch.Tensor | None, tar_speed_scalar: float, tar_states: torch.Tensor | None, reach_body_id: int,
+                  dt: float, tar_contact_forces: torch.Tensor | None, strike_body_ids: list[int] | None,
+                  recovery_counter: torch.Tensor | None, hist: torch.Tensor | None, dof_pos: torch.Tensor | None,
+                  dof_vel: torch.Tensor | None, dof_offsets: list[int] | None, key_body_ids: list[int] | None) -> None:
+    """Humanoid.post_physics_step + HumanoidAMP.post_physics_step in one launch on state read in place (operands: see
+    ase_hip_env_post_step; kind: 'heading' | 'location' | 'reach' | 'strike' | None).  Every tensor is passed by position, None
+    where a group is left out; progress_buf, obs, reward, reset, terminated and hist are written in place."""
+    k = None if kind is None else _task_kind(kind)
+    _check(body_pos.dim() == 3 and body_pos.shape[2] == 3, 'env_post_step: body_pos [n, B, 3]')
+    _check((hist is None) or (dof_pos is not None and dof_vel is not None and dof_offsets is not None and key_body_ids is not None),
+           'env_post_step: hist needs dof_pos, dof_vel, dof_offsets and key_body_ids')
+    _backend().env_post_step(body_pos, body_rot, body_vel, body_ang_vel, contact_forces, progress_buf, obs, reward, reset, terminated,
+                             termination_heights, contact_body_ids, max_episode_length, enable_early_termination, local_root_obs,
+                             root_height_obs, col_offset=col_offset, clip_obs=clip_obs, task_kind=k, enable_task_obs=enable_task_obs,
+                             root_states=root_states, prev_root_pos=prev_root_pos, tar_a=tar_a, tar_b=tar_b,
+                             tar_speed=tar_speed if tar_speed is not None else (tar_speed_scalar if k == L.TASK_LOCATION else None),
+                             tar_states=tar_states, reach_body_id=reach_body_id, dt=dt, tar_contact_forces=tar_contact_forces,
+                             strike_body_ids=strike_body_ids, recovery_counter=recovery_counter, hist=hist, dof_pos=dof_pos,
+                             dof_vel=dof_vel, dof_offsets=dof_offsets, key_body_ids=key_body_ids)
+
+
+@env_post_step.register_fake
+def _(body_pos, body_rot, body_vel, body_ang_vel, contact_forces, progress_buf, obs, reward, reset, terminated, termination_heights,
+      contact_body_ids, max_episode_length, enable_early_termination, local_root_obs, root_height_obs, col_offset, clip_obs, kind,
+      enable_task_obs, root_states, prev_root_pos, tar_a, tar_b, tar_speed, tar_speed_scalar, tar_states, reach_body_id, dt,
+      tar_contact_forces, strike_body_ids, recovery_counter, hist, dof_pos, dof_vel, dof_offsets, key_body_ids):
     return None
 
 

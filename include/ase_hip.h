@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id, ase_hip_rollout_store and ase_hip_hrl_latent / ase_hip_hrl_llc_action / ase_hip_hrl_accum were added WITHOUT a new version
+/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id, ase_hip_rollout_store, ase_hip_hrl_latent / ase_hip_hrl_llc_action / ase_hip_hrl_accum and ase_hip_env_pre_step / ase_hip_env_post_step were added WITHOUT a new version
  *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
  *  load time) */
 #define ASE_HIP_ABI_VERSION 9
@@ -611,6 +611,67 @@ int ase_hip_hrl_accum(const float* rewards, const void* dones, int dones_kind, c
                       const float* logit, int64_t ld_l, float disc_scale, float* acc, int64_t acc_stride, int first, int last,
                       int llc_steps, float* rewards_out, float* disc_out, float* dones_out, float* terminate_out, int n,
                       void* stream);
+
+/* One environment step's tensor work, ONE launch per side of the physics step (additions to ABI 9, nothing
+ * else changed).  Fixed grids, no atomics, no host decision: both record in a launch program.  Every f32 operation is rounded on
+ * its own (no a * b + c contraction); the arithmetic is the device functions ase_hip_humanoid_obs_max, ase_hip_humanoid_reset,
+ * ase_hip_task_obs, ase_hip_task_reward and ase_hip_build_amp_obs call, so the outputs are bitwise theirs.
+ *
+ * State operands.  A per-body or per-dof operand is a base pointer, an environment stride and an element stride, in floats:
+ *   element (e, b) sits at base + e * se + b * sb.  A contiguous [n, B, 3] tensor is (p, 3 B, 3); the position window of the
+ *   simulator's packed [n, bodies_per_env, 13] rigid-body tensor is (p, 13 bodies_per_env, 13), rotation / velocity / angular
+ *   velocity at p + 3 / + 7 / + 10; the two halves of the [n, D, 2] dof state are (p, 2 D, 2) and (p + 1, 2 D, 2).  root_states /
+ *   tar_states [.., 13] and tar_contact_forces [.., 3] have one stride (actor e at base + e * stride).  Nothing is copied.
+ *
+ * ase_hip_env_pre_step, the pre_physics_step chain, one lane per (environment, dof):
+ *   x = clamp(actions_in[e * ld_in + j], -clip_actions, clip_actions) (torch.clamp: a NaN stays NaN, -0.0 stays -0.0;
+ *   VecTaskPython.step) -> actions[e * ld_actions + j], the environment's own copy;
+ *   pd_control != 0: targets = pd_offset[j] + pd_scale[j] * x, the product and the sum each rounded (_action_to_pd_targets);
+ *   pd_control == 0: targets = x * motor_efforts[j] * power_scale, left to right (humanoid.py:361-366);
+ *   prev_root_pos (nullable) [n, 3] = root_states[e, 0:3] (heading, location, strike: humanoid_heading.py:81-85);
+ *   recovery_counter (nullable) int32 [n] = max(recovery_counter - 1, 0) (humanoid_amp_getup.py:131-134).
+ *   Refused: NULL actions_in / actions / targets; n_envs or n_dof < 1; a pitch below n_dof; clip_actions < 0 or NaN; PD control
+ *   without pd_offset / pd_scale, torque control without motor_efforts; prev_root_pos without root_states at a stride >= 3.
+ *
+ * ase_hip_env_post_step, Humanoid.post_physics_step + HumanoidAMP.post_physics_step, 16 environments per block:
+ *   progress_buf[e] += 1 (int64), and the incremented value is the one the reset test sees;
+ *   the 15 n_bodies - 2 columns of compute_humanoid_observations_max at obs + e * ld_obs + col_offset and, with enable_task_obs,
+ *   the task's 5 / 2 / 3 / 15 columns at obs + e * ld_obs + task_col_offset, every column clamped to +-clip_obs as torch.clamp
+ *   does (a NaN stays NaN; clip_obs = INFINITY stores the value as computed);
+ *   reward[e]: the task's reward (task_kind = ASE_TASK_*, operands as in ase_hip_task_reward, the reach body read from body_pos)
+ *   or 1.0f with task_kind < 0; prev_root_pos is only read;
+ *   reset[e], terminated[e] (int64): compute_humanoid_reset, the strike form with tar_contact_forces + strike_body_ids; then,
+ *   with recovery_counter (nullable, int32 [n]), both are 0 while recovery_counter[e] > 0 (humanoid_amp_getup.py:136-142);
+ *   hist (nullable) f32 [n, n_steps, F], F = 13 + 6 n_joints + n_dof + 3 n_key: every slot moves one step into the past, then
+ *   the new frame takes slot 0 - root state and key bodies are body 0 and key_body_ids of the rigid-body operands.  hist NULL:
+ *   the plain Humanoid; the dof operands and tables are then not read.
+ *   Refused: a NULL required operand; n_bodies outside [1, 64]; F > 255; an element stride smaller than its element or an
+ *   environment stride smaller than its elements; columns that do not fit ld_obs; clip_obs < 0 or NaN; a task operand missing
+ *   for its kind or given without use (reward operands, plus the observation's with enable_task_obs); enable_task_obs without a
+ *   task; dt <= 0 outside reach; body ids out of range; half a strike form; joints of other than 1 or 3 dofs.
+ * Replaces, per step: progress_buf += 1, five contiguous copies and an indexed gather in front of build_amp_obs, the two
+ *   launches of ase_hip_build_amp_obs, ase_hip_humanoid_obs_max, ase_hip_task_obs, ase_hip_task_reward, ase_hip_humanoid_reset,
+ *   the two masked fills of the recovery mask and torch.clamp of the observation; the action clamp and clone, the PD-target
+ *   expression, the prev_root_pos copy and the counter's sub / clamp. */
+int ase_hip_env_pre_step(const float* actions_in, int64_t ld_in, float clip_actions, float* actions, int64_t ld_actions,
+                         float* targets, int64_t ld_targets, int pd_control, const float* pd_offset, const float* pd_scale,
+                         const float* motor_efforts, float power_scale, const float* root_states, int64_t root_stride,
+                         float* prev_root_pos, int32_t* recovery_counter, int n_envs, int n_dof, void* stream);
+int ase_hip_env_post_step(const float* body_pos, int64_t pos_se, int64_t pos_sb, const float* body_rot, int64_t rot_se,
+                          int64_t rot_sb, const float* body_vel, int64_t vel_se, int64_t vel_sb, const float* body_ang_vel,
+                          int64_t ang_se, int64_t ang_sb, const float* contact_forces, int64_t cf_se, int64_t cf_sb,
+                          const float* dof_pos, int64_t dp_se, int64_t dp_sd, const float* dof_vel, int64_t dv_se, int64_t dv_sd,
+                          int n_envs, int n_bodies, int n_dof, int local_root_obs, int root_height_obs, float* obs,
+                          int64_t ld_obs, int col_offset, float clip_obs, int task_kind, int enable_task_obs,
+                          int task_col_offset, const float* root_states, int64_t root_stride, const float* prev_root_pos,
+                          const float* tar_a, const float* tar_b, const float* tar_speed, float tar_speed_scalar,
+                          const float* tar_states, int64_t tar_stride, int reach_body_id, float dt, float* reward,
+                          int64_t* progress_buf, const float* termination_heights, const int32_t* contact_body_ids,
+                          int n_contact, const float* tar_contact_forces, int64_t tar_contact_stride,
+                          const int32_t* strike_body_ids, int n_strike, float max_episode_length,
+                          int enable_early_termination, const int32_t* recovery_counter, int64_t* reset, int64_t* terminated,
+                          float* hist, int n_steps, const int32_t* dof_offsets, int n_joints, const int32_t* key_body_ids,
+                          int n_key, void* stream);
 
 /* The whole optimizer step of every dense layer in ONE launch: weight-only gradient terms (g += c * w: discriminator
  * weight decay / logit regulariser / encoder weight decay), their reported sums of squares (pre-update weights, into

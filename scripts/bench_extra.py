@@ -19,6 +19,8 @@ rollout-time inference path.  One JSON line per measurement on stdout.
   rollout-store: what play_steps does behind env_step for one step of config 2 (4096 envs, obs 253, actions 31, amp 1400, latents
           64, dones at 1/300): the host block (some thirty torch launches and dones.nonzero's round trip) next to the one
           rollout_store call, eager and replayed from a launch program (reported, not gated)
+  env-step: one step's environment work of the strike task with an AMP history of 10 at 4096 and 16384 environments: the
+          composition of the separate entries (eager, and replayed from a launch program) and env_pre_step + env_post_step
   hrl-step: the glue of one high-level HRL step around the frozen controller's dense layers at config 4's size (4096 envs,
           llc_steps 5, obs 253 + 5 task, actions 31, amp 1400, latents 64) - the default path's per-statement launches next to
           hrl_latent once and rms_normalize / hrl_llc_action / rms_normalize / hrl_accum per inner step, eager and replayed from a
@@ -432,6 +434,121 @@ def hrl_step_case():
     be.prog_destroy(prog)
 
 
+def env_step_case():
+    """One step's environment work of the strike task with an AMP history of 10 (N14), at 4096 and 16384 environments, on seeded
+    state in the packed simulator layout, three ways on the same tensors: the composition HumanoidEnv(fused_step=False) makes of
+    the separate entries (contiguous copies, torch glue) eager; the same recorded in a launch program (its torch glue as host
+    calls); the two launches env_pre_step / env_post_step recorded.  The physics step itself and update_task (nothing for strike)
+    are left out.  The three are alternated inside every repeat and timed between two events; seven repeats of 200 steps."""
+    from ase_amd import lib as L
+    from ase_amd.amp_env import action_to_pd_targets
+    from ase_amd.backend import HipBackend
+    be = HipBackend('cuda:0')
+    dev, f32 = 'cuda:0', torch.float32
+    offs = [0, 3, 6, 9, 10, 13, 16, 17, 20, 21, 24, 27, 28, 31]
+    keys, contact, strike = [5, 8, 11, 14, 6, 9], [11, 14], [4, 5, 6, 8, 9, 10]
+    B, D, S, F, FA = 17, 31, 10, 253, 140
+    for N in (4096, 16384):
+        g = torch.Generator().manual_seed(N)
+        rnd = lambda *s: torch.randn(*s, generator=g)
+        rb = rnd(N, B + 1, 13)
+        rb[:, :, 3:7] = rb[:, :, 3:7] / rb[:, :, 3:7].norm(dim=-1, keepdim=True)
+        rb, dof, root = rb.to(dev), (rnd(N, D, 2) * 0.5).to(dev), rb[:, [0, B]].contiguous().to(dev)
+        cf = (rnd(N, B + 1, 3) * (torch.rand(N, B + 1, 1, generator=g) < 0.3)).to(dev)
+        pos, rot, vel, ang = rb[:, :B, 0:3], rb[:, :B, 3:7], rb[:, :B, 7:10], rb[:, :B, 10:13]
+        rs, ts, cfb, tcf, dp, dv = root[:, 0], root[:, 1], cf[:, :B], cf[:, B], dof[:, :, 0], dof[:, :, 1]
+        heights = torch.full((B,), 0.15, device=dev)
+        actions_in = (rnd(N, D) * 0.8).to(dev)
+        off, sc = rnd(D).to(dev), (torch.rand(D, generator=g) + 0.5).to(dev)
+
+        def buffers():
+            z = lambda *s, dt=f32: torch.zeros(*s, dtype=dt, device=dev)
+            return dict(obs=z(N, F + 15), rew=z(N), reset=z(N, dt=torch.int64), term=z(N, dt=torch.int64), prog=z(N, dt=torch.int64),
+                        hist=z(N, S, FA), acts=z(N, D), tg=z(N, D), prev=z(N, 3), cnt=z(N, dt=torch.int32))
+        u, f = buffers(), buffers()
+
+        # the composition's contiguous copies go into FIXED buffers (a replay needs stable addresses; an eager .contiguous()
+        # would allocate on top of this)
+        fixed = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in (pos, rot, vel, ang, cfb, rs, ts, tcf)]
+        amp_in = [torch.empty(N, 3, device=dev), torch.empty(N, 4, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev),
+                  torch.empty(N, D, device=dev), torch.empty(N, D, device=dev), torch.empty(N, len(keys), 3, device=dev)]
+
+        def glue_pre():
+            u['acts'].copy_(torch.clamp(actions_in, -1.0, 1.0))
+            u['tg'].copy_(action_to_pd_targets(u['acts'], off, sc))
+            u['prev'].copy_(rs[:, 0:3])
+            u['cnt'].sub_(1).clamp_min_(0)
+            u['prog'].add_(1)
+            for dst, src in zip(fixed, (pos, rot, vel, ang, cfb, rs, ts, tcf)):
+                dst.copy_(src)
+
+        def glue_amp():
+            rec = u['cnt'] > 0
+            u['reset'].masked_fill_(rec, 0)
+            u['term'].masked_fill_(rec, 0)
+            for dst, src in zip(amp_in, (pos[:, 0], rot[:, 0], vel[:, 0], ang[:, 0], dp, dv, pos[:, keys])):
+                dst.copy_(src)
+
+        def composition(glue):
+            cp, cr, cv, ca, cc, crs, cts, ctc = fixed
+            glue(glue_pre)
+            be.humanoid_obs_max(cp, cr, cv, ca, True, True, u['obs'], 0)
+            be.task_obs(L.TASK_STRIKE, u['obs'], F, None, root_states=crs, tar_states=cts)
+            be.task_reward(L.TASK_STRIKE, u['rew'], root_states=crs, prev_root_pos=u['prev'], tar_states=cts, dt=1.0 / 30.0)
+            be.humanoid_reset(u['prog'], cc, cp, heights, contact, 300.0, True, u['reset'], u['term'], ctc, strike)
+            glue(glue_amp)
+            be.build_amp_obs(*amp_in, offs, True, True, u['hist'], shift=True)
+            glue(lambda: u['obs'].clamp_(-5.0, 5.0))
+
+        def eager():
+            composition(lambda fn: fn())
+
+        def fused():
+            be.env_pre_step(actions_in, f['acts'], f['tg'], 1.0, pd_offset=off, pd_scale=sc, root_states=rs, prev_root_pos=f['prev'],
+                            recovery_counter=f['cnt'])
+            be.env_post_step(pos, rot, vel, ang, cfb, f['prog'], f['obs'], f['rew'], f['reset'], f['term'], heights, contact, 300.0, True,
+                             True, True, clip_obs=5.0, task_kind=L.TASK_STRIKE, root_states=rs, prev_root_pos=f['prev'], tar_states=ts,
+                             dt=1.0 / 30.0, tar_contact_forces=tcf, strike_body_ids=strike, recovery_counter=f['cnt'], hist=f['hist'],
+                             dof_pos=dp, dof_vel=dv, dof_offsets=offs, key_body_ids=keys)
+        eager()
+        fused()
+        torch.cuda.synchronize()
+        same = all(torch.equal(u[k], f[k]) for k in ('obs', 'rew', 'reset', 'term', 'prog', 'hist', 'acts', 'tg', 'prev', 'cnt'))
+        p_comp, p_fused = be.prog_create(), be.prog_create()
+        be.prog_begin(p_comp)
+        composition(be.host_call)
+        be.prog_end(p_comp)
+        be.prog_begin(p_fused)
+        fused()
+        be.prog_end(p_fused)
+        variants = (('env step, composition of the separate entries (eager)', eager, None),
+                    ('env step, composition of the separate entries replayed from a launch program', lambda: be.prog_launch(p_comp),
+                     be.prog_size(p_comp)),
+                    ('env step, env_pre_step + env_post_step replayed from a launch program', lambda: be.prog_launch(p_fused),
+                     be.prog_size(p_fused)))
+        times = {name: [] for name, _, _ in variants}
+        for name, fn, _ in variants:                          # warm every shape
+            for _ in range(10):
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(7):
+            for name, fn, _ in variants:
+                a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(200):
+                    fn()
+                e.record()
+                torch.cuda.synchronize()
+                times[name].append(a.elapsed_time(e) / 200 * 1e3)
+        for name, _, entries in variants:
+            reps = sorted(times[name])
+            print(json.dumps({'measurement': name, 'envs': N, 'task': 'strike', 'amp_obs_steps': S, 'program_entries': entries,
+                              'outputs_bitwise_equal': same, 'us_per_step_median': round(reps[3], 1), 'us_per_step_min': round(reps[0], 1),
+                              'us_per_step_max': round(reps[-1], 1), 'repeats': 7, 'steps_per_repeat': 200}), flush=True)
+        be.prog_destroy(p_comp)
+        be.prog_destroy(p_fused)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--updates', type=int, default=4)
@@ -530,6 +647,8 @@ def main():
         rollout_store_case()
     if not args.only or 'hrl-step' in args.only.split(','):
         hrl_step_case()
+    if not args.only or 'env-step' in args.only.split(','):
+        env_step_case()
     if not args.only or 'ampobs' in args.only.split(','):
         # N2: observation production for 4096 envs (one frame + history push) and 5120 demo samples (512 x 10 steps)
         from ase_amd.backend import HipBackend
