@@ -327,6 +327,8 @@ class HipBackend:
         n, B = body_pos.shape[0], body_pos.shape[1]
         self._f32c(body_pos, body_rot, body_vel, body_ang_vel)
         ids, n_ids = self._rows(obs, env_ids)
+        if env_ids is not None and n_ids == 0:                # an empty tensor has a null pointer, which the entry reads as "every row"
+            return
         assert obs.shape[0] >= n and body_rot.shape == (n, B, 4) and body_vel.shape == body_ang_vel.shape == body_pos.shape == (n, B, 3)
         L.check(self.lib.ase_hip_humanoid_obs_max(_ptr(body_pos), _ptr(body_rot), _ptr(body_vel), _ptr(body_ang_vel), n, B,
                                                   int(local_root_obs), int(root_height_obs), _ptr(ids), n_ids, _ptr(obs),
@@ -354,6 +356,8 @@ class HipBackend:
         """Task observation of kind L.TASK_* (5 / 2 / 3 / 15 columns, see ase_hip.h) into columns col_offset.. of obs."""
         self._f32c(root_states, tar_a, tar_b, tar_speed, tar_states)
         ids, n_ids = self._rows(obs, env_ids)
+        if env_ids is not None and n_ids == 0:                # as in humanoid_obs_max: an empty list writes nothing
+            return
         n = obs.shape[0] if root_states is None else root_states.shape[0]
         for t, cols in ((root_states, 13), (tar_a, 3 if kind == L.TASK_REACH else 2), (tar_b, 2), (tar_speed, 1), (tar_states, 13)):
             assert t is None or t.numel() == n * cols, "task_obs: operand shape"

@@ -50,6 +50,7 @@ __device__ __forceinline__ int64_t humanoid_reset_row(const ResetRule& a, int64_
         for (int b = 0; b < a.B; ++b) {
             if ((a.contact_mask >> b) & 1) continue;                                   // masked_contact_buf[:, contact_body_ids] = 0
             const float* cb = c + b * c_sb;
+            // fmaxf on purpose: the reference asks torch.any over the components, so a NaN beside a loud component does not hide it
             const float m = fmaxf(fmaxf(fabsf(cb[0]), fabsf(cb[1])), fabsf(cb[2]));
             fall_contact |= m > 0.1f;                                                  // humanoid.py:653
             fall_height |= p[b * p_sb + 2] < a.heights[b];
@@ -93,7 +94,12 @@ __device__ __forceinline__ void task_obs_row(int kind, const float* rs, const fl
 }
 
 // ---- task rewards: every constant below is the reference's literal ----------------------------------------------------
-// torch.nn.functional.normalize of a 2-vector (eps 1e-12)
+// The reference clamps with torch.clamp_min, which keeps a NaN: every clamp here is floor_nan (fmaxf would turn the NaN of a
+// simulator state that has blown up into 0 and hand the agent a plausible finite reward).  A NaN operand that reaches a
+// reward's arithmetic gives NaN; the two overrides (location: pos_err < 0.5, strike: tar_rot_err < 0.2) replace what they
+// replace in the reference, NaN included, and no comparison with a NaN is true.
+// torch.nn.functional.normalize of a 2-vector (eps 1e-12).  Both components enter every sum they are used in, so a NaN norm
+// gives a NaN result whether the bound keeps it (clamp_min) or not (fmaxf)
 __device__ __forceinline__ void normalize2(float& x, float& y) {
     const float n = fmaxf(sqrtf(x * x + y * y), 1e-12f);
     x = x / n; y = y / n;
@@ -121,7 +127,7 @@ __device__ __forceinline__ float task_reward_row(int kind, const float* rs, cons
         float dir_reward = expf(-vel_err_scale * (err * err + tangent_err_w * tangent * tangent));
         if (speed <= 0.f) dir_reward = 0.f;
         const V3 fd = facing_dir(rs);
-        const float facing_reward = fmaxf(tb[0] * fd.x + tb[1] * fd.y, 0.f);
+        const float facing_reward = floor_nan(tb[0] * fd.x + tb[1] * fd.y, 0.f);
         reward = dir_reward_w * dir_reward + facing_reward_w * facing_reward;
     } break;
     case ASE_TASK_LOCATION: {      // compute_location_reward, humanoid_location.py:185-232
@@ -132,11 +138,11 @@ __device__ __forceinline__ float task_reward_row(int kind, const float* rs, cons
         const float pos_reward = expf(-pos_err_scale * pos_err);
         normalize2(dx, dy);
         const float speed = dir_speed(rs, prev, dt, dx, dy, vx, vy);
-        const float err = fmaxf(speed_tar - speed, 0.f);
+        const float err = floor_nan(speed_tar - speed, 0.f);
         float vel_reward = expf(-vel_err_scale * (err * err));
         if (speed <= 0.f) vel_reward = 0.f;
         const V3 fd = facing_dir(rs);
-        float facing_reward = fmaxf(dx * fd.x + dy * fd.y, 0.f);
+        float facing_reward = floor_nan(dx * fd.x + dy * fd.y, 0.f);
         if (pos_err < dist_threshold) { facing_reward = 1.f; vel_reward = 1.f; }
         reward = pos_reward_w * pos_reward + vel_reward_w * vel_reward + face_reward_w * facing_reward;
     } break;
@@ -148,11 +154,11 @@ __device__ __forceinline__ float task_reward_row(int kind, const float* rs, cons
     default: {                     // compute_strike_reward, humanoid_strike.py:221-252
         const float tar_speed = 1.0f, vel_err_scale = 4.0f, tar_rot_w = 0.6f, vel_reward_w = 0.4f;               // :224-228
         const float tar_rot_err = rot(load_q(ts + 3), V3{0.f, 0.f, 1.f}).z;       // <up, target's up>
-        const float tar_rot_r = fmaxf(1.0f - tar_rot_err, 0.f);
+        const float tar_rot_r = floor_nan(1.0f - tar_rot_err, 0.f);
         float dx = ts[0] - rs[0], dy = ts[1] - rs[1];
         normalize2(dx, dy);
         const float speed = dir_speed(rs, prev, dt, dx, dy, vx, vy);
-        const float err = fmaxf(tar_speed - speed, 0.f);
+        const float err = floor_nan(tar_speed - speed, 0.f);
         float vel_reward = expf(-vel_err_scale * (err * err));
         if (speed <= 0.f) vel_reward = 0.f;
         reward = tar_rot_w * tar_rot_r + vel_reward_w * vel_reward;

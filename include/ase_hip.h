@@ -799,6 +799,12 @@ int ase_hip_task_obs(int kind, const float* root_states, const float* tar_a, con
  *   LOCATION: root_states, prev_root_pos, tar_a [n, 2], tar_speed_scalar, dt
  *   REACH   : body_pos [n, n_bodies, 3] (body_id = the reaching body), tar_a [n, 3]
  *   STRIKE  : root_states, prev_root_pos, tar_states [n, 13], dt
+ * Non-finite operands: the rewards are the reference's, NaN for NaN.  Its clamps are torch.clamp_min, which keeps a NaN, and so
+ * do the clamps here (the heading and location facing terms, the location and strike speed errors, the strike rotation
+ * term): a NaN in an operand that reaches a reward's arithmetic gives a NaN reward, never a plausible finite one.  A comparison
+ * with a NaN is false, so a NaN speed is not "<= 0", a NaN pos_err not "< 0.5", a NaN tar_rot_err not "< 0.2"; where an override
+ * holds (LOCATION: pos_err < 0.5 sets the velocity and facing terms to 1; STRIKE: tar_rot_err < 0.2 sets the reward to 1) it
+ * replaces a NaN term as it does in the reference.  REACH has no clamp: exp(-4 |tar - body|^2), NaN for NaN, 0 for an infinity.
  * Replaces: compute_heading_reward (env/tasks/humanoid_heading.py:252-289), compute_location_reward
  *   (env/tasks/humanoid_location.py:185-232), compute_reach_reward (env/tasks/humanoid_reach.py:184-196),
  *   compute_strike_reward (env/tasks/humanoid_strike.py:221-252). */

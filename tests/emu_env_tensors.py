@@ -39,6 +39,19 @@ class EmuEnvTensors:
     name = "emu-env"
     device = torch.device('cpu')
 
+    # Every comparison and clamp the reference branches on, one method each, so that tests/test_env_edges_emu.py can restate a
+    # single term wrongly and show which recorded case notices.
+    _loud = staticmethod(lambda force, threshold: force > threshold)               # |contact component| against 0.1 / 1.0
+    _low = staticmethod(lambda height, threshold: height < threshold)
+    _started = staticmethod(lambda progress: progress > 1)
+    _timed_out = staticmethod(lambda progress, max_len: progress >= max_len - 1)
+    _stopped = staticmethod(lambda speed: speed <= 0)
+    _near = staticmethod(lambda pos_err: pos_err < 0.5)
+    _upright = staticmethod(lambda rot_err: rot_err < 0.2)
+    _clamp0 = staticmethod(lambda x: x.clamp_min(0.0))                             # torch.clamp_min: a NaN stays NaN
+    _force_cols, _tar_cols = 3, 2                                                  # components of a force / of the target's that count
+    _mask_height, _strike_falls = True, True
+
     # ---- humanoid.py:592-636
     def humanoid_obs_max(self, body_pos, body_rot, body_vel, body_ang_vel, local_root_obs, root_height_obs, obs, col_offset=0,
                          env_ids=None):
@@ -67,18 +80,21 @@ class EmuEnvTensors:
         if enable_early_termination:
             keep = torch.ones(B, dtype=torch.bool, device=body_pos.device)
             keep[list(contact_body_ids)] = False
-            force = contact_forces.abs().amax(-1)                                          # [n, B]
-            fall_contact = ((force > 0.1) & keep).any(-1)
-            fall_height = ((body_pos[..., 2] < termination_heights) & keep).any(-1)
+            # any component above the threshold, not the maximum above it: a NaN beside a loud component does not hide it
+            force = contact_forces[..., :self._force_cols].abs()                           # [n, B, 3]
+            other = keep.clone()
+            if strike_body_ids is not None:
+                other[list(strike_body_ids)] = False
+            fall_contact = (self._loud(force, 0.1).any(-1) & (keep if self._strike_falls else other)).any(-1)
+            low = self._low(body_pos[..., 2], termination_heights)
+            fall_height = ((low & keep) if self._mask_height else low).any(-1)
             failed = fall_contact & fall_height
             if strike_body_ids is not None:
-                other = keep.clone()
-                other[list(strike_body_ids)] = False
-                tar_hit = (tar_contact_forces[:, 0:2].abs() > 1.0).any(-1)
-                failed = failed | (tar_hit & ((force > 1.0) & other).any(-1))
-            term = (failed & (progress_buf > 1)).to(progress_buf.dtype)
+                tar_hit = self._loud(tar_contact_forces[:, 0:self._tar_cols].abs(), 1.0).any(-1)
+                failed = failed | (tar_hit & (self._loud(force, 1.0).any(-1) & other).any(-1))
+            term = (failed & self._started(progress_buf)).to(progress_buf.dtype)
         terminated.copy_(term)
-        reset.copy_(torch.where(progress_buf >= max_episode_length - 1, torch.ones_like(term), term))
+        reset.copy_(torch.where(self._timed_out(progress_buf, max_episode_length), torch.ones_like(term), term))
 
     # ---- task observations
     def task_obs(self, kind, obs, col_offset=0, env_ids=None, root_states=None, tar_a=None, tar_b=None, tar_speed=None,
@@ -108,13 +124,12 @@ class EmuEnvTensors:
         obs[r, col_offset:col_offset + out.shape[1]] = out
 
     # ---- task rewards (the constants are the reference's literals, lines in csrc/env_obs.hip)
-    @staticmethod
-    def _speed_reward(tar_dir, root_pos, prev_root_pos, tar_speed, dt):
+    def _speed_reward(self, tar_dir, root_pos, prev_root_pos, tar_speed, dt):
         root_vel = (root_pos - prev_root_pos) / dt
         speed = (tar_dir * root_vel[:, :2]).sum(-1)
-        err = (tar_speed - speed).clamp_min(0.0)
+        err = self._clamp0(tar_speed - speed)
         r = torch.exp(-4.0 * (err * err))
-        return torch.where(speed <= 0, torch.zeros_like(r), r)
+        return torch.where(self._stopped(speed), torch.zeros_like(r), r)
 
     def task_reward(self, kind, reward, root_states=None, prev_root_pos=None, tar_a=None, tar_b=None, tar_speed=None,
                     tar_states=None, body_pos=None, body_id=0, dt=0.0):
@@ -129,10 +144,10 @@ class EmuEnvTensors:
             tangent = (root_vel[:, :2] - speed.unsqueeze(-1) * tar_a).sum(-1)
             err = tar_speed - speed
             dir_r = torch.exp(-0.25 * (err * err + 0.1 * tangent * tangent))
-            dir_r = torch.where(speed <= 0, torch.zeros_like(dir_r), dir_r)
+            dir_r = torch.where(self._stopped(speed), torch.zeros_like(dir_r), dir_r)
             ex = torch.zeros_like(root_pos); ex[:, 0] = 1
             facing = A.quat_rotate(_heading_quat(root_states[:, 3:7]), ex)
-            face_r = (tar_b * facing[:, :2]).sum(-1).clamp_min(0.0)
+            face_r = self._clamp0((tar_b * facing[:, :2]).sum(-1))
             reward.copy_(0.7 * dir_r + 0.3 * face_r)
         elif kind == L.TASK_LOCATION:
             diff = tar_a - root_pos[:, :2]
@@ -141,8 +156,8 @@ class EmuEnvTensors:
             vel_r = self._speed_reward(tar_dir, root_pos, prev_root_pos, float(tar_speed), dt)
             ex = torch.zeros_like(root_pos); ex[:, 0] = 1
             facing = A.quat_rotate(_heading_quat(root_states[:, 3:7]), ex)
-            face_r = (tar_dir * facing[:, :2]).sum(-1).clamp_min(0.0)
-            near = pos_err < 0.5
+            face_r = self._clamp0((tar_dir * facing[:, :2]).sum(-1))
+            near = self._near(pos_err)
             one = torch.ones_like(vel_r)
             reward.copy_(0.5 * torch.exp(-0.5 * pos_err) + 0.4 * torch.where(near, one, vel_r) + 0.1 * torch.where(near, one, face_r))
         else:
@@ -150,8 +165,8 @@ class EmuEnvTensors:
             rot_err = A.quat_rotate(tar_states[:, 3:7], ez)[:, 2]
             tar_dir = torch.nn.functional.normalize(tar_states[:, 0:2] - root_pos[:, :2], dim=-1)
             vel_r = self._speed_reward(tar_dir, root_pos, prev_root_pos, 1.0, dt)
-            r = 0.6 * (1.0 - rot_err).clamp_min(0.0) + 0.4 * vel_r
-            reward.copy_(torch.where(rot_err < 0.2, torch.ones_like(r), r))
+            r = 0.6 * self._clamp0(1.0 - rot_err) + 0.4 * vel_r
+            reward.copy_(torch.where(self._upright(rot_err), torch.ones_like(r), r))
 
 
 # ---- the fixture tests/golden/env_tensors.pt (scripts/make_golden_env.py) -------------------------------------------------
