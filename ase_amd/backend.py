@@ -413,6 +413,67 @@ class HipBackend:
                                             float(near_dist), float(near_prob), int(enable_rand_heading), n, self._stream()),
                 "task_reset")
 
+    # ------------------------------------------------------------------ projectile launches of the perturbation task (N15)
+    def proj_launch(self, root_states, body_pos, body_vel, proj_states, progress_buf=None, timesteps=None, slot=-1, env_ids=None,
+                    u=None, eps=None, rng_state=None, advance=True, tar_body=1, dist_min=4.0, dist_max=5.0, h_min=0.25, h_max=2.0,
+                    speed_min=30.0, speed_max=40.0, noise=0.1, slot_out=None, ids_out=None, draws_out=None):
+        """HumanoidPerturb._update_proj in one launch (operands: see ase_hip_proj_launch).  root_states f32 [n, 13], body_pos /
+        body_vel f32 [n, B, 3] and proj_states f32 [n, K, 13] are read / written in place and may be strided views with unit
+        stride in the last dimension.  slot -1: due mode on progress_buf[0] (int64 [n]) and timesteps (int32 [K']); slot >= 0:
+        that projectile, for every environment or for env_ids (int32, distinct).  The draws are passed in (u f32 [rows, 4], eps
+        f32 [rows, 3]) or made on the device from rng_state (int64 [2] = seed | offset, advanced by one unless advance is false).
+        slot_out int32 [1], ids_out int32 [n], draws_out f32 [n, 7] are optional exports.  The entry takes raw addresses: every
+        tensor lives on the backend's device.  Recordable in a launch program."""
+        f32 = torch.float32
+        tensors = dict(root_states=root_states, body_pos=body_pos, body_vel=body_vel, proj_states=proj_states, progress_buf=progress_buf,
+                       timesteps=timesteps, env_ids=env_ids, u=u, eps=eps, rng_state=rng_state, slot_out=slot_out, ids_out=ids_out,
+                       draws_out=draws_out)
+        for who, t in tensors.items():
+            assert t is None or self._here(t), f"proj_launch: {who} must be a tensor on {self.device}, not {t.device}"
+        assert root_states.dtype == f32 and root_states.dim() == 2 and root_states.shape[1] == 13 and root_states.stride(1) == 1, \
+            "proj_launch: root_states f32 [n, 13], unit column stride"
+        n = root_states.shape[0]
+        for who, t in (('body_pos', body_pos), ('body_vel', body_vel)):
+            assert t.dtype == f32 and t.dim() == 3 and t.shape[0] == n and t.shape[2] == 3 and t.stride(2) == 1, \
+                f"proj_launch: {who} f32 [n, B, 3], unit stride in the last dimension"
+        assert body_vel.shape == body_pos.shape, "proj_launch: body_vel shaped like body_pos"
+        assert proj_states.dtype == f32 and proj_states.dim() == 3 and proj_states.shape[0] == n and proj_states.shape[2] == 13 and \
+            proj_states.stride(2) == 1, "proj_launch: proj_states f32 [n, K, 13], unit stride in the last dimension"
+        K = proj_states.shape[1]
+        n_slots = K
+        if timesteps is not None:
+            assert timesteps.dtype == torch.int32 and timesteps.dim() == 1 and timesteps.is_contiguous() and 1 <= timesteps.numel() <= K, \
+                "proj_launch: timesteps int32 [n_slots], n_slots at most the projectiles of proj_states"
+            n_slots = timesteps.numel()
+        assert progress_buf is None or (progress_buf.dtype == torch.int64 and progress_buf.is_contiguous() and progress_buf.numel() == n), \
+            "proj_launch: progress_buf int64 [n]"
+        assert int(slot) < n_slots, f"proj_launch: slot {slot} beyond the {n_slots} projectiles"
+        n_ids = 0
+        if env_ids is not None:
+            assert env_ids.dtype == torch.int32 and env_ids.is_contiguous() and env_ids.dim() == 1, "proj_launch: env_ids contiguous int32"
+            n_ids = env_ids.numel()
+            if n_ids == 0 and (rng_state is None or not advance) and slot_out is None:
+                return
+        rows = n_ids if env_ids is not None else n
+        assert u is None or (u.dtype == f32 and u.shape == (rows, 4) and u.is_contiguous()), "proj_launch: u f32 [rows, 4]"
+        assert eps is None or (eps.dtype == f32 and eps.shape == (rows, 3) and eps.is_contiguous()), "proj_launch: eps f32 [rows, 3]"
+        assert rng_state is None or (rng_state.dtype == torch.int64 and rng_state.numel() == 2 and rng_state.is_contiguous()), \
+            "proj_launch: rng_state int64 [2]"
+        assert slot_out is None or (slot_out.dtype == torch.int32 and slot_out.numel() == 1), "proj_launch: slot_out int32 [1]"
+        assert ids_out is None or (ids_out.dtype == torch.int32 and ids_out.numel() == n and ids_out.is_contiguous()), \
+            "proj_launch: ids_out int32 [n]"
+        assert draws_out is None or (draws_out.dtype == f32 and draws_out.shape == (n, L.PROJ_DRAWS) and draws_out.is_contiguous()), \
+            "proj_launch: draws_out f32 [n, 7]"
+        # an empty tensor has no storage: an empty id list is still ids mode, so it gets a pointer (that is never read)
+        ids_ptr = _ptr(root_states) if env_ids is not None and n_ids == 0 else _ptr(env_ids)
+        L.check(self.lib.ase_hip_proj_launch(_ptr(progress_buf), _ptr(timesteps), n_slots, int(slot), ids_ptr, n_ids, _ptr(u), _ptr(eps),
+                                             _ptr(rng_state), int(advance), _ptr(root_states), root_states.stride(0), _ptr(body_pos),
+                                             body_pos.stride(0), body_pos.stride(1), _ptr(body_vel), body_vel.stride(0),
+                                             body_vel.stride(1), body_pos.shape[1], int(tar_body), _ptr(proj_states),
+                                             proj_states.stride(0), proj_states.stride(1), float(dist_min), float(dist_max),
+                                             float(h_min), float(h_max), float(speed_min), float(speed_max), float(noise),
+                                             _ptr(slot_out), _ptr(ids_out), _ptr(draws_out), n, self._stream()), "proj_launch")
+
     # ------------------------------------------------------------------ renewals of the ASE latents (N9)
     def latent_renew(self, latents, env_ids=None, eps=None, steps=None, rng_state=None, advance=True, progress_buf=None,
                      reset_steps=None, steps_add=False, steps_low=0, steps_high=1, z2=None):

@@ -1,15 +1,17 @@
 """The humanoid task environment on the device: the step and reset logic of the reference's ``Humanoid``,
-``HumanoidAMP``, ``HumanoidAMPGetup``, ``HumanoidHeading``, ``HumanoidLocation``, ``HumanoidReach`` and ``HumanoidStrike``
-(env/tasks/humanoid.py:361-383, humanoid_amp.py:50-59,132-139, humanoid_amp_getup.py:63-66,131-142, base/vec_task.py:90-118
-of the reference) as ONE class on a small physics protocol.  ``HumanoidEnv`` composes ``env_tensors.HumanoidTensors``,
-``amp_env.HumanoidAMPTensors``, ``amp_env.pd_action_offset_scale`` and ``motion_lib.DeviceMotionLib`` / ``AmpObsDemoSource``
-and exposes what the agents and players use of an environment (the interface of ``synthetic.SyntheticVecEnv``).
+``HumanoidAMP``, ``HumanoidAMPGetup``, ``HumanoidHeading``, ``HumanoidLocation``, ``HumanoidReach``, ``HumanoidStrike`` and
+``HumanoidPerturb`` (env/tasks/humanoid.py:361-383, humanoid_amp.py:50-59,132-139, humanoid_amp_getup.py:63-66,131-142,
+humanoid_perturb.py:149-167,172-213, base/vec_task.py:90-118 of the reference) as ONE class on a small physics protocol.
+``HumanoidEnv`` composes ``env_tensors.HumanoidTensors``, ``amp_env.HumanoidAMPTensors``, ``amp_env.pd_action_offset_scale``,
+``motion_lib.DeviceMotionLib`` / ``AmpObsDemoSource`` and ``perturb.ProjectileLauncher`` and exposes what the agents and players
+use of an environment (the interface of ``synthetic.SyntheticVecEnv``).
 
 One step is::
 
     env_pre_step   (one launch)   action clamp + copy, PD targets / forces, prev_root_pos, recovery counter
     update_task    (one launch)   the task's due targets are redrawn (it draws, so it is a launch of its own)
     physics.apply(targets, pd); physics.step()
+    proj_launch    (one launch)   perturb only: the projectile that is due by progress_buf[0] is launched (it draws too)
     env_post_step  (one launch)   progress, observation, reward, reset / terminate, AMP history, observation clip
 
 Both launches read the simulator's tensors in place, at their own strides.  With ``fused_step=False`` the same step is made
@@ -31,10 +33,18 @@ The physics protocol - what an Isaac-Gym-like binding supplies:
     step()                                  the substeps and the refresh of the state tensors
     push_state(env_ids)                     the indexed set calls (root and dof state) for int32 env_ids; a full-length list
                                             with -1 for "skip" must be accepted, so the device reset path needs no compaction
+    state['proj_states']                    perturb only: [n, K, 13], the projectiles' rows of the root-state tensor
+    push_projectiles(env_ids, slot)         perturb only: the indexed root-state set call for the projectiles of int32 env_ids
+                                            (-1: skip); slot is a device int32 word that holds the one projectile to push, or
+                                            -1 for none, and None stands for all projectiles of those environments
 
 ``PlaybackPhysics`` is the stand-in of the tests and the benchmark: it replays recorded frames in the packed simulator layout
-and invents no dynamics.  A real simulator binding, ``_generate_fall_states``, ``_update_marker``, ``humanoid_perturb``,
+and invents no dynamics.  A real simulator binding, ``_generate_fall_states``, ``_update_marker``,
 ``humanoid_view_motion``, the ``dr_randomizations`` hooks and rendering are out of scope.
+
+``perturb=True`` (or a dict of ``perturb.ProjectileLauncher`` arguments) makes the environment the reference's
+``HumanoidPerturb``: a HumanoidAMP whose ``post_physics_step`` first launches the projectile that is due - by the counter of
+environment 0, for all environments, as the reference does - and whose reset test is the timeout alone.
 """
 import math
 
@@ -43,6 +53,7 @@ import torch
 from .amp_env import HumanoidAMPTensors, action_to_pd_targets, pd_action_offset_scale
 from .env_tensors import HumanoidTensors
 from .motion_lib import AmpObsDemoSource
+from .perturb import ProjectileLauncher
 from .synthetic import _Space
 
 BODY_KEYS = ('rigid_body_pos', 'rigid_body_rot', 'rigid_body_vel', 'rigid_body_ang_vel')
@@ -68,12 +79,20 @@ class HumanoidEnv:
     resets_done_on_device = True      # reset_done(mask): what the agents' device_rollout asks of an environment
 
     def __init__(self, backend, physics, env_cfg, motion_lib=None, task=None, getup=False, fused_step=True, seed=0,
-                 clip_observations=5.0, clip_actions=1.0):
+                 clip_observations=5.0, clip_actions=1.0, perturb=None):
         """env_cfg: the ``env`` section of the reference's task yaml (its key names).  motion_lib: a ``DeviceMotionLib`` - with
         it the environment is a HumanoidAMP (history, demo fetch, reference state initialisation), without it the plain
-        Humanoid.  clip_observations / clip_actions: the task config's values (5.0 / 1.0 in the reference)."""
+        Humanoid.  clip_observations / clip_actions: the task config's values (5.0 / 1.0 in the reference).  perturb: None, True
+        or a dict of ``ProjectileLauncher`` arguments - the HumanoidPerturb class: projectiles on the reference's schedule, reset
+        by timeout only (its own compute_humanoid_reset ignores enableEarlyTermination)."""
         if task not in TASK_KEYS:
             raise ValueError(f"task must be one of {list(TASK_KEYS)}, got {task!r}")
+        if perturb is not None and perturb is not True and not isinstance(perturb, dict):
+            raise ValueError(f"perturb must be None, True or a dict of ProjectileLauncher arguments, got {perturb!r}")
+        if perturb is not None and (task is not None or getup):
+            raise ValueError("perturb is the reference's HumanoidPerturb: no task and no get-up episodes combine with it")
+        if perturb is not None and motion_lib is None:
+            raise ValueError("the perturbation task is a HumanoidAMP: it needs a motion_lib")
         cfg = dict(env_cfg)
         known = set(COMMON_KEYS) | set(TASK_KEYS[task]) | set(OFF_KEYS) | (set(GETUP_KEYS) if getup else set())
         unknown = sorted(set(cfg) - known)
@@ -99,6 +118,17 @@ class HumanoidEnv:
         if task == 'strike' and not ('target_states' in state and 'tar_contact_forces' in state):
             raise ValueError("the strike task needs target_states and tar_contact_forces in physics.state")
         self.task_name, self.getup = task, bool(getup)
+        self.launcher = None
+        if perturb is not None:
+            kw = dict(seed=seed + 3)
+            kw.update(perturb if isinstance(perturb, dict) else {})
+            self.launcher = ProjectileLauncher(backend, n, device=dev, **kw)
+            proj = state.get('proj_states')
+            if proj is None or proj.dim() != 3 or proj.shape[0] != n or proj.shape[2] != 13 or proj.shape[1] < self.launcher.n_slots:
+                raise ValueError(f"perturb needs physics.state['proj_states'] [{n}, >= {self.launcher.n_slots}, 13]"
+                                 + ("" if proj is None else f", got {tuple(proj.shape)}"))
+            if not callable(getattr(ph, 'push_projectiles', None)):
+                raise ValueError("perturb needs physics.push_projectiles(env_ids, slot)")
         self.clip_obs, self.clip_actions = float(clip_observations), float(clip_actions)
         self._pd_control, self._power_scale = bool(cfg.get('pdControl', True)), float(cfg.get('powerScale', 1.0))
         self._enable_task_obs = bool(cfg.get('enableTaskObs', True)) and task is not None
@@ -112,7 +142,8 @@ class HumanoidEnv:
                                        contact_body_ids=ph.body_ids(cfg.get('contactBodies', [])),
                                        termination_heights=cfg.get('terminationHeight', 0.15),
                                        max_episode_length=cfg.get('episodeLength', 300),
-                                       enable_early_termination=cfg.get('enableEarlyTermination', True), dt=ph.dt, device=dev,
+                                       enable_early_termination=cfg.get('enableEarlyTermination', True) and perturb is None,
+                                       dt=ph.dt, device=dev,
                                        seed=seed, **task_kw)
         self.amp = None
         if motion_lib is not None:
@@ -234,6 +265,8 @@ class HumanoidEnv:
             self.tensors.reset_task(s, ids, self.progress_buf)
             self._write_back(packed)
             self.physics.push_state(ids)
+            if self.launcher is not None:
+                self.physics.push_projectiles(ids, None)
             self._compute_observations(s, ids)
         return self._clipped_obs()
 
@@ -249,6 +282,8 @@ class HumanoidEnv:
         self.tensors.reset_task(s, plan['env_ids'], self.progress_buf)
         self._write_back(packed)
         self.physics.push_state(plan['env_ids'])
+        if self.launcher is not None:
+            self.physics.push_projectiles(plan['env_ids'], None)
         self._compute_observations(s, plan['env_ids'])
         return self._clipped_obs()
 
@@ -300,6 +335,9 @@ class HumanoidEnv:
         """-> the observation of the step (clipped).  Fused: the one launch on the physics' tensors as they are; unfused: the
         separate methods on contiguous copies, as a binding of the existing entries has to make them."""
         t, s = self.tensors, self.state
+        if self.launcher is not None:                    # _update_proj runs before progress_buf is incremented
+            self.launcher.update(s, self.progress_buf)
+            self.physics.push_projectiles(self.launcher.launch_ids, self.launcher.slot_word)
         if self.fused_step:
             self.be.env_post_step(s['rigid_body_pos'], s['rigid_body_rot'], s['rigid_body_vel'], s['rigid_body_ang_vel'],
                                   s['contact_forces'], self.progress_buf, t.obs_buf, self.rew_buf, self.reset_buf, self.terminate_buf,
@@ -336,10 +374,12 @@ class PlaybackPhysics:
     layout - ``rigid_body_state`` [T, n, bodies_per_env, 13] (position, rotation, velocity, angular velocity),
     ``dof_state`` [T, n, D, 2], ``root_states`` [T, n, actors_per_env, 13], ``contact_forces`` [T, n, bodies_per_env, 3].
     With bodies_per_env = num_bodies + 1 and two actors the last body and the second actor are the strike task's target.
-    ``state`` holds windows of the packed tensors: nothing is contiguous but by accident."""
+    ``state`` holds windows of the packed tensors: nothing is contiguous but by accident.  With num_projectiles = K > 0 the
+    last K actors are the perturbation task's projectiles, ``state['proj_states']``: they start at frame 0's rows and are not
+    played back - what a launch wrote persists - and ``push_projectiles`` records its arguments."""
 
     def __init__(self, frames, num_bodies, dof_offsets, dof_limits_lower, dof_limits_upper, motor_efforts, body_names, dt=1.0 / 30.0,
-                 device='cpu'):
+                 device='cpu', num_projectiles=0):
         dev = torch.device(device)
         self.frames = {k: v.to(torch.float32).to(dev).contiguous() for k, v in frames.items()}
         rb, dof, root, cf = (self.frames[k] for k in ('rigid_body_state', 'dof_state', 'root_states', 'contact_forces'))
@@ -355,15 +395,25 @@ class PlaybackPhysics:
                       'rigid_body_vel': p['rigid_body_state'][:, :B, 7:10], 'rigid_body_ang_vel': p['rigid_body_state'][:, :B, 10:13],
                       'dof_pos': p['dof_state'][:, :, 0], 'dof_vel': p['dof_state'][:, :, 1],
                       'humanoid_root_states': p['root_states'][:, 0], 'contact_forces': p['contact_forces'][:, :B]}
-        if rb.shape[2] > B and root.shape[2] > 1:
+        K = self.num_projectiles = int(num_projectiles)
+        assert 0 <= K < root.shape[2], "the projectiles are the last actors behind the humanoid"
+        if rb.shape[2] > B and root.shape[2] - K > 1:
             self.state['target_states'] = p['root_states'][:, 1]
             self.state['tar_contact_forces'] = p['contact_forces'][:, B]
         self.t, self.applied, self.pushed = 0, None, []
         self._load(0)
+        if K > 0:
+            self.state['proj_states'] = p['root_states'][:, root.shape[2] - K:]
+            self.state['proj_states'].copy_(root[0, :, root.shape[2] - K:])
+            self.pushed_projectiles = []
 
     def _load(self, t):
         for k, v in self.frames.items():
-            self._packed[k].copy_(v[t % self.T])
+            if k == 'root_states' and self.num_projectiles > 0:
+                A = v.shape[2] - self.num_projectiles
+                self._packed[k][:, :A].copy_(v[t % self.T][:, :A])
+            else:
+                self._packed[k].copy_(v[t % self.T])
 
     def body_ids(self, names):
         return [self._body_names.index(x) for x in names]
@@ -377,3 +427,7 @@ class PlaybackPhysics:
 
     def push_state(self, env_ids):
         self.pushed.append(env_ids)
+
+    def push_projectiles(self, env_ids, slot):
+        assert self.num_projectiles > 0, "a physics without projectiles"
+        self.pushed_projectiles.append((env_ids, slot))

@@ -45,6 +45,12 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
                                                       (change_steps, tar_a, tar_b, tar_speed, tar_states, rng_state written in place)
                                                       _reset_task / _update_task of humanoid_heading / _location / _reach and
                                                       HumanoidStrike._reset_target: new targets and change steps in one launch
+  proj_launch(root_states, body_pos, body_vel, proj_states, progress_buf, timesteps, slot, env_ids, u, eps, rng_state, advance,
+              tar_body, ranges, noise, slot_out, ids_out, draws_out) -> ()
+                                                      (proj_states, rng_state and the three exports written in place)
+                                                      HumanoidPerturb._update_proj: the schedule test on progress_buf[0], the
+                                                      draws and the projectile's root-state row in one launch
+                                                      (env/tasks/humanoid_perturb.py:172-213)
   latent_renew(latents, env_ids, eps, steps, rng_state, advance, progress_buf, reset_steps, steps_add, steps_low, steps_high, z2) -> ()
                                                       (latents, reset_steps, rng_state, z2 written in place)
                                                       ASEAgent._reset_latents + _reset_latent_step_count / _update_latents and
@@ -679,6 +685,39 @@ def task_reset(kind: str, ranges: list[float], steps_low: int, steps_high: int, 
     _check(len(ranges) == len(names), f'task_reset: {kind} takes ranges = [{", ".join(names)}]')
     _backend().task_reset(k, progress_buf, change_steps, root_states, tar_a, tar_b, tar_speed, tar_states, env_ids, u, steps, rng_state,
                           advance, steps_low, steps_high, enable_rand_heading=enable_rand_heading, **dict(zip(names, ranges)))
+
+
+@torch.library.custom_op('ase_hip::proj_launch', mutates_args=('proj_states', 'rng_state', 'slot_out', 'ids_out', 'draws_out'),
+                         device_types='cuda')
+def proj_launch(root_states: torch.Tensor, body_pos: torch.Tensor, body_vel: torch.Tensor, proj_states: torch.Tensor,
+                progress_buf: torch.Tensor | None, timesteps: torch.Tensor | None, slot: int, env_ids: torch.Tensor | None,
+                u: torch.Tensor | None, eps: torch.Tensor | None, rng_state: torch.Tensor | None, advance: bool, tar_body: int,
+                ranges: list[float], noise: float, slot_out: torch.Tensor | None, ids_out: torch.Tensor | None,
+                draws_out: torch.Tensor | None) -> None:
+    """One projectile launch of the perturbation task (operands: see ase_hip_proj_launch).  slot -1: due mode on
+    progress_buf[0] and timesteps; slot >= 0: that projectile for every environment or for env_ids.  ranges = [dist_min,
+    dist_max, h_min, h_max, speed_min, speed_max]; draws from u / eps or, on the device, from rng_state (advanced unless advance
+    is false).  Every tensor is passed by position, None where the mode has none."""
+    _check(len(ranges) == 6, 'proj_launch: ranges = [dist_min, dist_max, h_min, h_max, speed_min, speed_max]')
+    for name, t, dt in (('root_states', root_states, torch.float32), ('body_pos', body_pos, torch.float32),
+                        ('body_vel', body_vel, torch.float32), ('proj_states', proj_states, torch.float32),
+                        ('progress_buf', progress_buf, torch.int64), ('timesteps', timesteps, torch.int32),
+                        ('env_ids', env_ids, torch.int32), ('u', u, torch.float32), ('eps', eps, torch.float32),
+                        ('rng_state', rng_state, torch.int64), ('slot_out', slot_out, torch.int32), ('ids_out', ids_out, torch.int32),
+                        ('draws_out', draws_out, torch.float32)):
+        _check(t is None or t.dtype == dt, f'proj_launch: {name} must be {dt}')
+    _check(proj_states.dim() == 3 and proj_states.shape[2] == 13 and proj_states.stride(2) == 1,
+           'proj_launch: proj_states f32 [n, K, 13] with unit stride in the last dimension')
+    keys = ('dist_min', 'dist_max', 'h_min', 'h_max', 'speed_min', 'speed_max')
+    _backend().proj_launch(root_states, body_pos, body_vel, proj_states, progress_buf, timesteps, slot, env_ids, u, eps, rng_state,
+                           advance, tar_body, noise=noise, slot_out=slot_out, ids_out=ids_out, draws_out=draws_out,
+                           **dict(zip(keys, ranges)))
+
+
+@proj_launch.register_fake
+def _(root_states, body_pos, body_vel, proj_states, progress_buf, timesteps, slot, env_ids, u, eps, rng_state, advance, tar_body,
+      ranges, noise, slot_out, ids_out, draws_out):
+    return None
 
 
 @torch.library.custom_op('ase_hip::latent_renew', mutates_args=('latents', 'reset_steps', 'rng_state', 'z2'), device_types='cuda')

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id, ase_hip_rollout_store, ase_hip_hrl_latent / ase_hip_hrl_llc_action / ase_hip_hrl_accum and ase_hip_env_pre_step / ase_hip_env_post_step were added WITHOUT a new version
+/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_proj_launch, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id, ase_hip_rollout_store, ase_hip_hrl_latent / ase_hip_hrl_llc_action / ase_hip_hrl_accum and ase_hip_env_pre_step / ase_hip_env_post_step were added WITHOUT a new version
  *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
  *  load time) */
 #define ASE_HIP_ABI_VERSION 9
@@ -857,6 +857,54 @@ int ase_hip_task_reset(int kind, const int32_t* env_ids, int n_ids, const float*
                        double tar_speed_max, double tar_dist_min, double tar_dist_max, double tar_height_min,
                        double tar_height_max, double near_dist, double near_prob, int enable_rand_heading, int n_envs,
                        void* stream);
+
+/* The projectile launches of the perturbation task (an addition to ABI 9, nothing else changed):
+ * HumanoidPerturb._update_proj in ONE launch, one lane per environment (or per id), on a fixed grid, no intermediate tensor.
+ * Which slot (projectile) and which rows:
+ *   due mode      slot = -1, env_ids NULL: progress_buf (DEVICE int64, element 0 is read - the reference's semantics: the counter
+ *                 of environment 0 decides for ALL environments) and timesteps (DEVICE int32 [n_slots], the cumulative sums of the
+ *                 objects' step counts, strictly increasing and positive) are read when the launch runs: t = progress_buf[0] mod
+ *                 (timesteps[n_slots - 1] + 1), the launched slot is the first k with timesteps[k] == t.  Without such a k
+ *                 nothing is written but slot_out = -1 and ids_out[e] = -1.  No host read, no nonzero, no where.
+ *   explicit mode 0 <= slot < n_slots from the caller (progress_buf, timesteps NULL), for every environment or for the rows
+ *                 env_ids (DEVICE int32 [n_ids], DISTINCT); ids outside [0, n_envs) are skipped and never dereferenced.
+ *   n_slots in 1 .. 32.
+ * Where the seven draws of a row come from - exactly one source:
+ *   u, eps    f32 [rows, 4] uniforms {theta, distance, height, speed} and f32 [rows, 3] normals (the direction noise), both
+ *             contiguous; rows = n_ids with env_ids (row i belongs to env_ids[i]), else n_envs.
+ *   rng_state u64[2] = {seed, offset} on the device, as in ase_hip_task_reset.  Draw j of environment e comes from element
+ *             8 e + j of the stream and depends on (seed, offset, e) only ("uniform": the 24-bit uniform (c[2] >> 8) * 2^-24 of
+ *             the element, "normal": its Box-Muller normal from words 0 and 1, as in ase_hip_sample_latents):
+ *               j = 0  uniform  theta = (float)(2 pi) u
+ *               j = 1  uniform  distance = (float)(dist_max - dist_min) u + dist_min
+ *               j = 2  uniform  height = (float)(h_max - h_min) u + h_min
+ *               j = 3 .. 5  normal   the noise of the launch direction x, y, z
+ *               j = 6  uniform  speed = (float)(speed_max - speed_min) u + speed_min
+ *             advance != 0: the offset moves on by one behind the launch, whether or not a launch was due (a call is one
+ *             stream position).
+ *   draws_out (nullable) f32 [n_envs, 7]: row e receives the draws of a launched environment e in the order j = 0 .. 6.
+ * What a launched row writes, f32 operation by operation in the reference's order (range differences taken in double and rounded
+ * once; sinf / cosf / sqrtf), into proj_states + e * ld_env + slot * ld_slot (13 floats; ld_env, ld_slot >= 13):
+ *   p = {root x + distance cos(theta), root y + (-distance) sin(theta), height}              columns 0:3
+ *   columns 3:6 = 0, column 6 = 1, columns 10:13 = 0
+ *   d = (target body position - p) + (float)noise * normals; d / max(|d|, 1e-12) (F.normalize: a NaN stays a NaN)
+ *   velocity = speed * d, + the target body's velocity in x and y only                             columns 7:10
+ * Operands are read in place from the simulator's layout: root_states row e at + e * ld_root (ld_root >= 13); the target body's
+ * position at body_pos + e * pos_se + tar_body * pos_sb, its velocity at body_vel + e * vel_se + tar_body * vel_sb (strides in
+ * floats, >= 3; tar_body in [0, n_bodies); the reference hard-codes body 1).  Every other slot, actor and row is untouched.
+ * Outputs besides the row (nullable): slot_out int32 [1], the launched slot or -1; ids_out int32 [n_envs] (not with env_ids),
+ * EVERY element written: e where environment e launched, -1 elsewhere - the full-length id list of ase_hip_rollout_store /
+ * ase_hip_amp_reset_due, here for the simulator's indexed root-state set call.
+ * Replaces: HumanoidPerturb._update_proj (env/tasks/humanoid_perturb.py:172-213) but its set_actor_root_state_tensor_indexed. */
+#define ASE_PROJ_DRAWS 7
+#define ASE_PROJ_MAX_SLOTS 32
+int ase_hip_proj_launch(const int64_t* progress_buf, const int32_t* timesteps, int n_slots, int slot, const int32_t* env_ids,
+                        int n_ids, const float* u, const float* eps, uint64_t* rng_state, int advance, const float* root_states,
+                        int64_t ld_root, const float* body_pos, int64_t pos_se, int64_t pos_sb, const float* body_vel,
+                        int64_t vel_se, int64_t vel_sb, int n_bodies, int tar_body, float* proj_states, int64_t ld_env,
+                        int64_t ld_slot, double dist_min, double dist_max, double h_min, double h_max, double speed_min,
+                        double speed_max, double noise, int32_t* slot_out, int32_t* ids_out, float* draws_out, int n_envs,
+                        void* stream);
 
 /* Renewals of the ASE agent's per-environment latents (an addition to ABI 9, nothing else changed): new unit
  * latents and new step counts for the selected environments, in ONE launch, one wave per row (lanes j and j + 64 hold the

@@ -25,6 +25,9 @@ rollout-time inference path.  One JSON line per measurement on stdout.
           llc_steps 5, obs 253 + 5 task, actions 31, amp 1400, latents 64) - the default path's per-statement launches next to
           hrl_latent once and rms_normalize / hrl_llc_action / rms_normalize / hrl_accum per inner step, eager and replayed from a
           launch program; the dense layers and the environment are left out of both (reported, not gated)
+  perturb: one _update_proj of the perturbation task at 4096 environments on a step that is not due and on a due step: the
+          reference-style torch composition with its progress_buf.cpu() read next to one ProjectileLauncher.update call, eager
+          and replayed from a launch program (reported, not gated)
   infer : get_action_values (eval-mode normalisation + actor + critic forward + sample) on 4096 observations
 """
 import argparse
@@ -345,6 +348,86 @@ def rollout_store_case():
     be.prog_destroy(prog)
 
 
+def perturb_case():
+    """HumanoidPerturb._update_proj at 4096 environments, 13 projectiles behind one actor, three ways on the same tensors, on a
+    step that is not due (progress_buf[0] = 59) and on a due step (60).  The torch composition is the reference's statements
+    (env/tasks/humanoid_perturb.py:172-213) on the device, its host read of progress_buf included.  Timed as rollout_store_case:
+    seven repeats of 100 calls, median and spread."""
+    import numpy as np
+    from ase_amd.backend import HipBackend
+    from ase_amd.perturb import PERTURB_OBJS, ProjectileLauncher
+    be = HipBackend('cuda:0')
+    g = torch.Generator().manual_seed(0)
+    N, A, B, dev = 4096, 14, 15, 'cuda:0'
+    K = len(PERTURB_OBJS)
+    root_states = torch.randn(N * A, 13, generator=g).to(dev)
+    rb = torch.randn(N, B, 13, generator=g).to(dev)
+    view = root_states.view(N, A, 13)
+    humanoid_root_states, proj_states = view[:, 0], view[:, A - K:]
+    rigid_body_pos, rigid_body_vel = rb[..., 0:3], rb[..., 7:10]
+    progress_buf = torch.zeros(N, dtype=torch.int64, device=dev)
+    perturb_timesteps = np.cumsum(PERTURB_OBJS)
+
+    def torch_update():
+        curr_timestep = progress_buf.cpu().numpy()[0]
+        curr_timestep = curr_timestep % (perturb_timesteps[-1] + 1)
+        perturb_step = np.where(perturb_timesteps == curr_timestep)[0]
+        if len(perturb_step) > 0:
+            perturb_id = perturb_step[0]
+            n = N
+            humanoid_root_pos = humanoid_root_states[..., 0:3]
+            rand_theta = torch.rand([n], dtype=proj_states.dtype, device=proj_states.device)
+            rand_theta *= 2 * np.pi
+            rand_dist = (5 - 4) * torch.rand([n], dtype=proj_states.dtype, device=proj_states.device) + 4
+            pos_x = rand_dist * torch.cos(rand_theta)
+            pos_y = -rand_dist * torch.sin(rand_theta)
+            pos_z = (2 - 0.25) * torch.rand([n], dtype=proj_states.dtype, device=proj_states.device) + 0.25
+            proj_states[..., perturb_id, 0] = humanoid_root_pos[..., 0] + pos_x
+            proj_states[..., perturb_id, 1] = humanoid_root_pos[..., 1] + pos_y
+            proj_states[..., perturb_id, 2] = pos_z
+            proj_states[..., perturb_id, 3:6] = 0.0
+            proj_states[..., perturb_id, 6] = 1.0
+            launch_tar_pos = rigid_body_pos[..., 1, :]
+            launch_dir = launch_tar_pos - proj_states[..., perturb_id, 0:3]
+            launch_dir += 0.1 * torch.randn_like(launch_dir)
+            launch_dir = torch.nn.functional.normalize(launch_dir, dim=-1)
+            launch_speed = (40 - 30) * torch.rand_like(launch_dir[:, 0:1]) + 30
+            launch_vel = launch_speed * launch_dir
+            launch_vel[..., 0:2] += rigid_body_vel[..., 1, 0:2]
+            proj_states[..., perturb_id, 7:10] = launch_vel
+            proj_states[..., perturb_id, 10:13] = 0.0
+
+    la = ProjectileLauncher(be, N, device=dev)
+    state = dict(humanoid_root_states=humanoid_root_states, rigid_body_pos=rigid_body_pos, rigid_body_vel=rigid_body_vel,
+                 proj_states=proj_states)
+    prog = be.prog_create()
+    be.prog_begin(prog)
+    la.update(state, progress_buf)
+    be.prog_end(prog)
+
+    def timeit(fn, calls=100):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(calls):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / calls * 1e3
+    for p0, what in ((59, 'not due'), (60, 'due')):
+        progress_buf[0] = p0
+        for name, fn in (('torch composition with the progress_buf.cpu() read', torch_update),
+                         ('one ProjectileLauncher.update call', lambda: la.update(state, progress_buf)),
+                         ('one ProjectileLauncher.update call replayed from a launch program', lambda: be.prog_launch(prog))):
+            reps = sorted(timeit(fn) for _ in range(7))
+            print(json.dumps({'measurement': f'perturb _update_proj, {what} step, {name}', 'envs': N, 'projectiles': K,
+                              'progress_buf0': p0, 'us_per_call_median': round(reps[3], 1), 'us_per_call_min': round(reps[0], 1),
+                              'us_per_call_max': round(reps[-1], 1), 'repeats': 7, 'calls_per_repeat': 100}), flush=True)
+    be.prog_destroy(prog)
+
+
 def hrl_step_case():
     """The glue of one high-level step of config 4 (HRLAgent.env_step around the LLC's dense layers and vec_env.step), both ways on
     the same tensors: the default path's statements (ForwardEngine.policy_forward / amp_heads / _calc_disc_rewards and the torch
@@ -645,6 +728,8 @@ def main():
         amp_reset_case()
     if not args.only or 'rollout-store' in args.only.split(','):
         rollout_store_case()
+    if not args.only or 'perturb' in args.only.split(','):
+        perturb_case()
     if not args.only or 'hrl-step' in args.only.split(','):
         hrl_step_case()
     if not args.only or 'env-step' in args.only.split(','):
