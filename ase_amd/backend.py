@@ -37,6 +37,7 @@ def _code(dtype):
 class HipBackend:
     name = "hip"
     nt_fused_epilogue = True     # gemm_nt(seed=, twin=, sq=): UpdateEngine's engine_opts gp_fuse needs it
+    nt_stack = True              # gemm_nt(stack=) and disc_head(gp_add=): UpdateEngine's engine_opts gp_stack needs them
 
     def __init__(self, device=None, x3=False):
         # x3: f32-stored GEMM operands are multiplied as three 16-bit MFMAs on a hi/lo split - True: bf16 parts (ASE_F32X3, any
@@ -130,8 +131,11 @@ class HipBackend:
     # ------------------------------------------------------------------ GEMMs
     def gemm_nt(self, A, B, Cm, M, N, K, bias=None, aux=None, aux_mode=L.AUX_NONE, colsum=None, colsum_n=0,
                 act=L.ACT_NONE, alpha=1.0, aux_split=0, aux_delta=0, mask_out=None, x3_exps=None, alpha_dev=None,
-                seed=None, twin=None, sq=None, store=True):
-        """seed / twin / sq (nt_fused_epilogue; ASE_F32H3 launches only - ase_hip_gemm_nt_ex): duties of the launch's epilogue that
+                seed=None, twin=None, sq=None, store=True, stack=None):
+        """stack = (split, aux2, alpha2, alpha_dev2) (nt_stack; ase_hip_gemm_nt_stacked): rows [split, M) are a second row block with
+        duties of its own - no bias, activation or mask_out, scale alpha2 / alpha_dev2, the optional bit mask aux2 [M - split, N / 32]
+        read at row m - split; bias, act, mask_out (its first `split` rows), alpha and alpha_dev then belong to rows [0, split) alone.
+        seed / twin / sq (nt_fused_epilogue; ASE_F32H3 launches only - ase_hip_gemm_nt_ex): duties of the launch's epilogue that
         were launches of their own.  seed = (w f32[n], scale): store scale * w[col] * [act(z) > 0] instead of the activation (gp_seed);
         twin = a 16-bit tensor that receives the stored values once more (the conversion of gather_multi; store=False with a twin: Cm
         names the shape only and is NOT written);
@@ -163,6 +167,16 @@ class HipBackend:
                                                 _ptr(dyn), self._stream()), "gemm_nt_ex")
             return
         out_f32 = int(Cm.dtype == torch.float32 and A.dtype != torch.float32)
+        if stack is not None:
+            split, aux2, alpha2, alpha_dev2 = stack
+            assert aux is None and aux_mode == L.AUX_NONE and colsum is None, "a stacked launch takes its mask operand in stack=(...)"
+            assert aux2 is None or aux2.dtype == torch.int32
+            L.check(self.lib.ase_hip_gemm_nt_stacked(_ptr(A), _ld(A), _ptr(B), _ld(B), _ptr(Cm), _ld(Cm), _ptr(bias), _ptr(aux2),
+                                                     _ld(aux2), int(split), int(split), None, 0, _ptr(mask_out), _ld(mask_out),
+                                                     M, N, K, act, L.AUX_NONE if aux2 is None else L.AUX_RELU_BITS, out_f32,
+                                                     float(alpha), _ptr(alpha_dev), int(split), float(alpha2), _ptr(alpha_dev2), dt,
+                                                     self._stream()), "gemm_nt_stacked")
+            return
         L.check(self.lib.ase_hip_gemm_nt(_ptr(A), _ld(A), _ptr(B), _ld(B), _ptr(Cm), _ld(Cm), _ptr(bias), _ptr(aux),
                                          _ld(aux), int(aux_split), int(aux_delta), _ptr(colsum), int(colsum_n),
                                          _ptr(mask_out), _ld(mask_out), M, N, K, act, aux_mode, out_f32,
@@ -1001,10 +1015,12 @@ class HipBackend:
             self._head_scratch_ls = torch.zeros(L.PPO_SCRATCH_LS, dtype=torch.float64, device=self.device)
         return self._head_scratch_ls
 
-    def disc_head(self, logit, d_logit, db_logit, acc, amb, amb_global, disc_coef, grad_scale=1.0, dyn=None):
-        L.check(self.lib.ase_hip_disc_head(_ptr(logit), _ld(logit), _ptr(d_logit), _ld(d_logit), _ptr(db_logit),
-                                           _ptr(acc), amb, amb_global, float(disc_coef), float(grad_scale), _ptr(dyn),
-                                           _code(d_logit.dtype), self._stream()), "disc_head")
+    def disc_head(self, logit, d_logit, db_logit, acc, amb, amb_global, disc_coef, grad_scale=1.0, dyn=None, gp_add=None):
+        """gp_add (nt_stack): an f64 cell added into acc[ACC_GP] by this launch (the stacked penalty schedule's sum of squares)."""
+        assert gp_add is None or gp_add.dtype == torch.float64
+        L.check(self.lib.ase_hip_disc_head_v2(_ptr(logit), _ld(logit), _ptr(d_logit), _ld(d_logit), _ptr(db_logit),
+                                              _ptr(acc), amb, amb_global, float(disc_coef), float(grad_scale), _ptr(dyn),
+                                              _ptr(gp_add), _code(d_logit.dtype), self._stream()), "disc_head")
 
     def enc_head(self, e, z, d_e, db_enc, enc_out, acc, amb, amb_global, z_dim, enc_coef, grad_scale=1.0, dyn=None):
         L.check(self.lib.ase_hip_enc_head(_ptr(e), _ld(e), _ptr(z), _ld(z), _ptr(d_e), _ld(d_e), _ptr(db_enc),

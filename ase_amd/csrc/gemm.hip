@@ -58,10 +58,11 @@ struct NTFused {
     bool any() const { return seed_w || twin || sq_acc; }
 };
 
-int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
-                 const float* bias, const void* aux, int64_t ldaux, int aux_split, int aux_delta,
-                 float* colsum, int colsum_n, void* mask_out, int64_t ldmask, int M, int N, int K, int act,
-                 int aux_mode, int out_f32, float alpha, float* alpha_dev, int dtype_word, const NTFused& fu, void* stream) {
+// argument checks of an NT launch and its parameter block
+int nt_fill(NTParams& p, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+            const float* bias, const void* aux, int64_t ldaux, int aux_split, int aux_delta,
+            float* colsum, int colsum_n, void* mask_out, int64_t ldmask, int M, int N, int K, int act,
+            int aux_mode, int out_f32, float alpha, float* alpha_dev, int dtype_word, const NTFused& fu) {
     const int dtype = dtype_word & 0xFF, ea = (dtype_word >> 8) & 0xFF, eb = (dtype_word >> 16) & 0xFF;
     const int es = ase_elem_size(dtype);
     ASE_CHECK_ARG(dtype == ASE_F32 || dtype == ASE_BF16 || dtype == ASE_F32X3 || dtype == ASE_F16 || dtype == ASE_F32H3,
@@ -98,7 +99,6 @@ int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, void* C
                   "gemm_nt: mask_out needs N %% 32 == 0 and ldmask >= N / 32 words");
     ASE_CHECK_ARG(mask_out == nullptr || !smooth || (ldmask >= N && ((uintptr_t)mask_out % 16) == 0 && (ldmask * es) % 8 == 0),
                   "gemm_nt: the pre-activation twin needs ldmask >= N elements, 16-byte alignment");
-    NTParams p;
     p.A = (const char*)A; p.lda = lda * es;
     p.B = (const char*)B; p.ldb = ldb * es;
     p.C = (char*)C; p.ldc = ldc * (out_f32 ? 4 : es);
@@ -113,14 +113,27 @@ int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, void* C
     p.seed_w = fu.seed_w; p.seed_n = fu.seed_n; p.seed_scale = fu.seed_scale;
     p.twin = (char*)fu.twin; p.ldtwin = fu.ldtwin * 2; p.twin_dtype = fu.twin_dtype;
     p.sq_acc = fu.sq_acc; p.sq_scale = fu.sq_scale; p.sq_dyn = fu.sq_dyn;
-    if (dtype == ASE_BF16) return dispatch_nt_bf16(p, (hipStream_t)stream);
-    if (dtype == ASE_F16) return dispatch_nt_f16(p, (hipStream_t)stream);
-    if (dtype == ASE_F32X3) return dispatch_nt_x3(p, (hipStream_t)stream);
+    p.stack_split = 0; p.alpha2 = 0.f; p.alpha_dev2 = nullptr;
     if (dtype == ASE_F32H3) {
         p.sa = ldexpf(1.f, ea);            // (B: pre-split and scaled by 2^eb by ase_hip_refresh_shadow)
         p.alpha = ldexpf(alpha, -(ea + eb));          // exact: powers of two
-        return dispatch_nt_h3(p, (hipStream_t)stream);
     }
+    return ASE_OK;
+}
+
+int gemm_nt_impl(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                 const float* bias, const void* aux, int64_t ldaux, int aux_split, int aux_delta,
+                 float* colsum, int colsum_n, void* mask_out, int64_t ldmask, int M, int N, int K, int act,
+                 int aux_mode, int out_f32, float alpha, float* alpha_dev, int dtype_word, const NTFused& fu, void* stream) {
+    NTParams p;
+    if (const int rc = nt_fill(p, A, lda, B, ldb, C, ldc, bias, aux, ldaux, aux_split, aux_delta, colsum, colsum_n, mask_out, ldmask, M, N, K,
+                               act, aux_mode, out_f32, alpha, alpha_dev, dtype_word, fu))
+        return rc;
+    const int dtype = dtype_word & 0xFF;
+    if (dtype == ASE_BF16) return dispatch_nt_bf16(p, (hipStream_t)stream);
+    if (dtype == ASE_F16) return dispatch_nt_f16(p, (hipStream_t)stream);
+    if (dtype == ASE_F32X3) return dispatch_nt_x3(p, (hipStream_t)stream);
+    if (dtype == ASE_F32H3) return dispatch_nt_h3(p, (hipStream_t)stream);
     return dispatch_nt_f32(p, (hipStream_t)stream);
 }
 
@@ -146,4 +159,39 @@ extern "C" int ase_hip_gemm_nt_ex(const void* A, int64_t lda, const void* B, int
     fu.sq_acc = sq_acc; fu.sq_scale = sq_scale; fu.sq_dyn = sq_dyn;
     return gemm_nt_impl(A, lda, B, ldb, C, ldc, bias, aux, ldaux, aux_split, aux_delta, colsum, colsum_n, mask_out, ldmask, M, N, K,
                         act, aux_mode, out_f32, alpha, alpha_dev, dtype_word, fu, stream);
+}
+
+// The stacked form: rows [0, split) and [split, M) of ONE A / C pair with an epilogue each.  Native: one launch of the phased 256 x 256
+// kernel's stacked instantiation when that is the kernel of the whole shape and split falls on a tile boundary; everything else is the two
+// plain launches, issued here.
+extern "C" int ase_hip_gemm_nt_stacked(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                                       const float* bias, const void* aux, int64_t ldaux, int aux_split, int aux_delta,
+                                       float* colsum, int colsum_n, void* mask_out, int64_t ldmask, int M, int N, int K, int act,
+                                       int aux_mode, int out_f32, float alpha, float* alpha_dev, int split, float alpha2,
+                                       float* alpha_dev2, int dtype_word, void* stream) {
+    ASE_CHECK_ARG(M > 0 && split > 0 && split < M, "gemm_nt_stacked: split=%d outside (0, M=%d)", split, M);
+    ASE_CHECK_ARG(colsum == nullptr && out_f32 == 0, "gemm_nt_stacked: neither row block takes column sums or an f32 output");
+    ASE_CHECK_ARG(act == ASE_ACT_NONE || act == ASE_ACT_RELU, "gemm_nt_stacked: the first block's activation is NONE or RELU, not %d", act);
+    ASE_CHECK_ARG(mask_out == nullptr || act == ASE_ACT_RELU, "gemm_nt_stacked: mask_out only behind ReLU");
+    ASE_CHECK_ARG(aux_mode == ASE_AUX_NONE || aux_mode == ASE_AUX_RELU_BITS, "gemm_nt_stacked: the mask operand is a bit matrix, not mode %d",
+                  aux_mode);
+    ASE_CHECK_ARG(aux_mode == ASE_AUX_NONE || (aux_split == split && aux_delta == split),
+                  "gemm_nt_stacked: the mask operand belongs to the second block alone (aux_split = aux_delta = split)");
+    const int dtype = dtype_word & 0xFF, es = ase_elem_size(dtype);
+    // the whole shape's checks first: nothing is launched for arguments either half would refuse
+    NTParams p;
+    if (const int rc = nt_fill(p, A, lda, B, ldb, C, ldc, bias, aux, ldaux, 0, 0, nullptr, 0, mask_out, ldmask, M, N, K, act, aux_mode, 0,
+                               alpha, alpha_dev, dtype_word, NTFused{}))
+        return rc;
+    const bool fits32 = (int64_t)M * p.lda < (int64_t)0x7FFFFFFF && (int64_t)N * p.ldb < (int64_t)0x7FFFFFFF;
+    if ((dtype == ASE_BF16 || dtype == ASE_F16) && split % 256 == 0 && M < 65536 && fits32 && nt_choice(M, N, K, es, true) == 2) {
+        p.stack_split = split; p.alpha2 = alpha2; p.alpha_dev2 = alpha_dev2;
+        return dtype == ASE_F16 ? dispatch_nt_stacked_f16(p, (hipStream_t)stream) : dispatch_nt_stacked_bf16(p, (hipStream_t)stream);
+    }
+    if (const int rc = gemm_nt_impl(A, lda, B, ldb, C, ldc, bias, nullptr, 0, 0, 0, nullptr, 0, mask_out, ldmask, split, N, K, act, ASE_AUX_NONE,
+                                    0, alpha, alpha_dev, dtype_word, NTFused{}, stream))
+        return rc;
+    return gemm_nt_impl((const char*)A + (int64_t)split * lda * es, lda, B, ldb, (char*)C + (int64_t)split * ldc * es, ldc, nullptr, aux, ldaux,
+                        0, 0, nullptr, 0, nullptr, 0, M - split, N, K, ASE_ACT_NONE, aux_mode, 0, alpha2, alpha_dev2, dtype_word, NTFused{},
+                        stream);
 }

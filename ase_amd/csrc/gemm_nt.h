@@ -54,6 +54,12 @@ struct NTParams {
     char* twin; int64_t ldtwin; int twin_dtype;          // nullable: the stored value once more, from_f32<f16 / bf16> (ldtwin in bytes);
                                                          // with a twin C may be null (no f32 store)
     double* sq_acc; double sq_scale; const float* sq_dyn;   // nullable: *sq_acc += sq_scale * sq_dyn[0] * sum of the stored values' squares
+    // ---- stacked form (ase_hip_gemm_nt_stacked; the STK instantiation of gemm_nt8_kernel reads them, nobody else): rows >= stack_split
+    // are a second row block with duties of its own - no bias, no activation, no mask_out, alpha2 / alpha_dev2 - and they alone take
+    // the mask operand (aux / aux_mode, read at row m - stack_split); bias, act, mask_out, alpha, alpha_dev belong to the first block
+    int stack_split;
+    float alpha2;
+    float* alpha_dev2;
 };
 
 
@@ -342,5 +348,8 @@ int dispatch_nt_f16(const NTParams& p, hipStream_t s);
 int dispatch_nt_f32(const NTParams& p, hipStream_t s);
 int dispatch_nt_x3(const NTParams& p, hipStream_t s);      // f32s_t: three bf16 MFMAs per product
 int dispatch_nt_h3(const NTParams& p, hipStream_t s);      // f32h_t: three f16 MFMAs per product, scaled operands
+// stacked form, ONE launch of the phased 256 x 256 kernel (the caller, ase_hip_gemm_nt_stacked, has checked that the shape takes it)
+int dispatch_nt_stacked_bf16(const NTParams& p, hipStream_t s);
+int dispatch_nt_stacked_f16(const NTParams& p, hipStream_t s);
 
 }  // namespace ase_nt

@@ -869,14 +869,21 @@ __device__ __forceinline__ void nt8_ktile(int t, int nk, const NT8Lane& L, const
 // row counts whose 256-row tiling leaves a quarter of the CUs idle (12288 x 1024: 192 tiles of 256 rows, 256 tiles of 192).  The
 // K-tile buffers keep their 64-KiB stride and B keeps following A (offset BM * 128); unit A1 covers rows 64-95 of BOTH wave rows
 // with one piece, its second piece repeats the first (same bytes, same place) so that the counted waits stay what they are.
-template <typename T, bool SW, int BM = 256>
+// STK (SW, 256-row tiles): the stacked form - two row blocks with an epilogue each in one launch.  stack_split is a multiple of the tile's
+// 256 rows, so every workgroup lies wholly in one block and takes that block's duties at its entry by rewriting the (scalar) parameter
+// fields; nothing further down knows about it, except that the mask operand has M - stack_split rows.  An instantiation of its own:
+// every other launch keeps its registers.
+template <typename T, bool SW, int BM = 256, bool STK = false>
 __global__ __launch_bounds__(512) void gemm_nt8_kernel(NTParams p) {
     static_assert(sizeof(T) == 2, "the phased kernel takes the 16-bit storage types");
     static_assert(BM == 256 || (BM == 192 && SW), "192-row tiles come with the row-per-lane epilogue");
+    static_assert(!STK || (SW && BM == 256), "the stacked form comes with the row-per-lane epilogue on 256-row tiles");
     constexpr int RB = 128, BN = 256, BK = 64, WM = BM / 2, NI = WM / 32;
     constexpr int kBuf = 512 * RB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (p.alpha_dev) p.alpha *= *p.alpha_dev;
+    if constexpr (!STK) {
+        if (p.alpha_dev) p.alpha *= *p.alpha_dev;
+    }
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -884,6 +891,18 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(NTParams p) {
     const int nwg = p.tiles_m * p.tiles_n;
     const int tile = xcd_remap(blockIdx.x, nwg);
     const int bm0 = (tile / p.tiles_n) * BM, bn0 = (tile % p.tiles_n) * BN;
+    if constexpr (STK) {
+        if (bm0 >= p.stack_split) {          // workgroup-uniform: the second block's duties
+            p.bias = nullptr;
+            p.act = ASE_ACT_NONE;
+            p.mask_out = nullptr;
+            p.alpha = p.alpha2;
+            p.alpha_dev = p.alpha_dev2;
+        } else {
+            p.aux_mode = ASE_AUX_NONE;       // the mask operand belongs to the second block
+        }
+        if (p.alpha_dev) p.alpha *= *p.alpha_dev;
+    }
 
     NT_PROF_STAMP(p.prof, tid, blockIdx.x * 4 + 0, false);
     NT8Lane L;
@@ -951,8 +970,10 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(NTParams p) {
 #pragma unroll
             for (int i = 0; i < NI; ++i) {
                 const int m = bm0 + wr * WM + i * 32 + (lane & 31);
-                const int ma = (m >= p.aux_split) ? m - p.aux_delta : m;
-                const uint32_t* w = reinterpret_cast<const uint32_t*>(p.aux + (int64_t)min(ma, p.M - 1) * p.ldaux) +
+                int ma;
+                if constexpr (STK) ma = min(m, p.M - 1) - p.stack_split;     // (the mask has M - stack_split rows: clamp FIRST)
+                else ma = min((m >= p.aux_split) ? m - p.aux_delta : m, p.M - 1);
+                const uint32_t* w = reinterpret_cast<const uint32_t*>(p.aux + (int64_t)ma * p.ldaux) +
                                     ((bn0 + wc * 64) >> 5) + (lane >> 5);
                 __builtin_amdgcn_global_load_lds((gptr_t*)w, (lptr_t*)(mlds + i * 256), 4, 0, 0);
             }
@@ -1003,9 +1024,9 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(NTParams p) {
     NT_PROF_CLOSE(p.prof, tid, blockIdx.x * 4 + 3);
 }
 
-template <typename T, bool SW = false, int BM = 256> int launch_nt8(const NTParams& p0, hipStream_t stream) {
+template <typename T, bool SW = false, int BM = 256, bool STK = false> int launch_nt8(const NTParams& p0, hipStream_t stream) {
     constexpr int lds = 2 * 512 * 128 + (SW ? 8 * 1024 : 0);     // ring + (row-per-lane epilogue) 1 KiB of mask words per wave
-    constexpr auto kern = gemm_nt8_kernel<T, SW, BM>;
+    constexpr auto kern = gemm_nt8_kernel<T, SW, BM, STK>;
     if (const int rc = ase_dynamic_lds<kern>("gemm_nt8", lds)) return rc;
     NTParams p = p0;
     p.prof = g_nt_prof;
@@ -1088,5 +1109,9 @@ template <typename T> int dispatch_nt(const NTParams& p, hipStream_t s) {
             return launch_nt<T, 2, 2, 2, 2, 64, 4>(p, s);                 // 64-byte rows, 4-stage ring (64 KB)
     }
 }
+
+// the stacked form as ONE launch (ase_hip_gemm_nt_stacked has checked: kernel 2 of a 16-bit shape, stack_split in whole 256-row tiles,
+// operands a 32-bit byte offset reaches, fewer than 65536 rows)
+template <typename T> int dispatch_nt_stacked(const NTParams& p, hipStream_t s) { return launch_nt8<T, true, 256, true>(p, s); }
 
 }  // namespace

@@ -276,7 +276,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void disc_head_kernel(const float* __restrict__ logit, int64_t ld_l, T* __restrict__ d_logit,
                                                         int64_t ld_d, float* __restrict__ db_logit, double* __restrict__ acc,
                                                         int amb, int amb_global, float disc_coef, float gs,
-                                                        float* __restrict__ gs_dev) {
+                                                        float* __restrict__ gs_dev, const double* __restrict__ gp_add) {
     __shared__ double sm[5 * 16];
     if (gs_dev) gs *= *gs_dev;
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -310,6 +310,8 @@ __global__ __launch_bounds__(256) void disc_head_kernel(const float* __restrict_
         atomic_add_f64(acc + ASE_ACC_BCE_DEMO, part[1]);
         atomic_add_f64(acc + ASE_ACC_AGENT_ACC, part[2]);
         atomic_add_f64(acc + ASE_ACC_DEMO_ACC, part[3]);
+        // the penalty's sum of squares, formed in a cell of the branch's own before the step's accumulators were zeroed
+        if (gp_add && blockIdx.x == 0) atomic_add_f64(acc + ASE_ACC_GP, *gp_add);
     }
 }
 
@@ -680,20 +682,28 @@ extern "C" int ase_hip_ppo_head(const float* mu, int64_t ld_mu, const float* val
     return ASE_OK;
 }
 
-extern "C" int ase_hip_disc_head(const float* logit, int64_t ld_l, void* d_logit, int64_t ld_d, float* db_logit,
-                                 double* acc, int amb, int amb_global, float disc_coef, float grad_scale,
-                                 float* grad_scale_dev, int dtype, void* stream) {
+extern "C" int ase_hip_disc_head_v2(const float* logit, int64_t ld_l, void* d_logit, int64_t ld_d, float* db_logit,
+                                    double* acc, int amb, int amb_global, float disc_coef, float grad_scale,
+                                    float* grad_scale_dev, const double* gp_add, int dtype, void* stream) {
     ASE_CHECK_ARG(logit && d_logit && acc && amb > 0 && amb_global >= amb && grad_scale > 0.f, "disc_head: null/empty operand");
+    ASE_CHECK_ARG(((uintptr_t)gp_add % 8) == 0, "disc_head: misaligned gp_add");
     const dim3 grid((3 * amb + 255) / 256);
     const int rc = ase_dispatch_storage(dtype, [&](auto tag) {
         typedef typename decltype(tag)::type T;
         ASE_LAUNCH(disc_head_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, logit, ld_l, (T*)d_logit, ld_d, db_logit, acc, amb,
-                   amb_global, disc_coef, grad_scale, grad_scale_dev);
+                   amb_global, disc_coef, grad_scale, grad_scale_dev, gp_add);
         return ASE_OK;
     });
     ASE_CHECK_ARG(rc == ASE_OK, "disc_head: bad dtype %d", dtype);
     ASE_CHECK_LAUNCH("disc_head");
     return ASE_OK;
+}
+
+extern "C" int ase_hip_disc_head(const float* logit, int64_t ld_l, void* d_logit, int64_t ld_d, float* db_logit,
+                                 double* acc, int amb, int amb_global, float disc_coef, float grad_scale,
+                                 float* grad_scale_dev, int dtype, void* stream) {
+    return ase_hip_disc_head_v2(logit, ld_l, d_logit, ld_d, db_logit, acc, amb, amb_global, disc_coef, grad_scale, grad_scale_dev, nullptr,
+                                dtype, stream);
 }
 
 extern "C" int ase_hip_enc_head(const float* e, int64_t ld_e, const float* z, int64_t ld_z, void* d_e, int64_t ld_de,

@@ -64,6 +64,11 @@ class _StepState:
         self.merged_stats = self.stats_exchanged = self.enc_z_ready = self.gp_x_done = self.acc_in_bucket = self.lr_live = False
 
 
+# engine_opts gp_stack = 'auto': the stacked penalty schedule is the default where it can run - same-box A/B of the benchmark update,
+# six alternations: 71.05 ms unstacked (70.72 - 71.17) against 69.00 ms stacked (68.66 - 69.56), profiles/nt_stacked_ab.txt
+_GP_STACK_AUTO = True
+
+
 class UpdateEngine(ForwardEngine):
     """The trainer on top of the forward engine: gradients, Adam state, the step and its schedule, the gradient penalty, the loss
     scaler, the collectives and the epoch tail.  kind: 'ase' | 'amp' | 'ppo'.  sizes: rows handled by THIS rank (M, AMB) and
@@ -174,6 +179,16 @@ class UpdateEngine(ForwardEngine):
         #                   step's accumulators, which the un-chained head of the cross-step schedule must not touch.
         #                   'auto' (default) = on where the backend has the capability; True / False force it (False, or a backend
         #                   without the capability: the launch sequence of round 6, the A/B leg)
+        #   gp_stack        (with gp_fuse) the backward of the penalty chain below its top layer - dJ/dU_l = m_l * (dJ/dU_{l-1} @ W_l^T),
+        #                   forward-shaped launches on AMB rows through the weights of the loss rows' forward - rides on that forward:
+        #                   layers 0 .. nl - 2 of the trunk run ONE launch each over the 4 AMB rows of Xd4 / Hd4 with a row-split
+        #                   epilogue (backend capability nt_stack, ase_hip_gemm_nt_stacked).  The forward sits in the branch's head,
+        #                   which the cross-step schedule runs BEFORE begin_step, so the whole value path moves there: its last launch
+        #                   (S s g_0 and the sum of its squares) adds into a cell of the branch's own beside the amp sums - zeroed with
+        #                   them - and the discriminator's loss head folds the cell into the step's accumulator (disc_head gp_add).
+        #                   Needs the value path inline on the branch's stream (gp_stream off) and a STATIC gradient scale: under the
+        #                   dynamic scale the head would read S before the previous step's scaler step, so that case stays unstacked.
+        #                   True / False force it where it can run; 'auto' (default): see _GP_STACK_AUTO
         #   gp_stream       gp_f32 modes: the penalty's value path (f32 / bf16x3 forward of the demo rows + chain: independent of
         #                   the loss rows until the conversion launch) on its own stream beside the discriminator branch.  Round 4's
         #                   A/B had it faster (with the bf16-split kernels of that round); on round 6's kernels it is SLOWER: f16gpx3
@@ -185,7 +200,8 @@ class UpdateEngine(ForwardEngine):
         #                   dynamic loss scale (95.3 vs 115.2 ms).  'auto' (default) = on for minibatches below 8192 rows and under the
         #                   dynamic loss scale, off otherwise; True / False force it
         o = dict(tn_grouped=True, tn_wg_side=64, disc_early=True, short_prologue=True, relu_bits=True, fused_apply=True,
-                 apply_wide=True, xstep=True, gp_stream='auto', side_priority=None, prefetch=True, gp_fuse='auto')
+                 apply_wide=True, xstep=True, gp_stream='auto', side_priority=None, prefetch=True, gp_fuse='auto',
+                 gp_stack='auto')
         unknown = set(cfg.get('engine_opts', {}) or {}) - set(o)
         assert not unknown, f"unknown engine_opts {sorted(unknown)}"
         o.update(cfg.get('engine_opts', {}) or {})
@@ -211,6 +227,11 @@ class UpdateEngine(ForwardEngine):
         # (it stays set where the split optimizer launch never runs - truncate_grads, the end-of-step forms of phase_apply: those end in
         #  refresh_shadows(), which calls _gp_refresh)
         self._gp_split = self._gp_fuse and hasattr(backend, 'apply_multi_split') and self._fused_apply and dtype == torch.float16
+        # (one rank: the merged statistics collective of a sharded step zeroes and exchanges the buffer the penalty's cell lives in from
+        #  ANOTHER stream than the one that folds it)
+        self._gp_stack = bool(self._gp_fuse and not self._gp_side and not self.dyn_scale and getattr(backend, 'nt_stack', False)
+                              and world_size == 1 and not cfg.get('force_dist', False)
+                              and (_GP_STACK_AUTO if o['gp_stack'] == 'auto' else bool(o['gp_stack'])))
         self._prefetch = bool(o['prefetch'])
         self._par, self._par_set, self._last_par, self._fenced = 0, False, None, False
         sp = o['side_priority']
@@ -404,12 +425,17 @@ class UpdateEngine(ForwardEngine):
         # [amp sums x3 | obs sums | mask sum]: one small all-reduce per step when the step runs its statistics in a
         # serial prologue; with the branch heads un-chained (cross-step schedule) each head exchanges ITS slice on its own stream -
         # the amp block from the discriminator's head, [obs | mask] (contiguous) from the policy prologue
+        # gp_stack: one more cell IN FRONT of the amp sums - the penalty's sum of squares, formed by the branch's head before the step's
+        # accumulators are zeroed (see _gp_value); whoever zeroes the amp sums zeroes it (amp_zero), no collective carries it
         n_amp = 3 * 2 * self.amp if self.has_disc else 0
-        self.stats_flat = torch.zeros(n_amp + 2 * self.obs + 1, dtype=torch.float64, device=dev)
-        self.obs_sums = self.stats_flat[n_amp:n_amp + 2 * self.obs]
+        c0 = 1 if (self.has_disc and self._gp_stack) else 0
+        self.stats_flat = torch.zeros(c0 + n_amp + 2 * self.obs + 1, dtype=torch.float64, device=dev)
+        self.obs_sums = self.stats_flat[c0 + n_amp:c0 + n_amp + 2 * self.obs]
         if self.has_disc:
-            self.amp_sums_flat = self.stats_flat[:n_amp]
+            self.gp_sq = self.stats_flat[:c0]
+            self.amp_sums_flat = self.stats_flat[c0:c0 + n_amp]
             self.amp_sums = self.amp_sums_flat.view(3, 2 * self.amp)
+            self.amp_zero = self.stats_flat[:c0 + n_amp]
         self.obs_mean = zt(1, self.obs, f32)
         self.obs_std = zt(1, self.obs, f32)
         self.acc = torch.zeros(L.ACC_COUNT, dtype=torch.float64, device=dev)
@@ -763,7 +789,7 @@ class UpdateEngine(ForwardEngine):
             with self._Branch(self, self._side(1), nowait=True):
                 be.zero_(self.grads[lo:hi])
                 if not merged:                   # (merged: the prologue's begin_step zeroed the whole statistics buffer)
-                    be.zero_(self.amp_sums)
+                    be.zero_(self.amp_zero)      # (gp_stack: with the penalty's cell in front of them)
                 st.disc_fwd_out = self._disc_forward(amp_streams, ds)
         if pf:
             # The weight-independent prologue, un-chained like the discriminator's head: on the critic's stream it follows that
@@ -1042,7 +1068,20 @@ class UpdateEngine(ForwardEngine):
         """Second half: the matrix launches (trunk forward, joint head) and the logit snapshot."""
         be, AMB = self.be, self.AMB
         Rd = 3 * AMB
-        hd = self._fwd_chain(self.disc, self.Xd, self.Hd, Rd)
+        if self._stacked():
+            # gp_stack: layer l < nl - 1 over [H_{l-1} ; dJ/dU_{l-1}] in ONE launch - rows [0, 3 AMB) the loss rows' forward, rows
+            # [3 AMB, 4 AMB) the penalty chain's backward dJ/dU_l = m_l * (dJ/dU_{l-1} @ W_l^T) through the value path's exact masks
+            # (S s g_0 = "dJ/dU_{-1}" is in place: _gp_value ran in front).  Earlier readers of the 4th row block: the previous step's
+            # stacked weight-gradient launches and the chain's top launch, on this stream.
+            g, X = self._gp32, self.Xd4
+            for l, d in enumerate(self.disc[:-1]):
+                self._nt(X, d.Ws, self.Hd4[l], 4 * AMB, d.n_pad, d.k_pad, bias=d.bs, act=d.act, mask_out=self._mask_of(self.Hd[l]),
+                         stack=(Rd, g.bits[l], 1.0, None))
+                X = self.Hd4[l]
+            self._fwd(self.disc[-1], X[:Rd], self.Hd[-1], Rd)
+            hd = self.Hd[-1]
+        else:
+            hd = self._fwd_chain(self.disc, self.Xd, self.Hd, Rd)
         self._fwd(self.disc_head, hd, self.HD, Rd)
         if self.logit_slot is not None:        # the step's logits into its slot of the result ring (train_result's disc_*_logit)
             be.gather_rows(self.HD, 1, None, (0, 0), Rd, self.logit_slot)
@@ -1051,6 +1090,11 @@ class UpdateEngine(ForwardEngine):
             he = self._fwd_chain(self.enc_chain, self.Xd[:AMB], self.He, AMB)
             self._fwd(self.enc_head, he, self.E, AMB)
         return hd, he
+
+    def _stacked(self):
+        """This step runs the stacked penalty schedule (engine_opts gp_stack; a penalty coefficient of 0 takes the plain route, which
+        skips the chain)."""
+        return self._gp_stack and len(self.disc) >= 2 and self.cfg['disc_coef'] * self.cfg['disc_grad_penalty'] != 0
 
     def _gp_stream(self):
         if not self.multi_stream:
@@ -1101,8 +1145,9 @@ class UpdateEngine(ForwardEngine):
             with self._Branch(self, self._side(1), fork0) as br_disc:
                 if not disc_early:
                     hd, he = self._disc_forward(amp_streams)
+                # (gp_stack: the launch folds the penalty's sum of squares, formed by the head in its own cell, into the accumulators)
                 be.disc_head(self.HD, self.dHD, self.disc_head.gb[0], self.acc, AMB, self._amb_den, c['disc_coef'],
-                             grad_scale=self.gs, dyn=self._dS)
+                             grad_scale=self.gs, dyn=self._dS, **({'gp_add': self.gp_sq} if self._stacked() else {}))
                 if self.has_enc:
                     self._gather_enc_z(ds, amp_streams)
                     if self.enc_sep:
@@ -1467,9 +1512,11 @@ class UpdateEngine(ForwardEngine):
         layer l.  The top launch is kept in f32 at true scale (top_scale = s / the scale its operand carries): only its column sums
         are used, the penalty's gradient w.r.t. the logit weights."""
         AMB, nl, d0 = self.AMB, len(self.disc), self.disc[0]
-        aux, mode = mask(0)
-        self._nt(self.G0, d0.Ws, self.dGp[0], AMB, d0.n_pad, d0.k_pad, aux=aux, aux_mode=mode)
-        for l in range(1, nl):
+        stacked = self._stacked()         # gp_stack: layers 0 .. nl - 2 rode on the loss rows' forward (_disc_matrices); the top is left
+        if not stacked:
+            aux, mode = mask(0)
+            self._nt(self.G0, d0.Ws, self.dGp[0], AMB, d0.n_pad, d0.k_pad, aux=aux, aux_mode=mode)
+        for l in range(nl - 1 if stacked else 1, nl):
             d = self.disc[l]
             last = l == nl - 1
             aux, mode = mask(l)
@@ -1532,6 +1579,18 @@ class UpdateEngine(ForwardEngine):
             if not fuse:      # (gp_fuse: _gp_f32 launches it - it adds to the step's accumulators)
                 d0 = self.disc[0]
                 self._nt(g.Gp[0], g.Wts[0], g.G0, AMB, d0.k_pad, d0.n_pad, alpha=S, alpha_dev=self._dS, **ex(12))     # S s * g_0
+            elif self._stacked():
+                # gp_stack: the loss rows' forward, next on this stream, carries the chain's backward and needs S s g_0 now.  The sum
+                # of squares goes to the branch's own cell (zeroed with the amp sums), not to accumulators begin_step has yet to zero
+                self._gp_last(gp_coef, ex, (self.gp_sq, 0))
+
+    def _gp_last(self, gp_coef, ex, sq_cell):
+        """The chain's last launch under gp_fuse: S s g_0 straight into the 16-bit row block (never stored in f32) + the sum of its
+        squares, scaled to the penalty's value, into sq_cell = (f64 buffer, slot)."""
+        g, S, d0 = self._gp32, self.gs, self.disc[0]
+        cg = gp_coef * 2.0 / self.AMBg
+        self._nt(g.Gp[0], g.Wts[0], g.G0, self.AMB, d0.k_pad, d0.n_pad, alpha=S, alpha_dev=self._dS, twin=self.G0, store=False,
+                 sq=sq_cell + (1.0 / (cg * S * S), self._dI2), **ex(12))
 
     @contextlib.contextmanager
     def _gp_mode(self):
@@ -1566,12 +1625,12 @@ class UpdateEngine(ForwardEngine):
         if self._st.gp_value_done is not None:
             self._join_branch(self._st.gp_value_done)
             self._st.gp_value_done = None
-        if self._gp_fuse:
-            # the chain's last launch: S s g_0 straight into the 16-bit row block (never stored in f32) + the sum of its squares;
-            # the 16-bit copies of s g_l were written by the launches that produced them (_gp_value)
+        if self._stacked():
+            pass             # (gp_stack: the whole value path, its last launch included, ran in the branch's head)
+        elif self._gp_fuse:
+            # the chain's last launch (_gp_last); the 16-bit copies of s g_l were written by the launches that produced them (_gp_value)
             with self._gp_mode() as ex:
-                self._nt(g.Gp[0], g.Wts[0], g.G0, AMB, d0.k_pad, d0.n_pad, alpha=S, alpha_dev=self._dS, twin=self.G0, store=False,
-                         sq=(self.acc, L.ACC_GP, 1.0 / (cg * S * S), self._dI2), **ex(12))
+                self._gp_last(gp_coef, ex, (self.acc, L.ACC_GP))
         else:
             self._gp_convert(cg)
         self._gp_backward(s)

@@ -46,6 +46,8 @@ SIGNATURES = {
     "ase_hip_gemm_nt": [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i, _i, _p, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f, _p, _i, _p],
     "ase_hip_gemm_nt_ex": [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i, _i, _p, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f, _p, _i,
                            _p, _i, _f, _p, _i64, _i, _p, _d, _p, _p],
+    "ase_hip_gemm_nt_stacked": [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i, _i, _p, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f, _p,
+                                _i, _f, _p, _i, _p],
     "ase_hip_gemm_tn": [_p, _i64, _p, _i64, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _i, _p],
     "ase_hip_refresh_shadow": [_p, _i, _i, _p, _i64, _p, _i64, _i, _i, _i, _p],
     "ase_hip_refresh_shadow_multi": [_p, _i, _i, _p],
@@ -59,6 +61,7 @@ SIGNATURES = {
     "ase_hip_ppo_head": [_p, _i64, _p, _i64] + [_p] * 11 + [_p, _i64, _p, _i64, _p, _p, _p, _p, _p] + [_i] * 8 + [_f] * 6 + [_p]
                         + [_i, _i64, _p, _i64, _p, _f] + [_i, _p],
     "ase_hip_disc_head": [_p, _i64, _p, _i64, _p, _p, _i, _i, _f, _f, _p, _i, _p],
+    "ase_hip_disc_head_v2": [_p, _i64, _p, _i64, _p, _p, _i, _i, _f, _f, _p, _p, _i, _p],
     "ase_hip_enc_head": [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _i, _i, _i, _f, _f, _p, _i, _p],
     "ase_hip_gp_seed": [_p, _i64, _p, _p, _i64, _i, _i, _f, _i, _i, _p],
     "ase_hip_gp_second": [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i, _i, _i, _i, _p],

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_proj_launch, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id, ase_hip_rollout_store, ase_hip_hrl_latent / ase_hip_hrl_llc_action / ase_hip_hrl_accum and ase_hip_env_pre_step / ase_hip_env_post_step were added WITHOUT a new version
+/* (ase_hip_gemm_nt_ex, ase_hip_gemm_nt_stacked, ase_hip_disc_head_v2, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_proj_launch, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id, ase_hip_rollout_store, ase_hip_hrl_latent / ase_hip_hrl_llc_action / ase_hip_hrl_accum and ase_hip_env_pre_step / ase_hip_env_post_step were added WITHOUT a new version
  *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
  *  load time) */
 #define ASE_HIP_ABI_VERSION 9
@@ -127,6 +127,27 @@ int ase_hip_gemm_nt_ex(const void* A, int64_t lda, const void* B, int64_t ldb, v
                        int aux_mode, int out_f32, float alpha, float* alpha_dev, int dtype,
                        const float* seed_w, int seed_n, float seed_scale, void* twin, int64_t ldtwin, int twin_dtype,
                        double* sq_acc, double sq_scale, const float* sq_dyn, void* stream);
+
+/* ase_hip_gemm_nt over TWO row blocks of one A [M,K] / C [M,N] pair (16-bit or 4-byte storage type, never out_f32) that share B, with
+ * an epilogue each - the forward of a discriminator layer over the loss rows and the backward of the gradient-penalty chain through
+ * the same weights (dJ/dU_l = m_l * (dJ/dU_{l-1} @ W_l^T) is forward-shaped), stacked as the engine's buffers already are:
+ *   rows [0, split):  bias (nullable), act NONE / RELU, mask_out (nullable, only behind ReLU; written for these rows alone),
+ *                     alpha, alpha_dev.  No mask operand.
+ *   rows [split, M):  no bias, no activation, no mask_out; alpha2, alpha_dev2 (nullable record, as alpha_dev); the optional mask operand
+ *                     aux in the ASE_AUX_RELU_BITS format, [M - split, ldaux] words, read at row m - split: pass aux_split = aux_delta =
+ *                     split.  The mask SELECTS, as in ase_hip_gemm_nt: a masked-out element is 0 even where the product is inf or NaN.
+ * The result is what ase_hip_gemm_nt on rows [0, split) followed by ase_hip_gemm_nt on rows [split, M) stores: bit for bit whenever both
+ * forms sum in the same order, always on operands whose products and sums are exact.  One launch of the phased 256 x 256 kernel when
+ * that is the kernel of the whole shape (ase_hip_gemm_nt_kernel_id(M, N, K, dtype) == 2, ASE_F16 / ASE_BF16, M < 65536) and split is a
+ * multiple of 256 - every workgroup then lies in one block and picks that block's duties at its entry; in every other case the
+ * library issues the two plain launches itself, on `stream`.
+ * Refused (ASE_EINVAL): split <= 0 or >= M; a mask operand that is not the second block's (aux_mode other than NONE / RELU_BITS, or
+ * aux_split / aux_delta != split); mask_out without ReLU; an activation beyond ReLU; colsum or out_f32. */
+int ase_hip_gemm_nt_stacked(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                            const float* bias, const void* aux, int64_t ldaux, int aux_split, int aux_delta,
+                            float* colsum, int colsum_n, void* mask_out, int64_t ldmask, int M, int N, int K, int act,
+                            int aux_mode, int out_f32, float alpha, float* alpha_dev, int split, float alpha2, float* alpha_dev2,
+                            int dtype, void* stream);
 
 /* G[n, kmap(k)] += alpha * sum_m A[m,n] * B[m,k]   for n < n_real, kmap(k) valid     "TN" GEMM
  *   A [M,N] dtype (output gradients), B [M,K] dtype (layer inputs), G f32 [n_real, k_real]
@@ -339,6 +360,12 @@ int ase_hip_ppo_head(const float* mu, int64_t ld_mu, const float* value, int64_t
 int ase_hip_disc_head(const float* logit, int64_t ld_l, void* d_logit, int64_t ld_d, float* db_logit,
                       double* acc, int amb, int amb_global, float disc_coef, float grad_scale, float* grad_scale_dev, int dtype,
                       void* stream);
+/* ... with an addend for the gradient penalty's accumulator: gp_add (nullable, DEVICE f64*): acc[ASE_ACC_GP] += *gp_add, once per
+ * launch.  The stacked schedule of the penalty (ase_hip_gemm_nt_stacked) forms sum (S s g_0)^2 in a cell of its own BEFORE the step's
+ * accumulators are zeroed; this launch, which runs behind that, folds it in.  gp_add = NULL: ase_hip_disc_head. */
+int ase_hip_disc_head_v2(const float* logit, int64_t ld_l, void* d_logit, int64_t ld_d, float* db_logit,
+                         double* acc, int amb, int amb_global, float disc_coef, float grad_scale, float* grad_scale_dev,
+                         const double* gp_add, int dtype, void* stream);
 
 /* Encoder head (learning/ase_network_builder.py:217, learning/ase_agent.py:413-418,469-472):
  * e f32 [amb, ld_e] pre-normalisation output, z f32 [amb, z_dim]; d_e dtype [amb, ld_de].
