@@ -320,6 +320,108 @@ class HipBackend:
                                              *[_ptr(o) for o in out], self._stream()), "clip_frames")
         return tuple(out)
 
+    # ------------------------------------------------------------------ retargeting (N16; operands: see ase_hip_retarget_*)
+    def _rt_check(self, name, *specs):
+        for t, dt, shape in specs:
+            assert t.dtype == dt and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device.type == self.device.type, \
+                f"{name}: operand {tuple(t.shape)} {t.dtype}, expected {tuple(shape)} {dt} on {self.device}"
+
+    def _rt_out(self, name, out, *specs):
+        if out is None:
+            return tuple(torch.empty(*shape, dtype=dt, device=self.device) for dt, shape in specs)
+        out = tuple(out) if isinstance(out, (tuple, list)) else (out,)
+        self._rt_check(name, *[(o, dt, shape) for o, (dt, shape) in zip(out, specs)])
+        return out
+
+    def retarget_fk(self, rotation, mode, tree, clip_first, clip_num_frames, src_first, frame_clip, out=None):
+        """Global rotations of a tree for the frames the clip tables select -> f64 [T, B, 4].  rotation f64 [Tsrc, B, 4]; mode 0
+        local rotations, 1 global as stored, 2 global through local form; tree int32 [B, ld]; the four tables int32."""
+        f64, i32 = torch.float64, torch.int32
+        Ts, B, T, Cn = rotation.shape[0], rotation.shape[1], frame_clip.numel(), clip_first.numel()
+        self._rt_check('retarget_fk', (rotation, f64, (Ts, B, 4)), (tree, i32, (B, tree.shape[1])), (clip_first, i32, (Cn,)),
+                       (clip_num_frames, i32, (Cn,)), (src_first, i32, (Cn,)), (frame_clip, i32, (T,)))
+        out, = self._rt_out('retarget_fk', out, (f64, (T, B, 4)))
+        L.check(self.lib.ase_hip_retarget_fk(_ptr(rotation), int(mode), _ptr(tree), tree.shape[1], B, _ptr(clip_first),
+                                             _ptr(clip_num_frames), _ptr(src_first), _ptr(frame_clip), Cn, T, Ts, _ptr(out),
+                                             self._stream()), "retarget_fk")
+        return out
+
+    def retarget_chain(self, src_global, rs_body, rs_parent, rt_src, rt_tree, params, out=None):
+        """Source global rotations f64 [T, Bs, 4] -> global rotations on the reduced target tree, f64 [T, M, 4]."""
+        f64, i32 = torch.float64, torch.int32
+        T, Bs, M = src_global.shape[0], src_global.shape[1], rs_body.numel()
+        self._rt_check('retarget_chain', (src_global, f64, (T, Bs, 4)), (rs_body, i32, (M,)), (rs_parent, i32, (M,)),
+                       (rt_src, i32, (M,)), (rt_tree, i32, (M, rt_tree.shape[1])), (params, f64, (12,)))
+        out, = self._rt_out('retarget_chain', out, (f64, (T, M, 4)))
+        L.check(self.lib.ase_hip_retarget_chain(_ptr(src_global), Bs, _ptr(rs_body), _ptr(rs_parent), _ptr(rt_src), _ptr(rt_tree),
+                                                rt_tree.shape[1], M, _ptr(params), T, _ptr(out), self._stream()), "retarget_chain")
+        return out
+
+    def retarget_pose(self, state_global, tpose_global, target_global, root_translation, params, rt_body, ancestor, parent_indices,
+                      clip_first, clip_num_frames, src_first, frame_clip, out=None):
+        """-> (local rotations on the target tree f64 [T, Bt, 4], root translation f64 [T, 3])."""
+        f64, i32 = torch.float64, torch.int32
+        T, M, Bt, Ts, Cn = state_global.shape[0], state_global.shape[1], ancestor.numel(), root_translation.shape[0], clip_first.numel()
+        self._rt_check('retarget_pose', (state_global, f64, (T, M, 4)), (tpose_global, f64, (M, 4)), (target_global, f64, (Bt, 4)),
+                       (root_translation, f64, (Ts, 3)), (params, f64, (12,)), (rt_body, i32, (M,)), (ancestor, i32, (Bt,)),
+                       (parent_indices, i32, (Bt,)), (clip_first, i32, (Cn,)), (clip_num_frames, i32, (Cn,)), (src_first, i32, (Cn,)),
+                       (frame_clip, i32, (T,)))
+        out = self._rt_out('retarget_pose', out, (f64, (T, Bt, 4)), (f64, (T, 3)))
+        L.check(self.lib.ase_hip_retarget_pose(_ptr(state_global), _ptr(tpose_global), _ptr(target_global), _ptr(root_translation),
+                                               _ptr(params), _ptr(rt_body), _ptr(ancestor), _ptr(parent_indices), M, Bt,
+                                               _ptr(clip_first), _ptr(clip_num_frames), _ptr(src_first), _ptr(frame_clip), Cn, T, Ts,
+                                               _ptr(out[0]), _ptr(out[1]), self._stream()), "retarget_pose")
+        return out
+
+    def retarget_hinge(self, local_rotation, root_translation, local_translation, tree, roles, out=None):
+        """project_joints from the roles table int32 [B, 6] -> local rotations f64 [T, B, 4]."""
+        f64, i32 = torch.float64, torch.int32
+        T, B = local_rotation.shape[0], local_rotation.shape[1]
+        self._rt_check('retarget_hinge', (local_rotation, f64, (T, B, 4)), (root_translation, f64, (T, 3)),
+                       (local_translation, torch.float32, (B, 3)), (tree, i32, (B, tree.shape[1])), (roles, i32, (B, 6)))
+        out, = self._rt_out('retarget_hinge', out, (f64, (T, B, 4)))
+        L.check(self.lib.ase_hip_retarget_hinge(_ptr(local_rotation), _ptr(root_translation), _ptr(local_translation), _ptr(tree),
+                                                tree.shape[1], _ptr(roles), B, T, _ptr(out), self._stream()), "retarget_hinge")
+        return out
+
+    def retarget_ground(self, local_rotation, root_translation, local_translation, tree, clip_first, clip_num_frames, out=None):
+        """-> per clip the minimum of global z over its frames and bodies, f64 [C]."""
+        f64, i32 = torch.float64, torch.int32
+        T, B, Cn = local_rotation.shape[0], local_rotation.shape[1], clip_first.numel()
+        self._rt_check('retarget_ground', (local_rotation, f64, (T, B, 4)), (root_translation, f64, (T, 3)),
+                       (local_translation, torch.float32, (B, 3)), (tree, i32, (B, tree.shape[1])), (clip_first, i32, (Cn,)),
+                       (clip_num_frames, i32, (Cn,)))
+        out, = self._rt_out('retarget_ground', out, (f64, (Cn,)))
+        L.check(self.lib.ase_hip_retarget_ground(_ptr(local_rotation), _ptr(root_translation), _ptr(local_translation), _ptr(tree),
+                                                 tree.shape[1], B, _ptr(clip_first), _ptr(clip_num_frames), Cn, T, _ptr(out),
+                                                 self._stream()), "retarget_ground")
+        return out
+
+    def retarget_finish(self, local_rotation, root_translation, min_z, params, local_translation, tree, frame_clip, out=None):
+        """-> (global rotation f64 [T, B, 4], global translation f64 [T, B, 3], rotation f32 [T, B, 4], root translation f32 [T, 3])
+        of the grounded motion."""
+        f64, f32, i32 = torch.float64, torch.float32, torch.int32
+        T, B, Cn = local_rotation.shape[0], local_rotation.shape[1], min_z.numel()
+        self._rt_check('retarget_finish', (local_rotation, f64, (T, B, 4)), (root_translation, f64, (T, 3)), (min_z, f64, (Cn,)),
+                       (params, f64, (12,)), (local_translation, f32, (B, 3)), (tree, i32, (B, tree.shape[1])), (frame_clip, i32, (T,)))
+        out = self._rt_out('retarget_finish', out, (f64, (T, B, 4)), (f64, (T, B, 3)), (f32, (T, B, 4)), (f32, (T, 3)))
+        L.check(self.lib.ase_hip_retarget_finish(_ptr(local_rotation), _ptr(root_translation), _ptr(min_z), _ptr(params),
+                                                 _ptr(local_translation), _ptr(tree), tree.shape[1], B, _ptr(frame_clip), Cn, T,
+                                                 *[_ptr(o) for o in out], self._stream()), "retarget_finish")
+        return out
+
+    def retarget_velocity(self, global_rotation, global_translation, clip_first, clip_num_frames, clip_fps, frame_clip, out=None):
+        """-> (global velocity, global angular velocity), f32 [T, B, 3]."""
+        f64, f32, i32 = torch.float64, torch.float32, torch.int32
+        T, B, Cn = global_rotation.shape[0], global_rotation.shape[1], clip_first.numel()
+        self._rt_check('retarget_velocity', (global_rotation, f64, (T, B, 4)), (global_translation, f64, (T, B, 3)),
+                       (clip_first, i32, (Cn,)), (clip_num_frames, i32, (Cn,)), (clip_fps, f64, (Cn,)), (frame_clip, i32, (T,)))
+        out = self._rt_out('retarget_velocity', out, (f32, (T, B, 3)), (f32, (T, B, 3)))
+        L.check(self.lib.ase_hip_retarget_velocity(_ptr(global_rotation), _ptr(global_translation), B, _ptr(clip_first),
+                                                   _ptr(clip_num_frames), _ptr(clip_fps), _ptr(frame_clip), Cn, T, _ptr(out[0]),
+                                                   _ptr(out[1]), self._stream()), "retarget_velocity")
+        return out
+
     # ------------------------------------------------------------------ environment side (N5)
     @staticmethod
     def _f32c(*ts):

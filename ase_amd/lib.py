@@ -116,6 +116,13 @@ SIGNATURES = {
     "ase_hip_env_post_step": [_p, _i64, _i64] * 7 + [_i, _i, _i, _i, _i, _p, _i64, _i, _f, _i, _i, _i, _p, _i64, _p, _p, _p, _p, _f, _p,
                               _i64, _i, _f, _p, _p, _p, _p, _i, _p, _i64, _p, _i, _f, _i, _p, _p, _p, _p, _i, _p, _i, _p, _i, _p],
     "ase_hip_clip_frames": [_p] * 6 + [_i] + [_p] * 4 + [_i, _i, _p, _p, _i] + [_p] * 7,
+    "ase_hip_retarget_fk": [_p, _i, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p, _p],
+    "ase_hip_retarget_chain": [_p, _i, _p, _p, _p, _p, _i, _i, _p, _i, _p, _p],
+    "ase_hip_retarget_pose": [_p] * 8 + [_i, _i] + [_p] * 4 + [_i, _i, _i, _p, _p, _p],
+    "ase_hip_retarget_hinge": [_p, _p, _p, _p, _i, _p, _i, _i, _p, _p],
+    "ase_hip_retarget_ground": [_p, _p, _p, _p, _i, _i, _p, _p, _i, _i, _p, _p],
+    "ase_hip_retarget_finish": [_p] * 6 + [_i, _i, _p, _i, _i] + [_p] * 5,
+    "ase_hip_retarget_velocity": [_p, _p, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p],
     "ase_hip_gemm_nt_kernel_id": [_i, _i, _i, _i],
     "ase_hip_gemm_tn_kernel_id": [_i, _i, _i, _i, _i, _i64, _i64, _i],
     "ase_hip_apply_multi": [_p, _i, _p, _p, _i, _p],

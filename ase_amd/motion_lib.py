@@ -15,9 +15,13 @@ dof observations, key bodies) - runs in two HIP kernels (``ase_hip_motion_state`
 ``AmpObsDemoSource.fetch_into`` is the whole demo fetch - draws, sampler, frames and the store into the demo ring - as one
 launch (``ase_hip_amp_demo_fetch``, N11).
 
-There is no host fallback for either.  Not here: FBX / MJCF import, retargeting, clips that store global rotations.
+There is no host fallback for either.  ``DeviceMotionLib.from_clips`` takes clip dicts instead of files (``read_clip``'s form,
+arrays on the host or on the device - what ``ase_amd.retarget.Retargeter.retarget`` returns), ``write_clip`` writes one as a
+poselib ``SkeletonMotion`` file.  Not here: FBX / MJCF import; the motion library itself loads local-rotation clips only
+(``read_clip(path, allow_global=True)`` reads a global-rotation clip for the retargeter).
 """
 import os
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -47,10 +51,11 @@ def fetch_motion_files(motion_file):
     return files, weights
 
 
-def read_clip(path):
+def read_clip(path, allow_global=False):
     """One ``SkeletonMotion`` file as poselib writes it (``numpy.save`` of an ordered dict, arrays under ``['arr']``) -> dict of
     numpy arrays: rotation [F, J, 4], root_translation [F, 3], global_velocity / global_angular_velocity [F, J, 3] (f64),
-    parent_indices [J], local_translation [J, 3] (f32), fps.  Nothing is computed.
+    parent_indices [J], local_translation [J, 3] (f32), fps, is_local.  Nothing is computed.  A clip that stores GLOBAL rotations
+    is refused unless ``allow_global`` (the retargeter takes one; the motion library does not).
 
     The format is a PICKLE (``allow_pickle=True``): loading a file runs code it names.  Read trusted files only."""
     try:
@@ -60,7 +65,7 @@ def read_clip(path):
     if not isinstance(d, dict) or d.get('__name__') != 'SkeletonMotion':
         name = d.get('__name__') if isinstance(d, dict) else type(d).__name__
         raise ValueError(f"{path}: holds a {name!r}, not a 'SkeletonMotion'")
-    if not d['is_local']:
+    if not d['is_local'] and not allow_global:
         raise ValueError(f'{path}: the clip stores global rotations (is_local == False), which are not loaded; '
                          're-save it in local form (rotations relative to the parent body, is_local == True)')
     tree = d['skeleton_tree']
@@ -69,7 +74,7 @@ def read_clip(path):
          'global_velocity': arr(d['global_velocity'], np.float64),
          'global_angular_velocity': arr(d['global_angular_velocity'], np.float64),
          'parent_indices': arr(tree['parent_indices'], np.int64), 'local_translation': arr(tree['local_translation'], np.float32),
-         'node_names': list(tree['node_names']), 'fps': float(d['fps'])}
+         'node_names': list(tree['node_names']), 'fps': float(d['fps']), 'is_local': bool(d['is_local'])}
     F, J = c['rotation'].shape[:2]
     if c['rotation'].shape != (F, J, 4) or c['root_translation'].shape != (F, 3) or c['global_velocity'].shape != (F, J, 3) or \
             c['global_angular_velocity'].shape != (F, J, 3) or c['parent_indices'].shape != (J,) or c['local_translation'].shape != (J, 3):
@@ -84,43 +89,102 @@ def read_clip(path):
     return c
 
 
-def read_motion_files(motion_file, dof_body_ids, dof_offsets, key_body_ids):
-    """The host side of ``DeviceMotionLib.from_file``: file list, per-clip tables as ``MotionLib._load_motions``
-    (utils/motion_lib.py:192-228,82-85) and the raw arrays of all clips concatenated along the frame axis.  Raises
-    ``ValueError`` naming the file for everything the loader refuses."""
-    files, weights = fetch_motion_files(motion_file)
+def write_clip(path, clip):
+    """A clip dict (``read_clip``'s form; arrays numpy or torch, on any device) as the ``SkeletonMotion`` file poselib's
+    ``to_file`` writes - ``numpy.save`` of an ordered dict with the keys, key order and dtypes of the shipped clip files (f64
+    arrays, int64 parents, f32 offsets) - which ``read_clip`` and the reference's ``SkeletonMotion.from_file`` load."""
+    def host(x, dt):
+        x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        return np.ascontiguousarray(x, dtype=dt)
+
+    def entry(x, dt):
+        return {'arr': host(x, dt), 'context': {'dtype': np.dtype(dt).name}}
+    F, J = host(clip['rotation'], np.float64).shape[:2]
+    for k, shape in (('rotation', (F, J, 4)), ('root_translation', (F, 3)), ('global_velocity', (F, J, 3)),
+                     ('global_angular_velocity', (F, J, 3)), ('parent_indices', (J,)), ('local_translation', (J, 3))):
+        if tuple(clip[k].shape) != shape:
+            raise ValueError(f'{path}: {k} {tuple(clip[k].shape)}, expected {shape}')
+    if len(clip['node_names']) != J:
+        raise ValueError(f"{path}: {len(clip['node_names'])} node names for {J} bodies")
+    tree = OrderedDict([('node_names', [str(n) for n in clip['node_names']]),
+                        ('parent_indices', entry(clip['parent_indices'], np.int64)),
+                        ('local_translation', entry(clip['local_translation'], np.float32))])
+    d = OrderedDict([('rotation', entry(clip['rotation'], np.float64)), ('root_translation', entry(clip['root_translation'], np.float64)),
+                     ('global_velocity', entry(clip['global_velocity'], np.float64)),
+                     ('global_angular_velocity', entry(clip['global_angular_velocity'], np.float64)),
+                     ('skeleton_tree', tree), ('is_local', bool(clip.get('is_local', True))), ('fps', float(clip['fps'])),
+                     ('__name__', 'SkeletonMotion')])
+    with open(path, 'wb') as f:                              # (numpy.save appends '.npy' to a bare path that lacks it)
+        np.save(f, d, allow_pickle=True)
+
+
+def clip_tables(clips, names, label, dof_body_ids, dof_offsets, key_body_ids):
+    """Per-clip tables as ``MotionLib._load_motions`` (utils/motion_lib.py:192-228,82-85) and the raw arrays of ``clips``
+    (``read_clip`` dicts; ``names`` label them in messages) concatenated along the frame axis - numpy when every clip's arrays
+    are, torch tensors otherwise.  Raises ``ValueError`` for everything the loader refuses."""
     dof_body_ids, dof_offsets, key_body_ids = [int(x) for x in dof_body_ids], [int(x) for x in dof_offsets], [int(x) for x in key_body_ids]
     if len(dof_offsets) != len(dof_body_ids) + 1 or dof_offsets[0] != 0:
-        raise ValueError(f'{motion_file}: dof_offsets {dof_offsets} do not describe the {len(dof_body_ids)} joints of dof_body_ids')
+        raise ValueError(f'{label}: dof_offsets {dof_offsets} do not describe the {len(dof_body_ids)} joints of dof_body_ids')
     for j in range(len(dof_body_ids)):
         if dof_offsets[j + 1] - dof_offsets[j] not in (1, 3):
-            raise ValueError(f'{motion_file}: joint {j} has {dof_offsets[j + 1] - dof_offsets[j]} dofs (1 or 3 supported)')
-    clips = [read_clip(f) for f in files]
+            raise ValueError(f'{label}: joint {j} has {dof_offsets[j + 1] - dof_offsets[j]} dofs (1 or 3 supported)')
     first = clips[0]
     J = first['rotation'].shape[1]
     for name, ids in (('dof_body_id', dof_body_ids), ('key_body_id', key_body_ids)):
         for b in ids:
             if not 0 <= b < J:
-                raise ValueError(f'{files[0]}: {name} {b} outside the skeleton of {J} bodies')
-    for f, c in zip(files, clips):
-        if c['rotation'].shape[1] != J or not np.array_equal(c['parent_indices'], first['parent_indices']):
-            raise ValueError(f"{f}: skeleton ({c['rotation'].shape[1]} bodies, parents {c['parent_indices'].tolist()}) differs from "
-                             f'that of {files[0]}')
-    num_frames = [c['rotation'].shape[0] for c in clips]
-    fps = [c['fps'] for c in clips]
+                raise ValueError(f'{names[0]}: {name} {b} outside the skeleton of {J} bodies')
+    parents = np.asarray(first['parent_indices'])
+    for f, c in zip(names, clips):
+        if c['rotation'].shape[1] != J or not np.array_equal(np.asarray(c['parent_indices']), parents):
+            raise ValueError(f"{f}: skeleton ({c['rotation'].shape[1]} bodies, parents {np.asarray(c['parent_indices']).tolist()}) differs from "
+                             f'that of {names[0]}')
+        if not c.get('is_local', True):
+            raise ValueError(f'{f}: the clip stores global rotations (is_local == False), which are not loaded')
+        if c['rotation'].shape[0] < 2:
+            raise ValueError(f"{f}: {c['rotation'].shape[0]} frame(s); a clip has 2 or more")
+    num_frames = [int(c['rotation'].shape[0]) for c in clips]
+    fps = [float(c['fps']) for c in clips]
     starts = np.concatenate([[0], np.cumsum(num_frames)[:-1]])
-    cat = lambda k: np.concatenate([c[k] for c in clips], axis=0)
-    return {'motion_files': files, 'weights': weights, 'fps': fps, 'num_frames': num_frames,
+    on_host = all(isinstance(c[k], np.ndarray) for c in clips for k in ('rotation', 'root_translation', 'global_velocity',
+                                                                       'global_angular_velocity'))
+    if on_host:
+        cat = lambda k, sel=None: np.concatenate([c[k] if sel is None else c[k][:, sel] for c in clips], axis=0)
+    else:
+        cat = lambda k, sel=None: torch.cat([torch.as_tensor(c[k]) if sel is None else torch.as_tensor(c[k])[:, sel] for c in clips], dim=0)
+    body0 = lambda k: np.ascontiguousarray(cat(k)[:, 0]) if on_host else cat(k, 0)
+    return {'fps': fps, 'num_frames': num_frames,
             'dt': [1.0 / x for x in fps],                                                  # motion_lib.py:193
             'lengths': [1.0 / x * (n - 1) for x, n in zip(fps, num_frames)],               # motion_lib.py:196
             'length_starts': starts.tolist(),
             'frame_clip': np.repeat(np.arange(len(clips), dtype=np.int32), num_frames),
-            'parent_indices': first['parent_indices'].tolist(),
+            'parent_indices': parents.tolist(),
             'rotation': cat('rotation'), 'root_translation': cat('root_translation'),
-            'root_velocity': np.ascontiguousarray(cat('global_velocity')[:, 0]),           # motion_lib.py:78-79: body 0
-            'root_angular_velocity': np.ascontiguousarray(cat('global_angular_velocity')[:, 0]),
-            'local_translation': np.stack([c['local_translation'] for c in clips]),        # each clip's own skeleton offsets
+            'root_velocity': body0('global_velocity'),                                     # motion_lib.py:78-79: body 0
+            'root_angular_velocity': body0('global_angular_velocity'),
+            'local_translation': np.stack([np.asarray(c['local_translation'], dtype=np.float32) for c in clips]),   # each clip's own offsets
             'dof_body_ids': dof_body_ids, 'dof_offsets': dof_offsets, 'key_body_ids': key_body_ids}
+
+
+def read_motion_files(motion_file, dof_body_ids, dof_offsets, key_body_ids):
+    """The host side of ``DeviceMotionLib.from_file``: file list, per-clip tables as ``MotionLib._load_motions``
+    (utils/motion_lib.py:192-228,82-85) and the raw arrays of all clips concatenated along the frame axis.  Raises
+    ``ValueError`` naming the file for everything the loader refuses."""
+    files, weights = fetch_motion_files(motion_file)
+    _check_joint_tables(motion_file, dof_body_ids, dof_offsets)
+    h = clip_tables([read_clip(f) for f in files], files, motion_file, dof_body_ids, dof_offsets, key_body_ids)
+    h.update(motion_files=files, weights=weights)
+    return h
+
+
+def _check_joint_tables(label, dof_body_ids, dof_offsets):
+    """The joint tables are checked before any file is read."""
+    dof_body_ids, dof_offsets = [int(x) for x in dof_body_ids], [int(x) for x in dof_offsets]
+    if len(dof_offsets) != len(dof_body_ids) + 1 or dof_offsets[0] != 0:
+        raise ValueError(f'{label}: dof_offsets {dof_offsets} do not describe the {len(dof_body_ids)} joints of dof_body_ids')
+    for j in range(len(dof_body_ids)):
+        if dof_offsets[j + 1] - dof_offsets[j] not in (1, 3):
+            raise ValueError(f'{label}: joint {j} has {dof_offsets[j + 1] - dof_offsets[j]} dofs (1 or 3 supported)')
 
 
 def clip_cdf(weights):
@@ -163,26 +227,45 @@ class DeviceMotionLib:
         return cls(clips, backend, device, **kw)
 
     @classmethod
-    def from_file(cls, motion_file, dof_body_ids, dof_offsets, key_body_ids, backend, device, **kw):
-        """``MotionLib(motion_file, dof_body_ids, dof_offsets, key_body_ids, device)`` (utils/motion_lib.py:65-89): a dataset
-        ``.yaml`` or one ``.npy`` clip.  The files are read on the host (``read_motion_files``; pickles - trusted files only),
-        their raw f64 arrays uploaded once, and every frame array computed by ONE launch of ``backend.clip_frames``.
-        ``motion_files`` and ``fps`` are kept as attributes.  Raises ``ValueError`` naming the file for what is refused."""
-        h = read_motion_files(motion_file, dof_body_ids, dof_offsets, key_body_ids)
+    def from_clips(cls, clips, dof_body_ids, dof_offsets, key_body_ids, backend, device, weights=None, _names=None, _label='clips',
+                   **kw):
+        """The body of ``from_file`` behind the file reading: ``clips`` is a list of clip dicts in ``read_clip``'s form, with
+        arrays on the host (numpy) or already on the device (torch - what ``Retargeter.retarget`` returns, so retargeted clips
+        enter a motion library without touching the disk).  The raw arrays are concatenated, uploaded once as f64, and every
+        frame array is computed by ONE launch of ``backend.clip_frames``.  ``fps`` is kept as an attribute."""
+        clips = list(clips)
+        if not clips:
+            raise ValueError(f'{_label}: no clips')
+        names = _names if _names is not None else [f'clip {i}' for i in range(len(clips))]
+        h = clip_tables(clips, names, _label, dof_body_ids, dof_offsets, key_body_ids)
         dev = torch.device(device)
-        up = lambda k, dt: torch.as_tensor(h[k], dtype=dt).contiguous().to(dev)
+        up = lambda k, dt: (h[k] if isinstance(h[k], torch.Tensor) else torch.as_tensor(h[k], dtype=dt)).to(dev, dtype=dt).contiguous()
         out = backend.clip_frames(up('rotation', torch.float64), up('root_translation', torch.float64),
                                   up('root_velocity', torch.float64), up('root_angular_velocity', torch.float64),
                                   up('local_translation', torch.float32), h['parent_indices'], up('length_starts', torch.int32),
                                   up('num_frames', torch.int32), up('fps', torch.float64), up('frame_clip', torch.int32),
                                   h['dof_body_ids'], h['dof_offsets'])
-        clips = dict(zip(('gts', 'grs', 'lrs', 'grvs', 'gravs', 'dvs'), out))
-        clips.update(lengths=torch.tensor(h['lengths'], dtype=torch.float32), dt=torch.tensor(h['dt'], dtype=torch.float32),
-                     num_frames=torch.tensor(h['num_frames']), length_starts=torch.tensor(h['length_starts']),
-                     dof_body_ids=h['dof_body_ids'], dof_offsets=h['dof_offsets'], key_body_ids=h['key_body_ids'])
-        kw.setdefault('weights', h['weights'])
-        ml = cls(clips, backend, dev, **kw)
-        ml.motion_files, ml.fps = h['motion_files'], torch.tensor(h['fps'], dtype=torch.float32)
+        arrays = dict(zip(('gts', 'grs', 'lrs', 'grvs', 'gravs', 'dvs'), out))
+        arrays.update(lengths=torch.tensor(h['lengths'], dtype=torch.float32), dt=torch.tensor(h['dt'], dtype=torch.float32),
+                      num_frames=torch.tensor(h['num_frames']), length_starts=torch.tensor(h['length_starts']),
+                      dof_body_ids=h['dof_body_ids'], dof_offsets=h['dof_offsets'], key_body_ids=h['key_body_ids'])
+        ml = cls(arrays, backend, dev, weights=weights, **kw)
+        ml.fps = torch.tensor(h['fps'], dtype=torch.float32)
+        return ml
+
+    @classmethod
+    def from_file(cls, motion_file, dof_body_ids, dof_offsets, key_body_ids, backend, device, **kw):
+        """``MotionLib(motion_file, dof_body_ids, dof_offsets, key_body_ids, device)`` (utils/motion_lib.py:65-89): a dataset
+        ``.yaml`` or one ``.npy`` clip.  The files are read on the host (``read_clip``; pickles - trusted files only) and handed
+        to ``from_clips``: their raw f64 arrays uploaded once, every frame array computed by ONE launch of
+        ``backend.clip_frames``.  ``motion_files`` and ``fps`` are kept as attributes.  Raises ``ValueError`` naming the file for
+        what is refused."""
+        files, weights = fetch_motion_files(motion_file)
+        _check_joint_tables(motion_file, dof_body_ids, dof_offsets)
+        kw.setdefault('weights', weights)
+        ml = cls.from_clips([read_clip(f) for f in files], dof_body_ids, dof_offsets, key_body_ids, backend, device,
+                            _names=files, _label=motion_file, **kw)
+        ml.motion_files = files
         return ml
 
     @classmethod

@@ -102,6 +102,10 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
               clip_fps, frame_clip, parent_indices, dof_body_ids, dof_offsets) -> (gts, grs, lrs, grvs, gravs, dvs)
                                                       the clip loader: forward kinematics and joint velocities of every frame of
                                                       every clip (MotionLib._load_motions, utils/motion_lib.py:174-236,279-294)
+  retarget_fk / retarget_chain / retarget_pose / retarget_hinge / retarget_ground / retarget_finish / retarget_velocity
+                                                      the launches of ase_amd.retarget.Retargeter, operands as the backend
+                                                      methods of the same names (poselib retarget_to, project_joints, grounding,
+                                                      from_skeleton_state); every operand a device tensor
 
 ``HipLinear`` is an ``nn.Linear`` whose forward is ``linear_act`` (optionally with a fused ReLU / tanh).
 """
@@ -1009,3 +1013,158 @@ def _(rotation, root_translation, root_velocity, root_angular_velocity, local_tr
     T, B = rotation.shape[0], rotation.shape[1]
     f = lambda *shape: rotation.new_empty(*shape, dtype=torch.float32)
     return f(T, B, 3), f(T, B, 4), f(T, B, 4), f(T, 3), f(T, 3), f(T, dof_offsets[-1])
+
+
+def _rt_dev(name, *ts):
+    for t in ts:
+        _check(t.is_cuda and t.dtype in (torch.float64, torch.float32, torch.int32), f'{name}: f64 / f32 / int32 device tensors')
+    return [t.contiguous() for t in ts]
+
+
+def _rt_shape(name, what, cond):
+    _check(cond, f'{name}: {what}')
+
+
+@torch.library.custom_op('ase_hip::retarget_fk', mutates_args=(), device_types='cuda')
+def retarget_fk(rotation: torch.Tensor, mode: int, tree: torch.Tensor, clip_first: torch.Tensor, clip_num_frames: torch.Tensor,
+                src_first: torch.Tensor, frame_clip: torch.Tensor) -> torch.Tensor:
+    """Global rotations of a tree (operands: see ase_hip_retarget_fk) -> f64 [T, B, 4]."""
+    _rt_shape('retarget_fk', 'rotation f64 [Tsrc, B, 4], tree int32 [B, ld]',
+              rotation.dim() == 3 and rotation.shape[2] == 4 and rotation.dtype == torch.float64 and tree.dim() == 2 and
+              tree.shape[0] == rotation.shape[1] and tree.dtype == torch.int32)
+    _rt_shape('retarget_fk', 'clip_first / clip_num_frames / src_first int32 [C], frame_clip int32 [T]',
+              clip_first.dim() == 1 and clip_first.shape == clip_num_frames.shape == src_first.shape and frame_clip.dim() == 1 and
+              all(t.dtype == torch.int32 for t in (clip_first, clip_num_frames, src_first, frame_clip)))
+    return _backend().retarget_fk(*_rt_dev('retarget_fk', rotation), mode,
+                                  *_rt_dev('retarget_fk', tree, clip_first, clip_num_frames, src_first, frame_clip))
+
+
+@retarget_fk.register_fake
+def _(rotation, mode, tree, clip_first, clip_num_frames, src_first, frame_clip):
+    return rotation.new_empty(frame_clip.shape[0], rotation.shape[1], 4)
+
+
+@torch.library.custom_op('ase_hip::retarget_chain', mutates_args=(), device_types='cuda')
+def retarget_chain(src_global: torch.Tensor, rs_body: torch.Tensor, rs_parent: torch.Tensor, rt_src: torch.Tensor,
+                   rt_tree: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
+    """Source global rotations -> global rotations on the reduced target tree (see ase_hip_retarget_chain), f64 [T, M, 4]."""
+    _rt_shape('retarget_chain', 'src_global f64 [T, Bs, 4], params f64 [12]',
+              src_global.dim() == 3 and src_global.shape[2] == 4 and src_global.dtype == params.dtype == torch.float64 and
+              params.shape == (12,))
+    _rt_shape('retarget_chain', 'rs_body / rs_parent / rt_src int32 [M], rt_tree int32 [M, ld]',
+              rs_body.dim() == 1 and rs_body.shape == rs_parent.shape == rt_src.shape and rt_tree.dim() == 2 and
+              rt_tree.shape[0] == rs_body.shape[0] and all(t.dtype == torch.int32 for t in (rs_body, rs_parent, rt_src, rt_tree)))
+    return _backend().retarget_chain(*_rt_dev('retarget_chain', src_global, rs_body, rs_parent, rt_src, rt_tree, params))
+
+
+@retarget_chain.register_fake
+def _(src_global, rs_body, rs_parent, rt_src, rt_tree, params):
+    return src_global.new_empty(src_global.shape[0], rs_body.shape[0], 4)
+
+
+@torch.library.custom_op('ase_hip::retarget_pose', mutates_args=(), device_types='cuda')
+def retarget_pose(state_global: torch.Tensor, tpose_global: torch.Tensor, target_global: torch.Tensor,
+                  root_translation: torch.Tensor, params: torch.Tensor, rt_body: torch.Tensor, ancestor: torch.Tensor,
+                  parent_indices: torch.Tensor, clip_first: torch.Tensor, clip_num_frames: torch.Tensor, src_first: torch.Tensor,
+                  frame_clip: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The pose transfer (see ase_hip_retarget_pose) -> (local rotations f64 [T, Bt, 4], root translation f64 [T, 3])."""
+    _rt_shape('retarget_pose', 'state_global f64 [T, M, 4], tpose_global f64 [M, 4], target_global f64 [Bt, 4], root_translation f64 [Tsrc, 3]',
+              state_global.dim() == 3 and state_global.shape[2] == 4 and tpose_global.shape == state_global.shape[1:] and
+              target_global.shape == (ancestor.numel(), 4) and root_translation.dim() == 2 and root_translation.shape[1] == 3 and
+              params.shape == (12,) and
+              all(t.dtype == torch.float64 for t in (state_global, tpose_global, target_global, root_translation, params)))
+    _rt_shape('retarget_pose', 'rt_body int32 [M], ancestor / parent_indices int32 [Bt], clip tables int32 [C], frame_clip int32 [T]',
+              rt_body.shape == (state_global.shape[1],) and ancestor.dim() == 1 and parent_indices.shape == ancestor.shape and
+              clip_first.dim() == 1 and clip_first.shape == clip_num_frames.shape == src_first.shape and
+              frame_clip.shape == (state_global.shape[0],) and
+              all(t.dtype == torch.int32 for t in (rt_body, ancestor, parent_indices, clip_first, clip_num_frames, src_first, frame_clip)))
+    return _backend().retarget_pose(*_rt_dev('retarget_pose', state_global, tpose_global, target_global, root_translation, params,
+                                             rt_body, ancestor, parent_indices, clip_first, clip_num_frames, src_first, frame_clip))
+
+
+@retarget_pose.register_fake
+def _(state_global, tpose_global, target_global, root_translation, params, rt_body, ancestor, parent_indices, clip_first,
+      clip_num_frames, src_first, frame_clip):
+    T = state_global.shape[0]
+    return state_global.new_empty(T, ancestor.shape[0], 4), state_global.new_empty(T, 3)
+
+
+def _rt_motion_shapes(name, local_rotation, root_translation, local_translation, tree):
+    _rt_shape(name, 'local_rotation f64 [T, B, 4], root_translation f64 [T, 3], local_translation f32 [B, 3], tree int32 [B, ld]',
+              local_rotation.dim() == 3 and local_rotation.shape[2] == 4 and root_translation.shape == (local_rotation.shape[0], 3) and
+              local_translation.shape == (local_rotation.shape[1], 3) and tree.dim() == 2 and tree.shape[0] == local_rotation.shape[1] and
+              local_rotation.dtype == root_translation.dtype == torch.float64 and local_translation.dtype == torch.float32 and
+              tree.dtype == torch.int32)
+
+
+@torch.library.custom_op('ase_hip::retarget_hinge', mutates_args=(), device_types='cuda')
+def retarget_hinge(local_rotation: torch.Tensor, root_translation: torch.Tensor, local_translation: torch.Tensor,
+                   tree: torch.Tensor, roles: torch.Tensor) -> torch.Tensor:
+    """project_joints from a table (see ase_hip_retarget_hinge) -> local rotations f64 [T, B, 4]."""
+    _rt_motion_shapes('retarget_hinge', local_rotation, root_translation, local_translation, tree)
+    _rt_shape('retarget_hinge', 'roles int32 [B, 6]', roles.shape == (local_rotation.shape[1], 6) and roles.dtype == torch.int32)
+    return _backend().retarget_hinge(*_rt_dev('retarget_hinge', local_rotation, root_translation, local_translation, tree, roles))
+
+
+@retarget_hinge.register_fake
+def _(local_rotation, root_translation, local_translation, tree, roles):
+    return torch.empty_like(local_rotation)
+
+
+@torch.library.custom_op('ase_hip::retarget_ground', mutates_args=(), device_types='cuda')
+def retarget_ground(local_rotation: torch.Tensor, root_translation: torch.Tensor, local_translation: torch.Tensor,
+                    tree: torch.Tensor, clip_first: torch.Tensor, clip_num_frames: torch.Tensor) -> torch.Tensor:
+    """Per clip the minimum of global z (see ase_hip_retarget_ground) -> f64 [C]."""
+    _rt_motion_shapes('retarget_ground', local_rotation, root_translation, local_translation, tree)
+    _rt_shape('retarget_ground', 'clip_first / clip_num_frames int32 [C]',
+              clip_first.dim() == 1 and clip_first.shape == clip_num_frames.shape and clip_first.dtype == clip_num_frames.dtype == torch.int32)
+    return _backend().retarget_ground(*_rt_dev('retarget_ground', local_rotation, root_translation, local_translation, tree,
+                                               clip_first, clip_num_frames))
+
+
+@retarget_ground.register_fake
+def _(local_rotation, root_translation, local_translation, tree, clip_first, clip_num_frames):
+    return local_rotation.new_empty(clip_first.shape[0])
+
+
+@torch.library.custom_op('ase_hip::retarget_finish', mutates_args=(), device_types='cuda')
+def retarget_finish(local_rotation: torch.Tensor, root_translation: torch.Tensor, min_z: torch.Tensor, params: torch.Tensor,
+                    local_translation: torch.Tensor, tree: torch.Tensor, frame_clip: torch.Tensor
+                    ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The grounded motion (see ase_hip_retarget_finish) -> (global rotation f64 [T, B, 4], global translation f64 [T, B, 3],
+    rotation f32 [T, B, 4], root translation f32 [T, 3])."""
+    _rt_motion_shapes('retarget_finish', local_rotation, root_translation, local_translation, tree)
+    _rt_shape('retarget_finish', 'min_z f64 [C], params f64 [12], frame_clip int32 [T]',
+              min_z.dim() == 1 and params.shape == (12,) and frame_clip.shape == (local_rotation.shape[0],) and
+              min_z.dtype == params.dtype == torch.float64 and frame_clip.dtype == torch.int32)
+    return _backend().retarget_finish(*_rt_dev('retarget_finish', local_rotation, root_translation, min_z, params, local_translation,
+                                               tree, frame_clip))
+
+
+@retarget_finish.register_fake
+def _(local_rotation, root_translation, min_z, params, local_translation, tree, frame_clip):
+    T, B = local_rotation.shape[0], local_rotation.shape[1]
+    f = lambda *shape: local_rotation.new_empty(*shape, dtype=torch.float32)
+    return torch.empty_like(local_rotation), local_rotation.new_empty(T, B, 3), f(T, B, 4), f(T, 3)
+
+
+@torch.library.custom_op('ase_hip::retarget_velocity', mutates_args=(), device_types='cuda')
+def retarget_velocity(global_rotation: torch.Tensor, global_translation: torch.Tensor, clip_first: torch.Tensor,
+                      clip_num_frames: torch.Tensor, clip_fps: torch.Tensor, frame_clip: torch.Tensor
+                      ) -> tuple[torch.Tensor, torch.Tensor]:
+    """Filtered velocities (see ase_hip_retarget_velocity) -> (global velocity, global angular velocity), f32 [T, B, 3]."""
+    T, B = global_rotation.shape[0], global_rotation.shape[1]
+    _rt_shape('retarget_velocity', 'global_rotation f64 [T, B, 4], global_translation f64 [T, B, 3], clip_fps f64 [C]',
+              global_rotation.dim() == 3 and global_rotation.shape[2] == 4 and global_translation.shape == (T, B, 3) and
+              global_rotation.dtype == global_translation.dtype == clip_fps.dtype == torch.float64)
+    _rt_shape('retarget_velocity', 'clip_first / clip_num_frames int32 [C], frame_clip int32 [T]',
+              clip_first.dim() == 1 and clip_first.shape == clip_num_frames.shape == clip_fps.shape and frame_clip.shape == (T,) and
+              all(t.dtype == torch.int32 for t in (clip_first, clip_num_frames, frame_clip)))
+    return _backend().retarget_velocity(*_rt_dev('retarget_velocity', global_rotation, global_translation, clip_first, clip_num_frames,
+                                                 clip_fps, frame_clip))
+
+
+@retarget_velocity.register_fake
+def _(global_rotation, global_translation, clip_first, clip_num_frames, clip_fps, frame_clip):
+    f = lambda: global_translation.new_empty(global_translation.shape, dtype=torch.float32)
+    return f(), f()

@@ -1125,6 +1125,81 @@ int ase_hip_clip_frames(const double* rotation, const double* root_translation, 
                         int n_frames, const int32_t* dof_body_ids, const int32_t* dof_offsets, int n_joints, float* gts,
                         float* grs, float* lrs, float* grvs, float* gravs, float* dvs, void* stream);
 
+/* Motion retargeting: a mocap clip on its own skeleton -> a SkeletonMotion on the target skeleton, all frames
+ * of all clips of a call in SEVEN launches (six without the hinge stage), whatever the number of clips and frames, with no
+ * host read in between.  Arithmetic: f64, operation by operation as poselib; every buffer between two launches is f64 on the
+ * device; the four outputs of a clip file are rounded to f32 once, at their store.  Clips are concatenated along the frame
+ * axis with the loader's tables (clip_first, clip_num_frames, clip_fps [n_clips], frame_clip [n_frames], DEVICE); no stencil,
+ * pairing or reduction crosses a clip boundary.  TRIMMING is table arithmetic: output row t of clip c, frame f = t -
+ * clip_first[c], reads source row src_first[c] + f (src_first already holds the clip's first kept frame).
+ * All skeleton tables are DEVICE int32 arrays (a source skeleton has up to 64 bodies).  A TREE table is [n, tree_ld]: column 0
+ * the depth of node b, columns 1 .. depth + 1 its chain from the root down to b itself; tree_ld <= 65.  The entries cannot
+ * read them, so the caller (ase_amd.retarget.Retargeter) checks that a parent precedes its child and that the reduced trees
+ * of a mapping have equal sizes; the kernels range-check every index they read from a table and an item whose tables do not
+ * describe it writes nothing.  Refused here: null operands, body counts outside 1-64, frames x bodies >= 2^31, clip counts
+ * that do not fit the frames, and (ase_hip_retarget_velocity) fewer than 2 frames per clip.
+ * params (DEVICE f64 [12]): the rotation to the target skeleton xyzw [0..3], the source T-pose's root translation [4..6], the
+ * target T-pose's [7..9], the scale [10], the root height offset [11].
+ *
+ * ase_hip_retarget_fk: global rotations of a tree, out [n_frames, n_bodies, 4].  mode 0: rotation holds local rotations,
+ *   forward kinematics (a root's is its own, a child's quat_mul_norm(global[parent], local[child])); 1: rotation holds
+ *   global rotations, copied as stored (SkeletonState._transfer_to of an is_local == False clip); 2: global rotations
+ *   taken to local form first (quat_mul_norm(inverse(global[parent]), global[child])), then mode 0 - a T-pose stored in
+ *   global form.  A T-pose is a one-frame call.
+ * ase_hip_retarget_chain: src_global [n_frames, n_src_bodies, 4] -> out [n_frames, n_mapped, 4], the global rotations on the
+ *   REDUCED TARGET tree: reduced-target node k takes the rotation of reduced-source node m = rt_src[k] (source body
+ *   rs_body[m]) local to its reduced-source parent rs_parent[m] (-1: none), node 0 is pre-multiplied by params[0..3]
+ *   (quat_mul_norm), and the locals are recomposed along rt_tree.  Where the two reduced trees differ in topology this is
+ *   not the source's global rotation (SkeletonState._transfer_to, _remapped_to, STEP 2 of retarget_to).
+ * ase_hip_retarget_pose: per frame and target body b, g(b) = quat_mul_norm(quat_mul_norm(state_global[i], inverse(
+ *   tpose_global[i])), target_global[rt_body[i]]) with i = ancestor[b], the reduced-target node of b or of its nearest mapped
+ *   ancestor; local_rotation[b] = g(b) for a root, quat_mul_norm(inverse(g(parent)), g(b)) otherwise.  root_out = params[7..9]
+ *   + (rotate(R, root_translation[src row]) - rotate(R, params[4..6])) * scale.  tpose_global [n_mapped, 4]: the source
+ *   T-pose through ase_hip_retarget_fk and _chain; target_global [n_bodies, 4]: the target T-pose through _fk.
+ * ase_hip_retarget_hinge: project_joints from a table, roles [n_bodies, 6] = (role, upper, lower, end, bend sign, twist
+ *   sense): role 0 copies the body, 1 sets it to identity, 3 (lower body of a limb) stores the bend about y by
+ *   sign * |theta|, theta the angle at `lower` between the global positions of `upper` and `end`; 2 (upper body) stores
+ *   quat_mul(local[upper], twist) with the twist about the offset of `end` that takes the bent direction to the unprojected
+ *   one, positive where dir0.y <= 0 (sense -1, arms) or dir0.y >= 0 (sense +1, legs).  All limbs read the unprojected input.
+ * ase_hip_retarget_ground: min_z [n_clips], the minimum of global z over all frames and bodies of a clip; one block per clip,
+ *   a fixed comparison order, no atomics; a NaN wins.
+ * ase_hip_retarget_finish: root z + -min_z[clip] + params[11]; global_rotation / global_translation (f64) of the grounded
+ *   motion by forward kinematics on the target tree; rotation_out [n_frames, n_bodies, 4], root_out [n_frames, 3]: f32.
+ * ase_hip_retarget_velocity: velocity = gaussian(numpy.gradient(global_translation)) / (1.0 / fps) (central differences,
+ *   one-sided at a clip's ends); angular_velocity = gaussian(axis * angle / (1.0 / fps)) of quat_mul_norm(r[f + 1],
+ *   inverse(r[f])), zero at a clip's last frame (angle: acos(clamp(2 w^2 - 1)), axis / max(norm, 1e-9)).  gaussian: 17 taps,
+ *   sigma 2, indices clamped to the clip, added in the order of scipy's symmetric correlation (centre, then the pairs from
+ *   the outermost in).  Both f32 [n_frames, n_bodies, 3].
+ * Replaces: SkeletonState.retarget_to / _transfer_to / _remapped_to / local_rotation, SkeletonMotion.retarget_to_by_tpose,
+ *   from_skeleton_state, _compute_velocity, _compute_angular_velocity (poselib/skeleton/skeleton3d.py:462-482,706-713,757-784,
+ *   786-948,1090-1120,1223-1246,1345-1390); project_joints and main of poselib/retarget_motion.py:24-175,211-243. */
+int ase_hip_retarget_fk(const double* rotation, int mode, const int32_t* tree, int tree_ld, int n_bodies,
+                        const int32_t* clip_first, const int32_t* clip_num_frames, const int32_t* src_first,
+                        const int32_t* frame_clip, int n_clips, int n_frames, int n_src_frames, double* out, void* stream);
+int ase_hip_retarget_chain(const double* src_global, int n_src_bodies, const int32_t* rs_body, const int32_t* rs_parent,
+                           const int32_t* rt_src, const int32_t* rt_tree, int tree_ld, int n_mapped, const double* params,
+                           int n_frames, double* out, void* stream);
+int ase_hip_retarget_pose(const double* state_global, const double* tpose_global, const double* target_global,
+                          const double* root_translation, const double* params, const int32_t* rt_body,
+                          const int32_t* ancestor, const int32_t* parent_indices, int n_mapped, int n_bodies,
+                          const int32_t* clip_first, const int32_t* clip_num_frames, const int32_t* src_first,
+                          const int32_t* frame_clip, int n_clips, int n_frames, int n_src_frames, double* local_rotation,
+                          double* root_out, void* stream);
+int ase_hip_retarget_hinge(const double* local_rotation, const double* root_translation, const float* local_translation,
+                           const int32_t* tree, int tree_ld, const int32_t* roles, int n_bodies, int n_frames, double* out,
+                           void* stream);
+int ase_hip_retarget_ground(const double* local_rotation, const double* root_translation, const float* local_translation,
+                            const int32_t* tree, int tree_ld, int n_bodies, const int32_t* clip_first,
+                            const int32_t* clip_num_frames, int n_clips, int n_frames, double* min_z, void* stream);
+int ase_hip_retarget_finish(const double* local_rotation, const double* root_translation, const double* min_z,
+                            const double* params, const float* local_translation, const int32_t* tree, int tree_ld,
+                            int n_bodies, const int32_t* frame_clip, int n_clips, int n_frames, double* global_rotation,
+                            double* global_translation, float* rotation_out, float* root_out, void* stream);
+int ase_hip_retarget_velocity(const double* global_rotation, const double* global_translation, int n_bodies,
+                              const int32_t* clip_first, const int32_t* clip_num_frames, const double* clip_fps,
+                              const int32_t* frame_clip, int n_clips, int n_frames, float* velocity, float* angular_velocity,
+                              void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Launch programs: record a sequence of the calls above ONCE (nothing is launched while recording), replay it with 4-5 us
  * of host work per launch on the same HIP streams - the optimisation step as one call, with OUR branch -> stream mapping
