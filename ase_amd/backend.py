@@ -590,6 +590,54 @@ class HipBackend:
                                              float(h_min), float(h_max), float(speed_min), float(speed_max), float(noise),
                                              _ptr(slot_out), _ptr(ids_out), _ptr(draws_out), n, self._stream()), "proj_launch")
 
+    # ------------------------------------------------------------------ the view-motion task (N17)
+    def motion_sync(self, clips, motion_ids, progress_buf, reset_buf, terminate_buf, mode=L.MOTION_SYNC, motion_dt=0.0,
+                    root_states=None, dof_pos=None, dof_vel=None, body_pos=None, body_rot=None, body_vel=None, body_ang_vel=None,
+                    env_ids=None, ids_out=None):
+        """HumanoidViewMotion's per-step logic in one launch (operands: see ase_hip_motion_sync).  clips: the dict of
+        ``motion_state``; motion_ids int32 [n], progress_buf / reset_buf / terminate_buf int64 [n], all written in place.
+        mode L.MOTION_SYNC: reset_buf = progress_buf * motion_dt > clip length (strict), terminate_buf = 0, and the pose of
+        (motion_ids, progress_buf * motion_dt) written in place - root_states f32 [n, 13] at any row stride (its velocities
+        zeroed), dof_pos / dof_vel f32 [n, D] at any environment and element stride (dof_vel zeroed), and the optional
+        body_pos / body_vel / body_ang_vel [n, B, 3] and body_rot [n, B, 4] at their own strides: the clip's global arrays
+        blended by the sampler's two expressions, velocities zero.  mode L.MOTION_RESET: for the rows with reset_buf != 0, or
+        for env_ids (int32, distinct, -1: skip), motion_ids = (motion_ids + n) % num_motions and the three buffers cleared; no
+        state operand; ids_out int32 [n] (not with env_ids) receives e for a reset row and -1 elsewhere.  The entry takes raw
+        addresses: every tensor lives on the backend's device.  Recordable in a launch program."""
+        f32, i64, i32 = torch.float32, torch.int64, torch.int32
+        n = motion_ids.numel()
+        B, D, J = clips['gts'].shape[1], int(clips['dof_offsets'][-1]), len(clips['dof_body_ids'])
+        tensors = dict(motion_ids=motion_ids, progress_buf=progress_buf, reset_buf=reset_buf, terminate_buf=terminate_buf,
+                       root_states=root_states, dof_pos=dof_pos, dof_vel=dof_vel, body_pos=body_pos, body_rot=body_rot, body_vel=body_vel,
+                       body_ang_vel=body_ang_vel, env_ids=env_ids, ids_out=ids_out)
+        for who, t in tensors.items():
+            assert t is None or self._here(t), f"motion_sync: {who} must be a tensor on {self.device}, not {t.device}"
+        assert motion_ids.dtype == i32 and motion_ids.is_contiguous() and motion_ids.dim() == 1, "motion_sync: motion_ids contiguous int32 [n]"
+        bufs = [self._dense(t, n, i64, who) for t, who in ((progress_buf, 'progress_buf'), (reset_buf, 'reset_buf'),
+                                                           (terminate_buf, 'terminate_buf'))]
+        ids_out_p = self._dense(ids_out, n, i32, 'ids_out')
+        ids_p, n_ids = None, 0
+        if env_ids is not None:
+            assert env_ids.dtype == i32 and env_ids.is_contiguous() and env_ids.dim() == 1, "motion_sync: env_ids contiguous int32"
+            n_ids = env_ids.numel()
+            if n_ids == 0:                                    # an empty tensor has no storage: an empty list resets nothing
+                return
+            ids_p = _ptr(env_ids)
+        rs, rs_stride = self._state_rows(root_states, n, 13, 'root_states')
+        dofs = []
+        for t, who in ((dof_pos, 'dof_pos'), (dof_vel, 'dof_vel')):
+            assert t is None or (t.dtype == f32 and tuple(t.shape) == (n, D)), f"motion_sync: {who} f32 [{n}, {D}]"
+            dofs += [None, 0, 0] if t is None else [_ptr(t), int(t.stride(0)), int(t.stride(1))]
+        bodies = []
+        for t, w, who in ((body_pos, 3, 'body_pos'), (body_rot, 4, 'body_rot'), (body_vel, 3, 'body_vel'), (body_ang_vel, 3, 'body_ang_vel')):
+            bodies += [None, 0, 0] if t is None else list(self._state_view(t, (n, B, w), who))
+        ia = lambda xs: self._id_array(xs)[0]
+        L.check(self.lib.ase_hip_motion_sync(int(mode), _ptr(clips['gts']), _ptr(clips['grs']), _ptr(clips['lrs']), B, _ptr(clips['lengths']),
+                                             _ptr(clips['num_frames']), _ptr(clips['dt']), _ptr(clips['length_starts']),
+                                             clips['lengths'].numel(), ia(clips['dof_body_ids']), ia(clips['dof_offsets']), J,
+                                             _ptr(motion_ids), bufs[0], float(motion_dt), bufs[1], bufs[2], rs, rs_stride, *dofs, *bodies,
+                                             ids_p, n_ids, ids_out_p, n, self._stream()), "motion_sync")
+
     # ------------------------------------------------------------------ renewals of the ASE latents (N9)
     def latent_renew(self, latents, env_ids=None, eps=None, steps=None, rng_state=None, advance=True, progress_buf=None,
                      reset_steps=None, steps_add=False, steps_low=0, steps_high=1, z2=None):

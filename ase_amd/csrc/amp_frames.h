@@ -44,22 +44,6 @@ __device__ __forceinline__ FrameBlend motion_blend(const MotionClips& a, int mid
     const int i1 = min(i0 + 1, nf - 1);
     return FrameBlend{i0 + a.length_starts[mid], i1 + a.length_starts[mid], (t - (float)i0 * dt) / dt};
 }
-// root position (lerp), rotation (slerp) and the two root velocities (unblended, frame 0 of the pair)
-__device__ __forceinline__ void motion_root(const MotionClips& a, const FrameBlend& fb, float* root_pos, float* root_rot,
-                                            float* root_vel, float* root_ang_vel) {
-    const float blend = fb.blend;
-    const float* p0 = a.gts + fb.f0 * a.B * 3;
-    const float* p1 = a.gts + fb.f1 * a.B * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) root_pos[c] = (1.f - blend) * p0[c] + blend * p1[c];
-    const Q4 rr = slerp(load_q(a.grs + fb.f0 * a.B * 4), load_q(a.grs + fb.f1 * a.B * 4), blend);
-    root_rot[0] = rr.x; root_rot[1] = rr.y; root_rot[2] = rr.z; root_rot[3] = rr.w;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        root_vel[c] = a.grvs[fb.f0 * 3 + c];
-        root_ang_vel[c] = a.gravs[fb.f0 * 3 + c];
-    }
-}
 // world position of body b (amp_demo.hip keeps a key-body table longer than kMaxJoints)
 __device__ __forceinline__ void motion_body(const MotionClips& a, const FrameBlend& fb, int b, float* out) {
     const float blend = fb.blend;
@@ -67,6 +51,22 @@ __device__ __forceinline__ void motion_body(const MotionClips& a, const FrameBle
     const float* p1 = a.gts + fb.f1 * a.B * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[c] = (1.f - blend) * p0[b * 3 + c] + blend * p1[b * 3 + c];
+}
+// world rotation of body b: the root rotation's expression (slerp of the frame pair's global rotations) on body b's rows
+__device__ __forceinline__ void motion_body_rot(const MotionClips& a, const FrameBlend& fb, int b, float* out) {
+    const Q4 rr = slerp(load_q(a.grs + (fb.f0 * a.B + b) * 4), load_q(a.grs + (fb.f1 * a.B + b) * 4), fb.blend);
+    out[0] = rr.x; out[1] = rr.y; out[2] = rr.z; out[3] = rr.w;
+}
+// root position (lerp), rotation (slerp) and the two root velocities (unblended, frame 0 of the pair): body 0's pose
+__device__ __forceinline__ void motion_root(const MotionClips& a, const FrameBlend& fb, float* root_pos, float* root_rot,
+                                            float* root_vel, float* root_ang_vel) {
+    motion_body(a, fb, 0, root_pos);
+    motion_body_rot(a, fb, 0, root_rot);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        root_vel[c] = a.grvs[fb.f0 * 3 + c];
+        root_ang_vel[c] = a.gravs[fb.f0 * 3 + c];
+    }
 }
 // world position of key body k
 __device__ __forceinline__ void motion_key(const MotionClips& a, const FrameBlend& fb, int k, float* out) {

@@ -40,7 +40,7 @@ The physics protocol - what an Isaac-Gym-like binding supplies:
 
 ``PlaybackPhysics`` is the stand-in of the tests and the benchmark: it replays recorded frames in the packed simulator layout
 and invents no dynamics.  A real simulator binding, ``_generate_fall_states``, ``_update_marker``,
-``humanoid_view_motion``, the ``dr_randomizations`` hooks and rendering are out of scope.
+the ``dr_randomizations`` hooks and rendering are out of scope (``humanoid_view_motion`` is ``ase_amd/view_motion.py``).
 
 ``perturb=True`` (or a dict of ``perturb.ProjectileLauncher`` arguments) makes the environment the reference's
 ``HumanoidPerturb``: a HumanoidAMP whose ``post_physics_step`` first launches the projectile that is due - by the counter of

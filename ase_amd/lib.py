@@ -25,6 +25,7 @@ RESET_HAS_TABLE, RESET_HAS_MOTION = 1, 2                            # ASE_RESET_
 KIND_U8, KIND_I32, KIND_I64, KIND_F32 = range(4)                    # ASE_KIND_*: the flag vectors of ase_hip_rollout_store
 ROLLOUT_STORE_MAX_FIELDS, ROLLOUT_STORE_ROWS = 16, 8                # ASE_ROLLOUT_STORE_*
 PROJ_DRAWS, PROJ_MAX_SLOTS = 7, 32                                  # ASE_PROJ_*: draws per row / slots of ase_hip_proj_launch
+MOTION_SYNC, MOTION_RESET, MOTION_SYNC_MAX_BODIES = 0, 1, 64              # ASE_MOTION_*: the modes of ase_hip_motion_sync
 INIT_DEFAULT, INIT_START, INIT_RANDOM, INIT_HYBRID = range(4)       # ASE_INIT_*: the state initialisation of ase_hip_amp_reset_due
 
 # accumulator slots (ASE_ACC_*)
@@ -100,6 +101,8 @@ SIGNATURES = {
     "ase_hip_task_reset": [_i, _p, _i, _p, _p, _p, _i, _p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p, _i64] + [_d] * 8 + [_i, _i, _p],
     "ase_hip_proj_launch": [_p, _p, _i, _i, _p, _i, _p, _p, _p, _i, _p, _i64, _p, _i64, _i64, _p, _i64, _i64, _i, _i, _p, _i64, _i64]
                            + [_d] * 7 + [_p, _p, _p, _i, _p],
+    "ase_hip_motion_sync": [_i, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _d, _p, _p, _p, _i64, _p, _i64, _i64, _p, _i64, _i64]
+                           + [_p, _i64, _i64] * 4 + [_p, _i, _p, _i, _p],
     "ase_hip_latent_renew": [_p, _i, _p, _i64, _p, _p, _i, _p, _i, _p, _i, _i64, _i64, _p, _i64, _p, _i64, _i, _i, _i, _p],
     "ase_hip_amp_reset": [_p] * 6 + [_i] + [_p] * 6 + [_i, _p, _i] + [_p] * 5 + [_i, _i, _p, _p, _p, _i, _p, _i64, _p, _p, _i64, _i,
                           _p, _p, _p, _p, _i, _i, _i, _f, _p, _i, _p],

@@ -51,6 +51,12 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
                                                       HumanoidPerturb._update_proj: the schedule test on progress_buf[0], the
                                                       draws and the projectile's root-state row in one launch
                                                       (env/tasks/humanoid_perturb.py:172-213)
+  motion_sync(mode, motion_ids, progress_buf, reset_buf, terminate_buf, motion_dt, root_states, dof_pos, dof_vel, body_pos,
+              body_rot, body_vel, body_ang_vel, env_ids, ids_out, gts, grs, lrs, lengths, num_frames, clip_dt, length_starts,
+              dof_body_ids, dof_offsets) -> ()        (the four buffers, the state tensors and ids_out written in place)
+                                                      HumanoidViewMotion._motion_sync + compute_view_motion_reset ('sync') and
+                                                      _reset_env_tensors ('reset') in one launch each
+                                                      (env/tasks/humanoid_view_motion.py:44-97)
   latent_renew(latents, env_ids, eps, steps, rng_state, advance, progress_buf, reset_steps, steps_add, steps_low, steps_high, z2) -> ()
                                                       (latents, reset_steps, rng_state, z2 written in place)
                                                       ASEAgent._reset_latents + _reset_latent_step_count / _update_latents and
@@ -721,6 +727,41 @@ def proj_launch(root_states: torch.Tensor, body_pos: torch.Tensor, body_vel: tor
 @proj_launch.register_fake
 def _(root_states, body_pos, body_vel, proj_states, progress_buf, timesteps, slot, env_ids, u, eps, rng_state, advance, tar_body,
       ranges, noise, slot_out, ids_out, draws_out):
+    return None
+
+
+@torch.library.custom_op('ase_hip::motion_sync', mutates_args=('motion_ids', 'progress_buf', 'reset_buf', 'terminate_buf', 'root_states',
+                                                                'dof_pos', 'dof_vel', 'body_pos', 'body_rot', 'body_vel', 'body_ang_vel',
+                                                                'ids_out'), device_types='cuda')
+def motion_sync(mode: str, motion_ids: torch.Tensor, progress_buf: torch.Tensor, reset_buf: torch.Tensor, terminate_buf: torch.Tensor,
+                motion_dt: float, root_states: torch.Tensor | None, dof_pos: torch.Tensor | None, dof_vel: torch.Tensor | None,
+                body_pos: torch.Tensor | None, body_rot: torch.Tensor | None, body_vel: torch.Tensor | None,
+                body_ang_vel: torch.Tensor | None, env_ids: torch.Tensor | None, ids_out: torch.Tensor | None, gts: torch.Tensor,
+                grs: torch.Tensor, lrs: torch.Tensor, lengths: torch.Tensor, num_frames: torch.Tensor, clip_dt: torch.Tensor,
+                length_starts: torch.Tensor, dof_body_ids: list[int], dof_offsets: list[int]) -> None:
+    """The view-motion task's step ('sync') or reset ('reset') in one launch (operands: see ase_hip_motion_sync).  'sync': the
+    end-of-clip test on progress_buf * motion_dt and the sampled pose written in place into root_states / dof_pos / dof_vel and
+    the optional rigid-body tensors, at their own strides.  'reset': the rows with reset_buf != 0, or env_ids, move on to their
+    next clip; no state tensor.  Every tensor is passed by position, None where the mode has none."""
+    _check(mode in ('sync', 'reset'), "motion_sync: mode is 'sync' or 'reset'")
+    for name, t, dt in (('motion_ids', motion_ids, torch.int32), ('progress_buf', progress_buf, torch.int64),
+                        ('reset_buf', reset_buf, torch.int64), ('terminate_buf', terminate_buf, torch.int64),
+                        ('root_states', root_states, torch.float32), ('dof_pos', dof_pos, torch.float32), ('dof_vel', dof_vel, torch.float32),
+                        ('body_pos', body_pos, torch.float32), ('body_rot', body_rot, torch.float32), ('body_vel', body_vel, torch.float32),
+                        ('body_ang_vel', body_ang_vel, torch.float32), ('env_ids', env_ids, torch.int32), ('ids_out', ids_out, torch.int32),
+                        ('gts', gts, torch.float32), ('grs', grs, torch.float32), ('lrs', lrs, torch.float32), ('lengths', lengths, torch.float32),
+                        ('num_frames', num_frames, torch.int32), ('clip_dt', clip_dt, torch.float32), ('length_starts', length_starts, torch.int32)):
+        _check(t is None or t.dtype == dt, f'motion_sync: {name} must be {dt}')
+    _check(gts.dim() == 3 and gts.is_contiguous() and grs.is_contiguous() and lrs.is_contiguous(), 'motion_sync: contiguous clip tensors')
+    clips = dict(gts=gts, grs=grs, lrs=lrs, lengths=lengths, num_frames=num_frames, dt=clip_dt, length_starts=length_starts,
+                 dof_body_ids=dof_body_ids, dof_offsets=dof_offsets)
+    _backend().motion_sync(clips, motion_ids, progress_buf, reset_buf, terminate_buf, L.MOTION_SYNC if mode == 'sync' else L.MOTION_RESET,
+                           motion_dt, root_states, dof_pos, dof_vel, body_pos, body_rot, body_vel, body_ang_vel, env_ids, ids_out)
+
+
+@motion_sync.register_fake
+def _(mode, motion_ids, progress_buf, reset_buf, terminate_buf, motion_dt, root_states, dof_pos, dof_vel, body_pos, body_rot, body_vel,
+      body_ang_vel, env_ids, ids_out, gts, grs, lrs, lengths, num_frames, clip_dt, length_starts, dof_body_ids, dof_offsets):
     return None
 
 

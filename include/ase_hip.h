@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_gemm_nt_stacked, ase_hip_disc_head_v2, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_proj_launch, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id, ase_hip_rollout_store, ase_hip_hrl_latent / ase_hip_hrl_llc_action / ase_hip_hrl_accum and ase_hip_env_pre_step / ase_hip_env_post_step were added WITHOUT a new version
+/* (ase_hip_gemm_nt_ex, ase_hip_gemm_nt_stacked, ase_hip_disc_head_v2, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_proj_launch, ase_hip_motion_sync, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id, ase_hip_rollout_store, ase_hip_hrl_latent / ase_hip_hrl_llc_action / ase_hip_hrl_accum and ase_hip_env_pre_step / ase_hip_env_post_step were added WITHOUT a new version
  *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
  *  load time) */
 #define ASE_HIP_ABI_VERSION 9
@@ -931,6 +931,48 @@ int ase_hip_proj_launch(const int64_t* progress_buf, const int32_t* timesteps, i
                         int64_t vel_se, int64_t vel_sb, int n_bodies, int tar_body, float* proj_states, int64_t ld_env,
                         int64_t ld_slot, double dist_min, double dist_max, double h_min, double h_max, double speed_min,
                         double speed_max, double noise, int32_t* slot_out, int32_t* ids_out, float* draws_out, int n_envs,
+                        void* stream);
+
+/* The view-motion task (an addition to ABI 9, nothing else changed): the per-step logic of HumanoidViewMotion in
+ * ONE launch, one lane per environment on a fixed grid over all n_envs, no host read, no intermediate tensor; recordable.
+ * motion_ids (DEVICE int32 [n_envs]), progress_buf, reset_buf, terminate_buf (DEVICE int64 [n_envs]) are the task's buffers.
+ * mode ASE_MOTION_SYNC = _compute_reset + _motion_sync, per environment e with m = motion_ids[e]:
+ *   t = (float)progress_buf[e] * (float)motion_dt - torch's product of an integer tensor and a Python float: the counter is
+ *       rounded to f32 (exact below 2^24), motion_dt (the f64 product controlFrequencyInv * sim dt) is rounded to f32 ONCE, on
+ *       the host, and the product is one f32 multiplication
+ *   reset_buf[e] = t > lengths[m] (strict), terminate_buf[e] = 0
+ *   the pose of (m, t) by the sampler of ase_hip_motion_state (the same device functions, the same bits):
+ *   root_states + e * ld_root (ld_root >= 13): position, rotation, then six +0.0 for the two velocities - the humanoid's row of
+ *       the packed root tensor, whatever actors lie beside it
+ *   dof_pos + e * dp_se + d * dp_sd = the dof positions, dof_vel + e * dv_se + d * dv_sd = +0.0 (strides in floats; Isaac Gym's
+ *       interleaved dof state [n, D, 2] is element stride 2)
+ *   optional (NULL: skipped) rigid-body outputs at + e * se + b * sb: body_pos [n, B, 3] = body b's global translation of the
+ *       frame pair, blended by the key-body expression; body_rot [n, B, 4] = body b's global rotation of the frame pair, blended
+ *       by the root rotation's expression (slerp); body 0 is bitwise the root row.  body_vel / body_ang_vel [n, B, 3] = +0.0.
+ *       These are the clip's own arrays: no forward kinematics runs.
+ *   env_ids, ids_out: NULL.  Every other element of every operand is untouched.
+ * mode ASE_MOTION_RESET = _reset_env_tensors, for every e with reset_buf[e] != 0 (env_ids NULL) or for the rows env_ids (DEVICE
+ *   int32 [n_ids], DISTINCT, n_ids <= n_envs; -1 and ids outside [0, n_envs) are skipped and never dereferenced):
+ *   motion_ids[e] = (motion_ids[e] + n_envs) mod num_motions, progress_buf[e] = reset_buf[e] = terminate_buf[e] = 0.
+ *   It writes NO state (every state and clip operand NULL / ignored): the reference's override does not call the base class's
+ *   indexed set, so a reset environment shows the old clip's last pose until the next ASE_MOTION_SYNC.
+ *   ids_out (nullable, not with env_ids) int32 [n_envs], EVERY element written: e where environment e was reset, -1 elsewhere -
+ *   the full-length id list of ase_hip_amp_reset_due.
+ * In both modes a row whose motion_ids[e] is outside [0, num_motions) writes nothing to the buffers (ids_out[e] = -1).
+ * Host checks: dof_offsets[0] == 0, joints of 1 or 3 dofs on bodies in range, n_bodies <= ASE_MOTION_SYNC_MAX_BODIES,
+ * n_joints <= 32, num_motions >= 1, strides that cover the widths.
+ * Replaces: HumanoidViewMotion._motion_sync, _compute_reset / compute_view_motion_reset, _reset_env_tensors
+ * (env/tasks/humanoid_view_motion.py:44-97) but the two indexed set calls. */
+enum { ASE_MOTION_SYNC = 0, ASE_MOTION_RESET = 1 };
+#define ASE_MOTION_SYNC_MAX_BODIES 64
+int ase_hip_motion_sync(int mode, const float* gts, const float* grs, const float* lrs, int n_bodies, const float* lengths,
+                        const int32_t* num_frames, const float* dt, const int32_t* length_starts, int num_motions,
+                        const int32_t* dof_body_ids, const int32_t* dof_offsets, int n_joints, int32_t* motion_ids,
+                        int64_t* progress_buf, double motion_dt, int64_t* reset_buf, int64_t* terminate_buf,
+                        float* root_states, int64_t ld_root, float* dof_pos, int64_t dp_se, int64_t dp_sd, float* dof_vel,
+                        int64_t dv_se, int64_t dv_sd, float* body_pos, int64_t bp_se, int64_t bp_sb, float* body_rot,
+                        int64_t br_se, int64_t br_sb, float* body_vel, int64_t bv_se, int64_t bv_sb, float* body_ang_vel,
+                        int64_t ba_se, int64_t ba_sb, const int32_t* env_ids, int n_ids, int32_t* ids_out, int n_envs,
                         void* stream);
 
 /* Renewals of the ASE agent's per-environment latents (an addition to ABI 9, nothing else changed): new unit
