@@ -896,6 +896,56 @@ class HipBackend:
                                                0 if workspace is None else workspace.numel(), _ptr(done_ids_out), n, int(slot),
                                                _ptr(slot_dev), int(n_slots), self._stream()), "rollout_store")
 
+    # ------------------------------------------------------------------ the head of a rollout step (N18)
+    def rollout_head(self, obs, z=None, mean=None, std=None, xa=None, xc=None, zc=None, zs=None, obses_out=None, z_out=None,
+                     slot=0, slot_dev=None):
+        """The head of one environment step in one launch (operands: see ase_hip_rollout_head).  obs f32 [n, D] and z f32
+        [n, Z] (optional) are read at their own pitch.  xa / xc [n, >= D] receive the eval-mode normalisation of obs with
+        mean / std f32 [D] (columns beyond D untouched), zc / zs [n, >= Z] the latents converted as gather_rows converts them;
+        the four share one dtype (f32 / bf16 / f16).  obses_out f32 [n_slots, n, D] and z_out f32 [n_slots, n, Z] receive the
+        raw rows of slot `slot`, or of the int32 [1] device word slot_dev read when the launch runs (a word outside the
+        buffer: the whole call writes nothing).  Every output is optional, one is required; every tensor has unit column
+        stride and lives on the backend's device (the entry takes raw addresses).  Recordable in a launch program."""
+        f32 = torch.float32
+        for who, t in dict(obs=obs, z=z, mean=mean, std=std, xa=xa, xc=xc, zc=zc, zs=zs, obses_out=obses_out, z_out=z_out,
+                           slot_dev=slot_dev).items():
+            assert t is None or self._here(t), f"rollout_head: {who} must be a tensor on {self.device}, not {t.device}"
+        assert obs.dim() == 2 and obs.dtype == f32 and obs.stride(1) == 1, "rollout_head: obs f32 [n, D], unit column stride"
+        n, D = obs.shape
+        Z = 0
+        if z is not None:
+            assert z.dim() == 2 and z.dtype == f32 and z.shape[0] == n and z.stride(1) == 1, "rollout_head: z f32 [n, Z], unit column stride"
+            Z = z.shape[1]
+        for who, t in (('mean', mean), ('std', std)):
+            assert t is None or (t.dtype == f32 and t.numel() == D and t.is_contiguous()), f"rollout_head: {who} contiguous f32 [D]"
+        xs = [t for t in (xa, xc, zc, zs) if t is not None]
+        assert all(t.dtype == xs[0].dtype for t in xs), "rollout_head: xa / xc / zc / zs share one dtype"
+        for who, t, w in (('xa', xa, D), ('xc', xc, D), ('zc', zc, Z), ('zs', zs, Z)):
+            assert t is None or (t.dim() == 2 and t.shape[0] == n and t.shape[1] >= w and t.stride(1) == 1), \
+                f"rollout_head: {who} [n, >= {w}], unit column stride"
+        n_slots = 1
+        for who, t, w in (('obses_out', obses_out, D), ('z_out', z_out, Z)):
+            if t is not None:
+                assert t.dtype == f32 and t.dim() == 3 and tuple(t.shape[1:]) == (n, w) and t.stride(2) == 1, \
+                    f"rollout_head: {who} f32 [n_slots, n, {w}], unit column stride"
+                n_slots = t.shape[0]
+        assert obses_out is None or z_out is None or obses_out.shape[0] == z_out.shape[0], "rollout_head: outputs disagree on n_slots"
+        assert slot_dev is None or (slot_dev.dtype == torch.int32 and slot_dev.numel() == 1), "rollout_head: slot_dev int32 [1]"
+        # (the row stride of a one-row view means nothing - 0 or 1 after a select or an expand: its width stands in for it)
+        ld = lambda t: 0 if t is None else (max(int(t.stride(0)), int(t.shape[1])) if n == 1 else int(t.stride(0)))
+        sl = lambda t: (None, 0, 0) if t is None else (_ptr(t), max(int(t.stride(1)), int(t.shape[2])) if n == 1 else int(t.stride(1)),
+                                                       int(t.stride(0)))
+        L.check(self.lib.ase_hip_rollout_head(_ptr(obs), ld(obs), D, _ptr(z), ld(z), Z, _ptr(mean), _ptr(std), _ptr(xa), ld(xa),
+                                              _ptr(xc), ld(xc), _ptr(zc), ld(zc), _ptr(zs), ld(zs),
+                                              _code(xs[0].dtype) if xs else L.F32, *sl(obses_out), *sl(z_out), n, int(slot),
+                                              _ptr(slot_dev), n_slots, self._stream()), "rollout_head")
+
+    def word_step(self, word, add=1, wrap=0):
+        """word[0] = (word[0] + add) mod wrap on the device, one lane (wrap <= 0: no modulo): the step counter of a recorded
+        rollout step, the word rollout_store and rollout_head read their slot from.  word: int32 [1] on the backend's device."""
+        assert self._here(word) and word.dtype == torch.int32 and word.numel() == 1, f"word_step: word int32 [1] on {self.device}"
+        L.check(self.lib.ase_hip_word_step(_ptr(word), int(add), int(wrap), self._stream()), "word_step")
+
     def _here(self, t):
         """Whether a tensor lives on this backend's GPU (a device given without an index is the current one)."""
         return t.is_cuda and t.device.index == (torch.cuda.current_device() if self.device.index is None else self.device.index)

@@ -276,26 +276,61 @@ class ForwardEngine:
         self._fwd_scr('Hs', self.style[:-1], self.style[-1], self.style_input(n), n, Xa[:, a0.split_dst:])
         return self._fwd_scr('Ha', self.actor, self.mu_head, Xa, n, 'MU')
 
-    def _policy_nets(self, obs, z, normalize, want_mu, want_value):
+    def rollout_stats(self):
+        """Eval mean / std of the observation normaliser for the steps of ONE rollout, in persistent buffers of their own
+        (their addresses are baked into a recorded rollout step): the statistics do not change inside a rollout - play_steps
+        begins with set_eval, and rms_finalize without sums is a pure function of the state - so a caller computes them once,
+        before the first step, and nothing inside the recording re-finalises them.  Without input normalisation: 0 / 1."""
+        hit = self._scratch.get('rollout_stats')
+        if hit is None:
+            hit = self._scratch['rollout_stats'] = (torch.zeros(1, self.obs, dtype=torch.float32, device=self.dev),
+                                                    torch.ones(1, self.obs, dtype=torch.float32, device=self.dev))
+        if self.cfg.get('normalize_input', True):
+            self.be.rms_finalize(self.obs_state, self.obs, None, 0, 0, hit[0], hit[1])
+        return hit[0][0], hit[1][0]
+
+    def rollout_head(self, obs, z, mean, std, obses_out=None, latents_out=None, slot=0, slot_dev=None, critic_only=False):
+        """The persistent Xa / Xc / Zs scratch of _policy_nets filled by ONE rollout_head launch from raw observations
+        [n, obs] and the latents z [n, z] (None without a latent): the normalisation with mean / std (rollout_stats) into the
+        actor's and the critic's input, the latents into the critic's concat block and the style input, and - obses_out
+        [H, n, obs], latents_out [H, n, z] - the raw rows into experience slot `slot` / the device word slot_dev.
+        critic_only: Xc and its concat block alone (the _next_values pass).  policy_act / policy_forward(inputs_ready=True)
+        run the chains on what this call wrote."""
+        n, a0 = obs.shape[0], self.actor[0]
+        Xc = self._scr('Xc', n, a0.k_pad)
+        zc = Xc[:, a0.split_dst:] if self.z else None
+        if critic_only:
+            self.be.rollout_head(obs, z if self.z else None, mean, std, xc=Xc, zc=zc)
+            return
+        Xa = self._scr('Xa', n, a0.k_pad)
+        zs = self._scr('Zs', n, P(self.z)) if self.style else None
+        self.be.rollout_head(obs, z if self.z else None, mean, std, xa=Xa, xc=Xc, zc=zc, zs=zs, obses_out=obses_out,
+                             z_out=latents_out if self.z else None, slot=slot, slot_dev=slot_dev)
+
+    def _policy_nets(self, obs, z, normalize, want_mu, want_value, inputs_ready=False):
         """Eval-mode observation normalisation + actor / critic forward on raw observations [n, obs].  Returns the padded
-        head outputs (MU f32 [n, P(act)] before any tanh, V f32 [n, 64]); every buffer is persistent scratch."""
+        head outputs (MU f32 [n, P(act)] before any tanh, V f32 [n, 64]); every buffer is persistent scratch.
+        inputs_ready: Xa / Xc / Zs already hold this step's inputs (rollout_head wrote them): no _eval_stats, no
+        rms_normalize, no gather_rows - the chains alone; obs gives the row count only."""
         be, n = self.be, obs.shape[0]
         f32 = torch.float32
         a0 = self.actor[0]
         Xa, Xc = self._scr('Xa', n, a0.k_pad), self._scr('Xc', n, a0.k_pad)
-        if normalize and self.cfg.get('normalize_input', True):
-            mean, std = self._eval_stats(self.obs_state, self.obs, 'obs')
-        else:
-            mean, std = self._scr('one_m', 1, self.obs, f32)[0].zero_(), self._scr('one_s', 1, self.obs, f32)[0].fill_(1.0)
-        be.rms_normalize(obs, self.obs, None, (0, 0), n, mean, std, [Xa, Xc])
+        if not inputs_ready:
+            if normalize and self.cfg.get('normalize_input', True):
+                mean, std = self._eval_stats(self.obs_state, self.obs, 'obs')
+            else:
+                mean, std = self._scr('one_m', 1, self.obs, f32)[0].zero_(), self._scr('one_s', 1, self.obs, f32)[0].fill_(1.0)
+            be.rms_normalize(obs, self.obs, None, (0, 0), n, mean, std, [Xa, Xc])
         MU = V = None
-        if self.z:
+        if self.z and not inputs_ready:
             sd = a0.split_dst
             be.gather_rows(z, self.z, None, (0, 0), n, Xc[:, sd:])
         if want_mu:
             if self.style:
                 Zs = self._scr('Zs', n, P(self.z))
-                be.gather_rows(z, self.z, None, (0, 0), n, Zs)
+                if not inputs_ready:
+                    be.gather_rows(z, self.z, None, (0, 0), n, Zs)
                 self._fwd_scr('Hs', self.style[:-1], self.style[-1], Zs, n, Xa[:, a0.split_dst:])
             MU = self._fwd_scr('Ha', self.actor, self.mu_head, Xa, n, 'MU')
         if want_value:
@@ -317,12 +352,14 @@ class ForwardEngine:
             return MU[:, off:off + self.act]
         return self.logstd
 
-    def policy_forward(self, obs, z=None, normalize=True, unnorm_value=True, want=('mu', 'value')):
+    def policy_forward(self, obs, z=None, normalize=True, unnorm_value=True, want=('mu', 'value'), inputs_ready=False):
         """Eval-mode actor / critic on raw observations [n, obs] (learning/ase_agent.py:117-148,385-393):
         eval-mode obs normalisation -> nets -> (mu [n, act], value [n, 1] un-normalised).  The returned tensors are
-        persistent scratch, overwritten by the next call with the same n."""
+        persistent scratch, overwritten by the next call with the same n.  inputs_ready: the input buffers were filled by
+        rollout_head, the call runs the chains alone (_policy_nets); unset, the call sequence is exactly what it was before
+        the argument existed."""
         n = obs.shape[0]
-        MU, V = self._policy_nets(obs, z, normalize, 'mu' in want or 'logstd' in want, 'value' in want)
+        MU, V = self._policy_nets(obs, z, normalize, 'mu' in want or 'logstd' in want, 'value' in want, inputs_ready)
         out = {}
         if 'mu' in want:
             mu = self._scr('mu_out', n, self.act, torch.float32)
@@ -339,12 +376,14 @@ class ForwardEngine:
             out['value'] = self._value_out(V, n, unnorm_value)
         return out
 
-    def policy_act(self, obs, z, rand_probs, rng_state):
+    def policy_act(self, obs, z, rand_probs, rng_state, inputs_ready=False):
         """One rollout step of get_action_values (learning/amp_agent.py:139-169, learning/ase_agent.py:117-148) as an
         explicit launch sequence: normalise -> actor + critic -> ase_hip_sample_actions (tanh / Normal sample / neglogp /
-        eps-greedy on device) -> value un-normalisation.  rand_probs None: every row stochastic (plain PPO)."""
+        eps-greedy on device) -> value un-normalisation.  rand_probs None: every row stochastic (plain PPO).
+        inputs_ready: the input buffers were filled by rollout_head, the normalise step is skipped (_policy_nets); unset, the
+        call sequence is exactly what it was before the argument existed."""
         n, f32 = obs.shape[0], torch.float32
-        MU, V = self._policy_nets(obs, z, True, True, True)
+        MU, V = self._policy_nets(obs, z, True, True, True, inputs_ready)
         o = {k: self._scr('act_' + k, n, c, f32) for k, c in (('mus', self.act), ('sigmas', self.act), ('actions', self.act),
                                                              ('neglogpacs', 1), ('rand_action_mask', 1))}
         kw = dict(logstd_rows=True) if self.sigma_mode == 'head' else {}

@@ -202,6 +202,13 @@ class CommonAgent:
         self._device_rollout = bool(config.get('device_rollout', False))
         if self._device_rollout:
             self._check_device_rollout()
+        # opt-in: one environment step recorded ONCE as a launch program of the library and replayed horizon_length times, the
+        # experience slot in a device word (_play_steps_program)
+        self._rollout_program = bool(config.get('rollout_program', False))
+        self._rp = self._rp_notes = None
+        if self._rollout_program:
+            assert self._device_rollout, "rollout_program needs device_rollout: True (the step it records is _play_steps_device's)"
+            self._check_rollout_program()
         self.writer = config.get('writer', None) or ScalarLog()
         self.is_tensor_obses = True
         self._load_config_params(config)
@@ -227,6 +234,9 @@ class CommonAgent:
             from ..backend import HipBackend
             backend = HipBackend(self.ppo_device, x3=(precision == 'bf16x3'))
         self.backend = backend
+        if self._rollout_program:
+            for entry in ('prog_begin', 'rollout_head', 'word_step'):
+                assert hasattr(backend, entry), f"rollout_program needs a backend with {entry}"
         self.engine = UpdateEngine(self.kind, self.model.a2c_network, config, backend, minibatch=self.minibatch_size,
                                    amp_minibatch=getattr(self, '_amp_minibatch_size', 0), dtype=dtype,
                                    world_size=self.world_size, rank=self.rank, dp_mode=self.dp_mode,
@@ -283,6 +293,20 @@ class CommonAgent:
         assert self.num_agents == 1 and self.value_size == 1, "device_rollout: num_agents == 1 and value_size == 1"
         assert type(self.algo_observer) is _NullObserver or getattr(self.algo_observer, 'accepts_done_ids', False), \
             "device_rollout: process_infos receives the device id list (e / -1), the observer must declare accepts_done_ids = True"
+
+    def _on_agent_device(self, t):
+        dev = torch.device(self.ppo_device)
+        if t.device.type != dev.type:
+            return False
+        return dev.type != 'cuda' or t.device.index == (torch.cuda.current_device() if dev.index is None else dev.index)
+
+    def _check_rollout_program(self):
+        """What config['rollout_program'] needs of the environment, refused at construction: a recorded step bakes addresses
+        in, so everything the environment hands over lives on the agent's device."""
+        env = getattr(self.vec_env, 'env', self.vec_env)
+        dev = getattr(env, 'device', None)
+        assert dev is None or self._on_agent_device(torch.empty(0, device=dev)), \
+            f"rollout_program: the environment is on {dev}, the agent on {self.ppo_device} - a recorded step reads the environment's tensors in place"
 
     def _randperm(self, n):
         return torch.randperm(n, device=self.ppo_device, generator=self._gen).to(torch.int32)
@@ -351,6 +375,9 @@ class CommonAgent:
                 for prog in g['graphs']:
                     self.backend.prog_destroy(prog)
         self._graphs = {}
+        if getattr(self, '_rp', None) is not None:               # the recorded rollout step has the experience buffers baked in too
+            self.backend.prog_destroy(self._rp['prog'])
+        self._rp = self._rp_notes = None
 
     def init_tensors(self):
         H, N, dev = self.horizon_length, self.num_actors * self.num_agents, self.ppo_device
@@ -583,6 +610,8 @@ class CommonAgent:
                     self.experience[k].copy_(v.to(self.ppo_device))
             return self._play_steps_tail()
         if self._device_rollout:
+            if self._rollout_program:
+                return self._play_steps_program() if self._rp_notes is not None else self._play_steps_noting()
             return self._play_steps_device()
         E = self.experience
         done_indices = []
@@ -654,6 +683,156 @@ class CommonAgent:
                              done_ids_out=self._done_ids)
             self.algo_observer.process_infos(infos, self._done_ids)
             done_mask = self.dones
+        self._meter_host.written()
+        return self._play_steps_tail()
+
+    # ---- config['rollout_program']: the step above recorded once as a launch program ------------------------------------------
+    def _play_steps_noting(self):
+        """The first rollout after construction or _drop_graphs: _play_steps_device itself, with shape, dtype and address of
+        everything env_step returns noted on the way - recording executes nothing, so a program cannot learn them, and the
+        environment is not stepped an extra time to find out.  The next rollout records the program."""
+        seen, env_step = {}, self.env_step
+
+        def noting_step(actions):
+            out = env_step(actions)
+            for k, t in self._step_results(*out).items():
+                first = seen.setdefault(k, dict(t=t, ptr=t.data_ptr(), calls=0, stable=True))
+                first.update(t=t, calls=first['calls'] + 1, stable=first['stable'] and t.data_ptr() == first['ptr'])
+            return out
+        self.env_step = noting_step
+        try:
+            out = self._play_steps_device()
+        finally:
+            del self.env_step
+        for k, e in seen.items():
+            assert self._on_agent_device(e['t']), \
+                f"rollout_program: the environment's {k} is on {e['t'].device}, the agent on {self.ppo_device}"
+            # the same storage on every call (HumanoidEnv's fused step returns its own buffers): read in place, no copy
+            e['stable'] = e['stable'] and e['calls'] >= 2 and e['t'].is_contiguous() and k != 'dones'
+        self._rp_notes = seen
+        return out
+
+    def _step_results(self, obs, rewards, dones, infos):
+        """The tensors of one env_step a recorded step reads, by name."""
+        return {'obs': obs['obs'], 'rewards': rewards, 'dones': dones, 'terminate': infos['terminate'].to(self.ppo_device)}
+
+    def _program_inputs(self):
+        """(latents, rand_action_probs) of the recorded policy_act."""
+        return None, None
+
+    def _record_reset(self, rp):
+        """Step 1 of the recorded step: the done rows' reset inside a host callback, the observation into the agent's buffer."""
+        def reset_cb():
+            obs = CommonAgent._reset_done(self, rp['dones'])
+            rp['obs'].copy_(obs['obs'])
+        self.backend.host_call(self._guarded(rp, reset_cb))
+
+    def _guarded(self, rp, fn):
+        """A host callback of the recorded step.  A backend that replays a program keeps a callback's exception and lets the
+        rest of the program run, so a callback that raises first names no slot - the launches left in this replay store
+        nothing - and the callbacks behind it return at once: a refused replay neither stores nor steps the environment."""
+        def guarded():
+            if rp['refused']:
+                return
+            try:
+                fn()
+            except BaseException:
+                rp['refused'] = True
+                rp['word'].fill_(-(1 << 30))
+                raise
+        return guarded
+
+    def _program_fields(self, rp, res):
+        """Per-step experience fields beyond CommonAgent's as rows of the recorded rollout_store's table: what
+        _rollout_fields gives the eager loop, on the program's buffers (the latents are the head's to store)."""
+        return []
+
+    def _record_before_act(self, rp):
+        pass
+
+    def _record_program(self):
+        """One step of _play_steps_device as a launch program of the library, recorded once; the slot is the device word."""
+        E, be, eng, notes = self.experience, self.backend, self.engine, self._rp_notes
+        N, dev = self.num_actors * self.num_agents, self.ppo_device
+        rp = {'word': torch.zeros(1, dtype=torch.int32, device=dev), 'infos': None, 'refused': False,
+              'obs': torch.zeros(N, *self.obs_shape, dtype=torch.float32, device=dev)}
+        for k, e in notes.items():          # what env_step returns: the environment's own storage, or a buffer the callback fills
+            rp['step_' + k] = e['t'] if e['stable'] else torch.zeros_like(e['t'], memory_format=torch.contiguous_format)
+        rp['dones'] = rp['step_dones']
+        z, probs = self._program_inputs()
+        mean, std = eng.rollout_stats()
+        prog = rp['prog'] = be.prog_create()
+        be.prog_begin(prog)
+        try:
+            self._record_reset(rp)
+            self._record_before_act(rp)
+            eng.rollout_head(rp['obs'], z, mean, std, obses_out=E['obses'], latents_out=E.get('ase_latents') if z is not None else None,
+                             slot_dev=rp['word'])
+            res = eng.policy_act(rp['obs'], z, probs, self.action_rng, inputs_ready=True)
+
+            def take_step():
+                obs, rewards, dones, infos = self.env_step(res['actions'])
+                for k, t in self._step_results(obs, rewards, dones, infos).items():
+                    e, buf = notes[k], rp['step_' + k]
+                    if tuple(t.shape) != tuple(buf.shape) or t.dtype != buf.dtype or not self._on_agent_device(t):
+                        raise RuntimeError(f"rollout_program: env_step's {k} changed: {tuple(t.shape)} {t.dtype} on {t.device}, "
+                                           f"recorded {tuple(buf.shape)} {buf.dtype}")
+                    if not e['stable']:
+                        buf.copy_(t)
+                    elif t.data_ptr() != buf.data_ptr():
+                        raise RuntimeError(f"rollout_program: env_step's {k} was the environment's own storage when the step was "
+                                           "recorded and is another tensor now: the recorded launches would store stale rows")
+                rp['infos'] = infos
+            be.host_call(self._guarded(rp, take_step))
+            nobs = rp['step_obs']
+            eng.rollout_head(nobs, z, mean, std, critic_only=True)
+            next_values = eng.policy_forward(nobs, z, want=('value',), inputs_ready=True)['value']
+            fields = [(res[k], E[k]) for k in ('actions', 'neglogpacs', 'values', 'mus', 'sigmas')]
+            fields.append((nobs, E['next_obses']))
+            fields += self._program_fields(rp, res)
+            be.rollout_store(rp['dones'], slot=0, fields=fields, rewards=rp['step_rewards'], shift=self._reward_shift,
+                             scale=self._reward_scale, rewards_out=E['rewards'], dones_out=E['dones'], next_values=next_values,
+                             terminate=rp['step_terminate'], next_values_out=E['next_values'], cur_rewards=self.current_rewards,
+                             cur_lengths=self.current_lengths, meter=self._meter_words, max_size=self.games_to_track,
+                             done_ids_out=self._done_ids, slot_dev=rp['word'])
+            be.host_call(self._guarded(rp, lambda: self.algo_observer.process_infos(rp['infos'], self._done_ids)))
+            be.word_step(rp['word'], 1, 0)
+        finally:
+            be.prog_end(prog)
+        rp['baked'] = self._program_addresses()
+        return rp
+
+    def _program_addresses(self):
+        """Addresses a recording has baked in that the agent or the engine may re-allocate."""
+        eng, N, E = self.engine, self.num_actors * self.num_agents, self.experience
+        ts = [eng._scr('Xa', N, eng.actor[0].k_pad), eng._scr('act_actions', N, self.actions_num, torch.float32),
+              eng._scr('value_out', N, 1, torch.float32), E['obses'], E['dones'], self.current_rewards, self.current_lengths]
+        return [t.data_ptr() for t in ts]
+
+    def _play_steps_program(self):
+        """play_steps with config['rollout_program']: the step of _play_steps_device - reset of the done rows, (ASE) both
+        latent renewals, ONE rollout_head for the obses / latents store and the network inputs, policy_act on ready inputs,
+        env_step, the critic-only head and the value pass, ONE rollout_store, process_infos, the word's increment - recorded
+        once and replayed horizon_length times.  env_step, the environment's reset and process_infos run inside host
+        callbacks at their position of the sequence; the observation statistics are finalised once, before the first replay."""
+        be = self.backend
+        if self.obs is None:
+            self.obs = self.env_reset()
+        if self._rp is not None and self._program_addresses() != self._rp['baked']:
+            be.prog_destroy(self._rp['prog'])
+            self._rp = None
+        if self._rp is None:
+            self._rp = self._record_program()
+        rp = self._rp
+        rp['refused'] = False
+        rp['word'].zero_()
+        rp['dones'].zero_()                            # the reference's first env_reset([]) resets nothing
+        self._done_ids.fill_(-1)
+        self.engine.rollout_stats()
+        for n in range(self.horizon_length):
+            be.prog_launch(rp['prog'])
+        self._rollout_step = self.horizon_length - 1
+        self.obs, self.dones = {'obs': rp['step_obs']}, rp['dones']
         self._meter_host.written()
         return self._play_steps_tail()
 
@@ -1127,6 +1306,16 @@ class AMPAgent(CommonAgent):
         E = self.experience
         return [(infos['amp_obs'].to(self.ppo_device), E['amp_obs']), (res_dict['rand_action_mask'], E['rand_action_mask'])]
 
+    def _step_results(self, obs, rewards, dones, infos):
+        return dict(super()._step_results(obs, rewards, dones, infos), amp_obs=infos['amp_obs'].to(self.ppo_device))
+
+    def _program_inputs(self):
+        return None, self._rand_action_probs
+
+    def _program_fields(self, rp, res):
+        E = self.experience
+        return [(rp['step_amp_obs'], E['amp_obs']), (res['rand_action_mask'], E['rand_action_mask'])]
+
     def _record_train_batch_info(self, batch_dict, train_info):
         super()._record_train_batch_info(batch_dict, train_info)
         train_info['disc_rewards'] = batch_dict['disc_rewards']
@@ -1326,6 +1515,44 @@ class ASEAgent(AMPAgent):
         rng[1:2] += (self._done_ids.max() >= 0).to(rng.dtype)
         return obs
 
+    def _check_rollout_program(self):
+        super()._check_rollout_program()
+        env = getattr(self.vec_env, 'env', self.vec_env)
+        pb = env.task.progress_buf
+        assert self._on_agent_device(pb) and pb.is_contiguous(), \
+            f"rollout_program: progress_buf is on {pb.device}, the agent on {self.ppo_device} - the recorded due test reads it in place"
+
+    def _program_inputs(self):
+        return self._ase_latents, self._rand_action_probs
+
+    def _record_reset(self, rp):
+        """+ env_reset's latent part, as _reset_done has it: the launch is recorded, the stream-position line - torch
+        arithmetic - goes into a host callback.  The callback also holds the environment to the progress_buf it was recorded
+        with."""
+        env = getattr(self.vec_env, 'env', self.vec_env)
+        rp['progress_buf'] = env.task.progress_buf
+
+        def reset_cb():
+            if env.task.progress_buf.data_ptr() != rp['progress_buf'].data_ptr():
+                raise RuntimeError("rollout_program: the environment's progress_buf moved since the step was recorded")
+            obs = CommonAgent._reset_done(self, rp['dones'])
+            rp['obs'].copy_(obs['obs'])
+        self.backend.host_call(self._guarded(rp, reset_cb))
+        rng = self.engine.rng_state
+        self.backend.latent_renew(self._ase_latents, env_ids=self._done_ids, rng_state=rng, advance=False,
+                                  reset_steps=self._latent_reset_steps, steps_add=False, steps_low=int(self._latent_steps_min),
+                                  steps_high=int(self._latent_steps_max))
+
+        def bump():
+            rng[1:2] += (self._done_ids.max() >= 0).to(rng.dtype)
+        self.backend.host_call(self._guarded(rp, bump))
+
+    def _record_before_act(self, rp):
+        """_update_latents' launch without z2: the head that follows stores the latents."""
+        self.backend.latent_renew(self._ase_latents, rng_state=self.engine.rng_state, progress_buf=rp['progress_buf'],
+                                  reset_steps=self._latent_reset_steps, steps_add=True, steps_low=int(self._latent_steps_min),
+                                  steps_high=int(self._latent_steps_max))
+
     def _rand_steps(self, n):
         return torch.randint(int(self._latent_steps_min), int(self._latent_steps_max), (n,), device=self.ppo_device,
                              generator=self._gen, dtype=torch.int32)
@@ -1418,6 +1645,8 @@ class HRLAgent(CommonAgent):
     kind = 'ppo'
 
     def __init__(self, base_name, config):
+        assert not config.get('rollout_program', False), \
+            "rollout_program: the HRL agent's env_step is a loop of llc_steps simulator steps of its own and stays out of the recorded step"
         llc = config['llc_config']
         if not isinstance(llc, dict):
             import yaml

@@ -112,6 +112,9 @@ SIGNATURES = {
                               + [_p, _i64, _i, _i, _p, _p],
     "ase_hip_rollout_store": [_p, _i, _p, _f, _f, _p, _i64, _p, _i, _p, _i64, _p, _p, _i, _p, _i64, _p, _p, _p, _i, _p, _i64, _p,
                               _i, _i, _p, _i, _p],
+    "ase_hip_rollout_head": [_p, _i64, _i, _p, _i64, _i, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i, _p, _i64, _i64, _p, _i64,
+                             _i64, _i, _i, _p, _i, _p],
+    "ase_hip_word_step": [_p, _i, _i, _p],
     "ase_hip_hrl_latent": [_p, _i64, _p, _i64, _p, _i64, _i, _i, _i, _p],
     "ase_hip_hrl_llc_action": [_p, _i64, _p, _p, _p, _i64, _i, _i, _i, _p],
     "ase_hip_hrl_accum": [_p, _p, _i, _p, _i, _p, _i64, _f, _p, _i64, _i, _i, _i, _p, _p, _p, _p, _i, _p],

@@ -89,6 +89,14 @@ the CUDA (= HIP) dispatch key only: on CPU tensors PyTorch itself raises ``NotIm
                                                       list written in place) one environment step into experience slot `slot`:
                                                       what play_steps does behind env_step, without dones.nonzero
                                                       (learning/common_agent.py:267-293)
+  rollout_head(obs, z, mean, std, xa, xc, zc, zs, obses_out, z_out, slot, slot_dev=None) -> ()
+                                                      (the six outputs written in place) the head of one environment step in
+                                                      one launch: the obses / latents store into experience slot `slot`, the
+                                                      eval-mode normalisation into the actor's and critic's inputs and the
+                                                      latents' conversion into the concat block and the style input
+                                                      (learning/common_agent.py:253-262)
+  word_step(word, add, wrap) -> ()                    (word written in place) word = (word + add) mod wrap on the device: the
+                                                      step counter of a recorded rollout step
   hrl_latent(actions) -> z                            F.normalize(torch.clamp(actions, -1, 1), dim=-1): the latent a high-level
                                                       action selects, once per high-level step (learning/hrl_agent.py:89-93,235)
   hrl_llc_action(mu, low, high, act, clip) -> a       the LLC's padded head output -> the environment's action: clamp and
@@ -911,6 +919,37 @@ def rollout_store(dones: torch.Tensor, slot: int, n_slots: int, srcs: list[torch
 @rollout_store.register_fake
 def _(dones, slot, n_slots, srcs, dsts, rewards, shift, scale, rewards_out, dones_out, next_values, terminate, next_values_out,
       cur_rewards, cur_lengths, meter, max_size, done_ids_out, slot_dev=None):
+    return None
+
+
+@torch.library.custom_op('ase_hip::rollout_head', mutates_args=('xa', 'xc', 'zc', 'zs', 'obses_out', 'z_out'), device_types='cuda')
+def rollout_head(obs: torch.Tensor, z: torch.Tensor | None, mean: torch.Tensor | None, std: torch.Tensor | None,
+                 xa: torch.Tensor | None, xc: torch.Tensor | None, zc: torch.Tensor | None, zs: torch.Tensor | None,
+                 obses_out: torch.Tensor | None, z_out: torch.Tensor | None, slot: int, slot_dev: torch.Tensor | None = None) -> None:
+    """The head of one environment step in one launch (operands: see ase_hip_rollout_head): obs [n, D] normalised with mean /
+    std into xa / xc, the latents z [n, Z] converted into zc / zs, the raw rows copied into obses_out[slot] / z_out[slot]
+    ([n_slots, n, D] / [n_slots, n, Z]); slot_dev int32 [1]: the slot is the word read when the launch runs.  Every tensor is
+    passed by position, None where an output is left out."""
+    _check(obs.dim() == 2 and obs.dtype == torch.float32, 'rollout_head: obs f32 [n, D]')
+    _check(any(t is not None for t in (xa, xc, zc, zs, obses_out, z_out)), 'rollout_head: at least one output')
+    _check((xa is None and xc is None) or (mean is not None and std is not None), 'rollout_head: xa / xc need mean and std')
+    _backend().rollout_head(obs, z, mean, std, xa, xc, zc, zs, obses_out, z_out, slot, slot_dev)
+
+
+@rollout_head.register_fake
+def _(obs, z, mean, std, xa, xc, zc, zs, obses_out, z_out, slot, slot_dev=None):
+    return None
+
+
+@torch.library.custom_op('ase_hip::word_step', mutates_args=('word',), device_types='cuda')
+def word_step(word: torch.Tensor, add: int, wrap: int) -> None:
+    """word[0] = (word[0] + add) mod wrap on the device (wrap <= 0: no modulo); word int32 [1]."""
+    _check(word.dtype == torch.int32 and word.numel() == 1, 'word_step: word int32 [1]')
+    _backend().word_step(word, add, wrap)
+
+
+@word_step.register_fake
+def _(word, add, wrap):
     return None
 
 

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-/* (ase_hip_gemm_nt_ex, ase_hip_gemm_nt_stacked, ase_hip_disc_head_v2, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_proj_launch, ase_hip_motion_sync, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id, ase_hip_rollout_store, ase_hip_hrl_latent / ase_hip_hrl_llc_action / ase_hip_hrl_accum and ase_hip_env_pre_step / ase_hip_env_post_step were added WITHOUT a new version
+/* (ase_hip_gemm_nt_ex, ase_hip_gemm_nt_stacked, ase_hip_disc_head_v2, ase_hip_rms_normalize_multi_v2, ase_hip_apply_multi_v2, ase_hip_task_reset, ase_hip_proj_launch, ase_hip_motion_sync, ase_hip_latent_renew, ase_hip_amp_reset_due, ase_hip_amp_demo_fetch, ase_hip_gemm_tn_kernel_id, ase_hip_rollout_store, ase_hip_rollout_head / ase_hip_word_step, ase_hip_hrl_latent / ase_hip_hrl_llc_action / ase_hip_hrl_accum and ase_hip_env_pre_step / ase_hip_env_post_step were added WITHOUT a new version
  *  number: a library built before them passes this check and fails at symbol lookup instead - ase_amd/lib.py resolves every symbol at
  *  load time) */
 #define ASE_HIP_ABI_VERSION 9
@@ -589,6 +589,49 @@ int ase_hip_rollout_store(const int64_t* fields, int n_fields, const float* rewa
                           float* next_values_out, int64_t next_values_ss, float* cur_rewards, float* cur_lengths,
                           double* meter, int max_size, double* workspace, int64_t workspace_doubles, int32_t* done_ids_out,
                           int n_envs, int slot, const int32_t* slot_dev, int n_slots, void* stream);
+
+/* The head of one environment step in ONE launch (an addition to ABI 9, nothing else changed), over n rows of a
+ * raw f32 observation obs [n, D] read at its own pitch ld_obs, and - optional - the latents z [n, Z] at ld_z.  Every output
+ * is nullable, at least one is required; all pitches are in elements.
+ *   xa, xc       (x_dtype: ASE_F32 / ASE_BF16 / ASE_F16; the actor's and the critic's input buffer)
+ *                x[e * ld + j] = from_f32_plain<T>(y), y = ceil_nan(floor_nan((obs[e, j] - mean[j]) / std[j], -5), 5) for j < D:
+ *                an IEEE f32 subtraction, an IEEE f32 division, each rounded on its own, then torch.clamp, under which a NaN
+ *                stays NaN, then a plain RNE cast without saturation - rms_normalize_kernel's arithmetic operation by operation
+ *                (csrc/rms.hip:197-203 with store_opt, rms.hip:181-183; the 16-byte variant rms.hip:218-232).  mean, std f32
+ *                [D] are required with either.  Columns at and beyond D are not touched.
+ *   zc, zs       (x_dtype; the critic input's concat block and the style chain's input buffer)
+ *                zc[e * ld_zc + k] = zs[e * ld_zs + k] = from_f32<T>(z[e, k]) for k < Z: gather_rows_kernel's SATURATING
+ *                conversion (rms.hip:257) - half: clamped to +-65504 by a median of three, under which a NaN is stored as
+ *                -65504; bf16: RNE; f32: the bits.
+ *   obses_out, z_out  (f32, a row pitch and a slot stride each) the raw rows copied BITWISE into experience slot s:
+ *                obses_out[s * obses_slot_stride + e * ld_obses_out + j] = obs[e, j], z_out likewise from z - the
+ *                E['obses'][n].copy_(obs) of learning/common_agent.py:253-262 and the latents' store of
+ *                learning/ase_agent.py:66-100.  s = slot, or - slot_dev non-NULL (DEVICE int32 [1]) - the word read when the
+ *                launch runs, ase_hip_rollout_store's convention: a word outside [0, n_slots) makes the WHOLE call write
+ *                nothing, the normalised and converted outputs included.  With neither slot output the slot arguments (slot,
+ *                slot_dev, n_slots) are ignored.
+ * Each side moves 16 bytes per lane (16-bit outputs: one 8-byte store of four elements) or 4 bytes per lane, chosen on the
+ * host; the result is bitwise the same.  Observation side, 16 bytes when: D % 4 == 0, ld_obs % 4 == 0, obs 16-byte aligned,
+ * mean and std 16-byte aligned when xa or xc is given, every given xa / xc with ld % 4 == 0 and its base aligned to four
+ * elements (16 bytes f32, 8 bytes 16-bit), obses_out (when given) with ld_obses_out % 4 == 0, obses_slot_stride % 4 == 0 and a
+ * 16-byte aligned base.  Latent side: the same clauses on Z, ld_z, z, zc / zs and z_out.
+ * Refused, on the host, before any launch (ASE_EINVAL): no output at all; n <= 0 or D <= 0; NULL obs; a pitch below its
+ * width (ld_obs, ld_xa, ld_xc, ld_obses_out < D; ld_z, ld_zc, ld_zs, ld_z_out < Z); Z < 0 or Z > 0 without z; z_out, zc or zs
+ * given with Z == 0; xa or xc without mean and std; an x_dtype outside the three; and, with a slot output: a slot stride below
+ * n * pitch, n_slots <= 0, slot outside [0, n_slots) (checked also when slot_dev is given).
+ * Replaces, per rollout step: the obses copy, ase_hip_rms_normalize into two outputs, two ase_hip_gather_rows and the latent
+ * launch's z2 store. */
+int ase_hip_rollout_head(const float* obs, int64_t ld_obs, int D, const float* z, int64_t ld_z, int Z, const float* mean,
+                         const float* stdv, void* xa, int64_t ld_xa, void* xc, int64_t ld_xc, void* zc, int64_t ld_zc, void* zs,
+                         int64_t ld_zs, int x_dtype, float* obses_out, int64_t ld_obses_out, int64_t obses_slot_stride,
+                         float* z_out, int64_t ld_z_out, int64_t z_slot_stride, int n, int slot, const int32_t* slot_dev,
+                         int n_slots, void* stream);
+
+/* The step counter of a recorded rollout step: one lane computes *word = (*word + add) mod wrap - the sum in 64 bits, the
+ * result in [0, wrap) also for a negative sum; wrap <= 0: no modulo, the low 32 bits of the sum (two's complement) - and
+ * writes it with a plain vector store.  word: DEVICE int32 [1], the slot word ase_hip_rollout_store and ase_hip_rollout_head
+ * read; a launch program ends its step with this entry.  Refused on the host: NULL word. */
+int ase_hip_word_step(int32_t* word, int add, int wrap, void* stream);
 
 /* The glue of the HRL agent's inner loop (additions to ABI 9, nothing else changed): one high-level step wraps
  * llc_steps simulator steps around the frozen low-level controller (learning/hrl_agent.py:45-82).  Three entries, each ONE

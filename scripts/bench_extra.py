@@ -19,6 +19,8 @@ rollout-time inference path.  One JSON line per measurement on stdout.
   rollout-store: what play_steps does behind env_step for one step of config 2 (4096 envs, obs 253, actions 31, amp 1400, latents
           64, dones at 1/300): the host block (some thirty torch launches and dones.nonzero's round trip) next to the one
           rollout_store call, eager and replayed from a launch program (reported, not gated)
+  rollout-program: one play_steps() of config 2 on HumanoidEnv over PlaybackPhysics, the step issued call by call
+            (device_rollout) against the step recorded once as a launch program (rollout_program), alternated
   env-step: one step's environment work of the strike task with an AMP history of 10 at 4096 and 16384 environments: the
           composition of the separate entries (eager, and replayed from a launch program) and env_pre_step + env_post_step
   hrl-step: the glue of one high-level HRL step around the frozen controller's dense layers at config 4's size (4096 envs,
@@ -632,6 +634,67 @@ def env_step_case():
         be.prog_destroy(p_fused)
 
 
+def rollout_program_case(rollouts=7, warmup=3):
+    """One play_steps() of config 2 - 4096 environments, horizon 32, the real widths, ASE with device_latents and device_rollout -
+    on HumanoidEnv over PlaybackPhysics (device-resident: SyntheticVecEnv draws on the CPU and would hide the difference), the
+    step issued call by call (_play_steps_device) against the step recorded once as a launch program (rollout_program).  Two
+    agents of the same seed on environments of the same recording; host wall time of one play_steps() ending in a device
+    synchronise, after `warmup` rollouts of each (the program agent needs two before it replays), the two alternated inside one
+    process, `rollouts` of each."""
+    import statistics
+    from ase_amd import cfg as defaults
+    from ase_amd.backend import HipBackend
+    from ase_amd.learning import agents, models
+    from ase_amd.learning.network_builder import ASEBuilder
+    from tests import env_step_cases as CS
+    N, dev = 4096, 'cuda:0'
+    Gf, clips, A = CS.load()
+    small = CS.recording(Gf)
+    reps = (N + Gf['num_envs'] - 1) // Gf['num_envs']
+    frames = {k: v.repeat(1, reps, *([1] * (v.dim() - 2)))[:, :N].contiguous() for k, v in small.items()}
+
+    def agent(**extra):
+        be = HipBackend(dev)
+        env = CS.make_env(be, 'cuda', Gf, clips, A, None, False, True, frames=frames,
+                          cfg_update=dict(numAMPObsSteps=10, episodeLength=300))
+        net_p, cfg = defaults.get('ase')
+        torch.manual_seed(0)
+        b = ASEBuilder()
+        b.load(net_p)
+        cfg = dict(cfg)
+        info = {'observation_space': env.observation_space, 'action_space': env.action_space,
+                'amp_observation_space': env.amp_observation_space}
+        cfg.update(network=models.ModelASEContinuous(b), num_actors=N, device=dev, precision='bf16', backend=be, vec_env=env,
+                   env_info=info, print_stats=False, device_latents=True, device_rollout=True, **extra)
+        return agents.ASEAgent('rollout', cfg)
+    eager, prog = agent(), agent(rollout_program=True)
+    shapes = dict(obs=eager.obs_shape[0], actions=eager.actions_num, amp=eager.experience['amp_obs'].shape[-1],
+                  latents=eager.experience['ase_latents'].shape[-1], horizon=eager.horizon_length)
+    times = {'eager': [], 'program': []}
+
+    def one(ag, seed):
+        torch.manual_seed(seed)                   # (HumanoidEnv's host reset path draws from the global generator)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ag.play_steps()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+    for i in range(warmup):
+        one(eager, i)
+        one(prog, i)
+    assert prog._rp is not None
+    for i in range(rollouts):
+        times['eager'].append(one(eager, warmup + i))
+        times['program'].append(one(prog, warmup + i))
+    same = all(torch.equal(eager.experience[k], prog.experience[k]) for k in eager.experience)
+    for name, ts in times.items():
+        print(json.dumps({'measurement': 'rollout-program', 'path': name, 'envs': N, **shapes, 'precision': 'bf16',
+                          'environment': 'HumanoidEnv over PlaybackPhysics (fused step)', 'ms_per_play_steps_mean': round(statistics.mean(ts), 3),
+                          'ms_min': round(min(ts), 3), 'ms_max': round(max(ts), 3), 'ms_stdev': round(statistics.stdev(ts), 3),
+                          'rollouts': rollouts, 'warmup': warmup, 'program_entries': prog.backend.prog_size(prog._rp['prog']),
+                          'experience_equal_after_last_rollout': same}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--updates', type=int, default=4)
@@ -734,6 +797,8 @@ def main():
         hrl_step_case()
     if not args.only or 'env-step' in args.only.split(','):
         env_step_case()
+    if not args.only or 'rollout-program' in args.only.split(','):
+        rollout_program_case()
     if not args.only or 'ampobs' in args.only.split(','):
         # N2: observation production for 4096 envs (one frame + history push) and 5120 demo samples (512 x 10 steps)
         from ase_amd.backend import HipBackend
